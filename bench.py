@@ -8,6 +8,14 @@ n-k erasure pattern per stripe) + decode every stripe back to its k data rows.
 Inputs are resident in HBM before the timed region starts.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--stripes S]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, warm
+up, time exactly K steps, print the line.  `--full` adds what else the bench
+measures, after the headline's timed region: the cfg3 line (`secondary`) and
+the same-run CPU baseline (`cpu_baseline`; `--no-secondary` and
+`--no-cpu-baseline` drop either again).  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/<name>.npy (dump_outputs below).
 
 Multi-GPU: one process per GPU.  Stripes are independent codewords, so every
 rank encodes/decodes its own batch of S stripes with no data-path collective
@@ -336,9 +344,17 @@ def parse_args(argv=None):
                          "see CTX_STREAM); 2: that stream at the low and the "
                          "encode / decode stream at the high priority, so the "
                          "context blocks fill the encode's last round")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed region also run what "
+                         "else the bench measures: the cfg3 line of a cfg2 "
+                         "run (secondary) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as "
+                         "DIR/<name>.npy (at most 64 MB; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the cfg3 line the default (cfg2) run appends")
+                    help="with --full: skip the cfg3 line a cfg2 run appends")
     ap.add_argument("--cpu-seconds", type=float, default=1.0)
     ap.add_argument("--dry-run", action="store_true",
                     help="launch/shard/reduce/report on the CPU (gloo), no "
@@ -351,6 +367,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if args.gpus > 1:
@@ -388,14 +406,15 @@ def main(argv=None):
     res = run_config(args.cfg, args.stripes, bool(args.systematic), args.steps,
                      args.warmup, NC=max(1, args.chunks), n_streams=args.streams,
                      dist=dist, dev=dev, dry=dry, rank=rank, world=world,
-                     ctx_stream=args.ctx_stream, timed_events=args.timed_events)
+                     ctx_stream=args.ctx_stream, timed_events=args.timed_events,
+                     dump_dir=args.dump_outputs)
     out = report(res, args.cfg, world, args.steps, args.warmup, dry)
     ok = res["ok"]
-    # BASELINE.json configs[2] (k=64 n=1024 pkt=4KiB, 1024 stripes) in the
-    # same process, after the headline's timed region and in a timed region
-    # of its own: a driver-observed line for the high-fragmentation code
-    if (args.cfg == "cfg2" and not args.systematic and not args.no_secondary
-            and args.chunks == 1):
+    # --full: BASELINE.json configs[2] (k=64 n=1024 pkt=4KiB, 1024 stripes)
+    # in the same process, after the headline's timed region and in a timed
+    # region of its own: a line for the high-fragmentation code
+    if (args.full and args.cfg == "cfg2" and not args.systematic
+            and not args.no_secondary and args.chunks == 1):
         # (50 warmup steps, ~60 ms: a cfg3 step is 1.1 ms, and the GPU's
         # clock takes a few tens of ms of load to settle, tools/ramp.py)
         w3 = 50
@@ -409,10 +428,11 @@ def main(argv=None):
                 "decode_ctx_ms", "decode_GBps", "roundtrip_ok", "roofline",
                 "decode_roofline")}}
         ok = ok and r3["ok"]
-    # the CPU baseline runs on rank 0 after the timed regions and their final
-    # barriers (every rank's kernels are done), at every world size, so a
-    # multi-GPU line carries the same-run CPU number as the 1-GPU one
-    if rank == 0 and not args.no_cpu_baseline:
+    # --full: the CPU baseline runs on rank 0 after the timed regions and
+    # their final barriers (every rank's kernels are done), at every world
+    # size, so a multi-GPU line carries the same-run CPU number as the 1-GPU
+    # one
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(res["k"], res["m"], res["P"],
                                            res["sys"], args.cpu_seconds)
     if rank == 0:
@@ -434,14 +454,73 @@ def main(argv=None):
 CTX_STREAM = set()
 
 
+DUMP_SEED = 0x51D0D0  # of the fixed sample --dump-outputs takes
+# elements per dumped array at the most: (6 + 3 + 1) Mi float32 and 1 Mi
+# float64, 48 MiB in all
+DUMP_CODED, DUMP_DECODED, DUMP_COUNTS, DUMP_ENTRIES = 6 << 20, 3 << 20, 1 << 20, 1 << 20
+
+
+def _sample_u16(t, budget, rng):
+    """A u16 tensor (held as int16) as float32: all of it when it has at
+    most `budget` elements, else `budget` elements at sorted flat indices
+    drawn from `rng` (uniform, with repetition)."""
+    flat = t.reshape(-1)
+    if flat.numel() > budget:
+        idx = np.sort(rng.integers(0, flat.numel(), budget, dtype=np.int64))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return (flat.to(torch.int32) & 0xFFFF).to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(path, coded, dec, counts, entries, cap):
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    as <path>/<name>.npy.  Each array is whole when it fits its share of the
+    64 MB, else a fixed sample (DUMP_SEED), so two builds run with the same
+    arguments write the same elements of the same (seeded) batch:
+
+    coded.npy       float32  the encode's [S, n_out, P] u16 rows, flattened
+    decoded.npy     float32  the decode's [S, k, P] u16 rows, flattened
+    oor_counts.npy  float32  OOR marks per (stripe, output row) bucket
+    oor_entries.npy float64  [buckets, cap] the marked columns (of a sample
+                             of the buckets where they exceed their share),
+                             each bucket's valid entries ascending
+                             and -1 behind them (the kernels append marks in
+                             no fixed order and leave older steps' entries
+                             behind the count: a caller reads a bucket as the
+                             set of its first `count` entries)"""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    np.save(os.path.join(path, "coded.npy"), _sample_u16(coded, DUMP_CODED, rng))
+    np.save(os.path.join(path, "decoded.npy"), _sample_u16(dec, DUMP_DECODED, rng))
+    nb = counts.numel()
+
+    def buckets(budget):
+        if nb <= budget:
+            return counts, entries.view(nb, cap)
+        idx = np.sort(rng.choice(nb, budget, replace=False))
+        idx = torch.from_numpy(idx).to(counts.device)
+        return counts[idx], entries.view(nb, cap)[idx]
+
+    cnt, _ = buckets(DUMP_COUNTS)
+    np.save(os.path.join(path, "oor_counts.npy"),
+            cnt.cpu().numpy().astype(np.float32))
+    cnt, ent = (x.cpu().numpy().astype(np.int64)
+                for x in buckets(max(1, DUMP_ENTRIES // cap)))
+    big = np.iinfo(np.int64).max
+    ent = np.sort(np.where(np.arange(cap)[None, :] < cnt[:, None], ent, big), axis=1)
+    ent[ent == big] = -1
+    np.save(os.path.join(path, "oor_entries.npy"), ent.astype(np.float64))
+
+
 def run_config(cfg, stripes, sys_, steps, warmup, NC=1, n_streams=2, dist=None,
-               dev=None, dry=False, rank=0, world=1, ctx_stream=None, timed_events=False):
+               dev=None, dry=False, rank=0, world=1, ctx_stream=None, timed_events=False,
+               dump_dir=None):
     """Build one configuration's synthetic batch in HBM, run `warmup`
     untimed steps, check the round trip, then time exactly `steps` steps
     between barriers + device synchronisations (max over ranks).  One step =
     encode every stripe (OOR recorded) + build the per-stripe decode
     contexts (a random n-k erasure pattern per stripe) + decode every
-    stripe back to its k data rows."""
+    stripe back to its k data rows.  `dump_dir`: rank 0 writes the last
+    timed step's outputs there (dump_outputs)."""
     k, m, pkt_bytes, S = CONFIGS[cfg]
     if stripes:
         S = stripes
@@ -588,6 +667,13 @@ def run_config(cfg, stripes, sys_, steps, warmup, NC=1, n_streams=2, dist=None,
     elapsed = time.perf_counter() - t0
     # and again after the timed steps (their last decode), outside the timer
     ok = ok and check()
+    if dump_dir and rank == 0:
+        if dry:
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, "data.npy"),
+                    data.numpy().astype(np.float64))
+        else:
+            dump_outputs(dump_dir, coded, dec, counts, entries, cap)
     if dist:
         elapsed, ok = reduce_over_ranks(dist, elapsed, ok, dev)
     enc_ms = dec_ms = ctx_ms = None  # dry run: no kernels

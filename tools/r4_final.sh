@@ -15,7 +15,7 @@ if [ "$PART" = main ]; then
   timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log
   timeout -k 10 120 python3 -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || exit $?
-  timeout -k 10 300 python3 bench.py > $O/bench.log 2>&1 || exit $?
+  timeout -k 10 300 python3 bench.py --full > $O/bench.log 2>&1 || exit $?
   line $O/bench.log cfg2
   timeout -k 10 300 python3 bench.py --systematic --no-cpu-baseline > $O/bench_sys.log 2>&1 || exit $?
   line $O/bench_sys.log cfg2_sys

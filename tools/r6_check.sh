@@ -14,7 +14,7 @@ if [ -z "$R6_SKIP_TESTS" ]; then
   tail -1 $O/pytest_gpu.log
   timeout -k 10 120 python3 -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || exit $?
 fi
-timeout -k 10 300 python3 bench.py > $O/bench.log 2>&1 || { cat $O/bench.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $O/bench.log 2>&1 || { cat $O/bench.log; exit 1; }
 python3 tools/summ.py $O
 for c in $CFGS; do
   [ $c = cfg2 ] && continue
