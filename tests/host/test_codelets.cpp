@@ -9,6 +9,10 @@
 //     plain matrix-vector product, checking the 32-bit accumulator bound,
 //  4. the matrix-core path (pack_mf_dword operand tiles x byte planes, the
 //     three int32 GEMMs of matrix_mfma_kernel and its epilogue) likewise.
+//  3 and 4 run on all-0, all-65535 and random inputs, whose sums are a random
+//  walk, and on sign-matched inputs (craft_x) that drive one row's dot2 sum,
+//  D2, or D0 and D1 to the most valid symbols allow.
+#include <algorithm>
 #include <cassert>
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +108,62 @@ static void test_dft(std::mt19937_64& g)
                 plan_folds<K, LO, HI>());
 }
 
+// Sign-matched input for the output whose row-scaled canonical coefficients
+// are c[0 .. kin): every term of the targeted sum has the same sign.
+//   mode 0 / 1  dot+-: x = 65535 where balanced(c) > 0, else 0 (negated:
+//               swapped): sum c (x - 32768) = +-sum |c| w, w in {32767, 32768}
+//   mode 2 / 3  d2+-:  h' = 127 where b > 0 else -128, l' = 127 where a > 0
+//               else -128 (c = 256 a + b): |D2| = sum |b| w_h + |a| w_l
+//   mode 4 / 5  d01+-: h' follows the sign of a, l' that of b: |D0|, |D1|
+// x = 256 h' + l' + 32896 is a valid u16 for every byte pair.
+static std::vector<uint32_t> craft_x(const int32_t* c, int kin, int mode)
+{
+    std::vector<uint32_t> x(kin);
+    const bool neg = mode & 1;
+    for (int i = 0; i < kin; i++) {
+        if (mode < 2) {
+            x[i] = ((balanced(static_cast<uint32_t>(c[i])) > 0) != neg) ? 65535u : 0u;
+            continue;
+        }
+        int32_t a, b;
+        split_i8(static_cast<uint32_t>(c[i]), a, b);
+        const int32_t ch = mode < 4 ? b : a, cl = mode < 4 ? a : b;
+        const int h = ((ch > 0) != neg) ? 127 : -128, l = ((cl > 0) != neg) ? 127 : -128;
+        x[i] = static_cast<uint32_t>(256 * h + l + 32896);
+    }
+    return x;
+}
+
+// Plant rows at the ends of the byte split into M (R x kin): (a, b) =
+// (-128, -128) / (127, 127) alternating along row 0, (-128, 127) /
+// (127, -128) along the last row.  The signs alternate, so all-0, all-65535
+// and random inputs cancel on them; only a sign-matched input (craft_x) adds
+// them up, to the bounds themselves: |D2| = 2 kin 128^2 less the 127s.
+static void plant_extreme_rows(std::vector<uint32_t>& M, int R, int kin)
+{
+    if (R < 2 || kin < 2)
+        return;
+    for (int i = 0; i < kin; i++) {
+        M[i] = i & 1 ? 32639u : 32641u;
+        M[static_cast<size_t>(R - 1) * kin + i] = i & 1 ? 32384u : 32896u;
+    }
+}
+
+// Rows to craft against: the first, the last, and the first that needed a
+// row scale (rscale != 1), if any.
+static std::vector<int> craft_rows(const int32_t* rscale, int R)
+{
+    std::vector<int> rows{0};
+    if (R > 1)
+        rows.push_back(R - 1);
+    for (int t = 1; t + 1 < R; t++)
+        if (rscale[t] != 1) {
+            rows.push_back(t);
+            break;
+        }
+    return rows;
+}
+
 static void test_matrix(std::mt19937_64& g)
 {
     for (int kin : {1, 2, 3, 16, 33, 64, 128}) {
@@ -115,14 +175,13 @@ static void test_matrix(std::mt19937_64& g)
             v = mode == 0 ? 32767u + static_cast<uint32_t>(g() % 4)
                           : static_cast<uint32_t>(g() % 65537);
         }
+        plant_extreme_rows(M, R, kin);
         const MatLayout L{R, kin, KP};
         std::vector<int32_t> blk(L.words());
         for (int t = 0; t < R; t++)
             pack_row(M.data() + static_cast<size_t>(t) * kin, L, t, blk.data());
-        for (int trial = 0; trial < 50; trial++) {
-            std::vector<uint32_t> x(kin);
-            for (auto& v : x)
-                v = trial == 0 ? 0u : trial == 1 ? 65535u : static_cast<uint32_t>(g() % 65536);
+        long long reach[2] = {0, 0};  // max |acc + x0 c0 + x1 c1|: random / crafted trials
+        auto run = [&](const std::vector<uint32_t>& x, int kind) {
             for (int t = 0; t < R; t++) {
                 // device sequence: acc = kcorr; acc = fold(dot2(x', m, acc))
                 long long acc = blk[static_cast<size_t>(R) * KP + t];
@@ -137,6 +196,7 @@ static void test_matrix(std::mt19937_64& g)
                     const long long s = acc + static_cast<long long>(x0) * m0 +
                                         static_cast<long long>(x1) * m1;
                     CHECK(s >= -2147483648LL && s <= 2147483647LL, "dot2 overflow");
+                    reach[kind] = std::max(reach[kind], s < 0 ? -s : s);
                     acc = fold(static_cast<int32_t>(s));
                 }
                 int32_t y = fold(static_cast<int32_t>(acc));
@@ -152,7 +212,18 @@ static void test_matrix(std::mt19937_64& g)
                 CHECK(y >= -1 && y <= 65536, "T range");
                 CHECK(canon64(y) == static_cast<uint32_t>(ref), "matrix kin=%d t=%d", kin, t);
             }
+        };
+        for (int trial = 0; trial < 50; trial++) {
+            std::vector<uint32_t> x(kin);
+            for (auto& v : x)
+                v = trial == 0 ? 0u : trial == 1 ? 65535u : static_cast<uint32_t>(g() % 65536);
+            run(x, 0);
         }
+        for (int t : craft_rows(blk.data() + L.rscale(), R))
+            for (int mode = 0; mode < 6; mode++)
+                run(craft_x(blk.data() + L.plain() + static_cast<size_t>(t) * kin, kin, mode), 1);
+        std::printf("dot2 kin=%d: max |step sum| random %lld, crafted %lld\n", kin, reach[0],
+                    reach[1]);
     }
     std::printf("matrix dot2 path ok\n");
 }
@@ -177,6 +248,7 @@ static void test_matrix_mfma(std::mt19937_64& g)
                     : mode == 2 ? 65536u - static_cast<uint32_t>(g() % 300)
                                 : static_cast<uint32_t>(g() % 65537);
             }
+            plant_extreme_rows(M, R, kin);
             std::vector<int32_t> blk(L.words());
             for (int t = 0; t < R; t++)
                 pack_row(M.data() + static_cast<size_t>(t) * kin, L, t, blk.data());
@@ -208,10 +280,8 @@ static void test_matrix_mfma(std::mt19937_64& g)
                     CHECK(mf_entry(L, blk.data() + L.mf(), t, i) ==
                               static_cast<uint32_t>(blk[L.plain() + static_cast<size_t>(t) * kin + i]),
                           "mf_entry kin=%d t=%d i=%d", kin, t, i);
-            for (int trial = 0; trial < 30; trial++) {
-                std::vector<uint32_t> x(kin);
-                for (auto& v : x)
-                    v = trial == 0 ? 0u : trial == 1 ? 65535u : static_cast<uint32_t>(g() % 65536);
+            long long reach[2] = {0, 0};  // max |D2|: random / crafted trials
+            auto run = [&](const std::vector<uint32_t>& x, int kind) {
                 for (int t = 0; t < R; t++) {
                     const int rb = t / 16;
                     // device: acc1 starts at kmf[t]; rows past kin hold a
@@ -229,6 +299,7 @@ static void test_matrix_mfma(std::mt19937_64& g)
                     }
                     for (long long d : D)
                         CHECK(d >= -2147483648LL && d <= 2147483647LL, "mfma acc overflow");
+                    reach[kind] = std::max(reach[kind], D[2] < 0 ? -D[2] : D[2]);
                     // KS >= 16 (k > 128): the device folds D2 before the shift (KS = 40:
                     // the two K chunks accumulate into the same D0, D1, D2)
                     const long long d2 = KS >= 16 ? fold(static_cast<int32_t>(D[2])) : D[2];
@@ -244,7 +315,20 @@ static void test_matrix_mfma(std::mt19937_64& g)
                     CHECK(y >= -1 && y <= 65536, "mfma T range");
                     CHECK(canon64(y) == static_cast<uint32_t>(ref), "mfma kin=%d R=%d t=%d", kin, R, t);
                 }
+            };
+            for (int trial = 0; trial < 30; trial++) {
+                std::vector<uint32_t> x(kin);
+                for (auto& v : x)
+                    v = trial == 0 ? 0u : trial == 1 ? 65535u : static_cast<uint32_t>(g() % 65536);
+                run(x, 0);
             }
+            for (int t : craft_rows(blk.data() + L.rscale(), R))
+                for (int mode = 0; mode < 6; mode++)
+                    run(craft_x(blk.data() + L.plain() + static_cast<size_t>(t) * kin, kin, mode),
+                        1);
+            if (R == kin)
+                std::printf("mfma kin=%d KS=%d: max |D2| random %lld, crafted %lld\n", kin, KS,
+                            reach[0], reach[1]);
         }
     }
     std::printf("matrix mfma path ok\n");

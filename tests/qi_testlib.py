@@ -289,3 +289,228 @@ def check_windows_vs_oracle(k, m, sys_, data, outs, oor, cnt, wins, missing=None
             ok, o_dec = oracle_decode_blocks(k, m, sys_, o_out, o_oor, o_cnt,
                                              missing, d)
             assert ok == 1 and (dec[:, 2 * lo:2 * hi] == o_dec).all(), (lo, hi)
+
+
+# ------------------------------------------------------------------------
+# Inputs at the accumulator extremes.  The codes are linear over GF(65537)
+# and their matrices are known, so for any output row the input column that
+# drives that row's accumulators as far as valid data can is computed, not
+# hoped for (uniform random symbols make the sums a random walk, an order of
+# magnitude short of the bounds the kernels' range arguments rest on).
+
+_CTX_BYTES = 4 + 16 * 4096 + 64   # >= sizeof(qo_ctx)
+DOT_MODES = ("dot+", "dot-")
+MFMA_MODES = ("d2+", "d2-", "d01+", "d01-")
+ALL_MODES = DOT_MODES + MFMA_MODES
+
+
+def balanced_np(M):
+    """gf65537.h balanced(): the representative in [-32768, 32768]."""
+    M = np.asarray(M, np.int64)
+    return np.where(M > 32768, M - Q, M)
+
+
+def generator_matrix(k, m, sys_):
+    """(n_outputs, k) int64, entries 0..65536: column i is the encode of unit
+    vector i (systematic: the parity rows, through an encode context over ids
+    0..k-1)."""
+    o = oracle()
+    c = codec(k, m, sys_)
+    first = k if sys_ else 0
+    cw = (C.c_uint32 * c.n)()
+    din = (C.c_uint32 * k)()
+    ctx = C.create_string_buffer(_CTX_BYTES)
+    if sys_:
+        assert o.qo_ctx_init(C.byref(c), ctx, (C.c_uint32 * k)(*range(k))) == 0
+    G = np.zeros((c.n_outputs, k), np.int64)
+    for i in range(k):
+        din[i] = 1
+        o.qo_encode_column(C.byref(c), ctx if sys_ else None, din, cw)
+        din[i] = 0
+        G[:, i] = np.frombuffer(cw, np.uint32)[first:first + c.n_outputs]
+    return G
+
+
+def decode_matrix(k, m, sys_, ids):
+    """(k, k) int64: column i is the decode of unit vector i received at
+    ids[i].  Column by column, not through the block API: that stores u16
+    and loses the entries equal to 65536."""
+    o = oracle()
+    c = codec(k, m, sys_)
+    ctx = C.create_string_buffer(_CTX_BYTES)
+    assert o.qo_ctx_init(C.byref(c), ctx,
+                         (C.c_uint32 * k)(*[int(v) for v in ids])) == 0
+    win = (C.c_uint32 * k)()
+    dout = (C.c_uint32 * k)()
+    M = np.zeros((k, k), np.int64)
+    for i in range(k):
+        win[i] = 1
+        o.qo_decode_column(C.byref(c), ctx, win, dout)
+        win[i] = 0
+        M[:, i] = np.frombuffer(dout, np.uint32)
+    return M
+
+
+def matvec_mod(M, X):
+    """M @ X mod q for entries 0..65536, exact: every partial sum is an
+    integer below 2^33 * rows < 2^53, so the float64 product is exact."""
+    assert M.shape[1] < (1 << 19)
+    Y = np.asarray(M, np.float64) @ np.asarray(X, np.float64)
+    return Y.astype(np.int64) % Q
+
+
+def split_i8_np(M):
+    """matrix_pack.h split_i8: canonical c -> (a, b) in [-128, 127] with
+    c = 256 a + b mod q (every residue but balanced 32640)."""
+    v = balanced_np(M)
+    v = np.where(v > 32639, v - Q, v)
+    b = ((v + 128) & 255) - 128
+    a = (v - b) // 256
+    return a, b
+
+
+def coef_ok_np(M):
+    v = balanced_np(M)
+    return (np.abs(v) <= 32766) & (v != 32640)
+
+
+def row_scale(row):
+    """pack_row's search: the smallest s >= 2 whose inverse is within
+    |s^-1| <= 32766 and that makes every s * row entry coef_ok (1: the row
+    needs no scale)."""
+    row = np.asarray(row, np.int64)
+    if coef_ok_np(row).all():
+        return 1
+    s = 1
+    while True:
+        s += 1
+        si = pow(s, Q - 2, Q)
+        if abs(si - Q if si > 32768 else si) > 32766:
+            continue
+        if coef_ok_np(row * s % Q).all():
+            return s
+
+
+def extreme_targets(M, n_spread=8, max_scaled=48):
+    """[(row, s)]: every row that needs a row scale (at most max_scaled), raw
+    (s = 1) and scaled, then n_spread rows spread evenly over the matrix --
+    row 0 and the last row (of the last 16-row block) among them."""
+    R = M.shape[0]
+    need = np.flatnonzero(~coef_ok_np(M).all(axis=1))[:max_scaled]
+    tg = []
+    for t in need:
+        tg += [(int(t), 1), (int(t), row_scale(M[t]))]
+    for t in sorted(set(np.linspace(0, R - 1, min(n_spread, R)).round().astype(int))):
+        tg.append((int(t), 1))
+    return tg
+
+
+def craft_column(row, mode):
+    """One input column (values 0..65535) that drives the accumulators of
+    the output whose canonical coefficients are `row` to the `mode` extreme:
+      dot+-  x = 65535 where balanced(c) > 0 else 0 (negated: swapped): every
+             v_dot2 step and every butterfly sum feeding the output adds in
+             one direction, sum c (x - 32768) = +-sum |c| w, w in {32767, 32768}
+      d2+-   bytes h' = 127 where b > 0 else -128, l' = 127 where a > 0 else
+             -128 (c = 256 a + b): |D2| = sum |b| w_h + |a| w_l, w in {127, 128}
+      d01+-  h' follows the sign of a, l' that of b: |D0| and |D1| together
+    x = 256 h' + l' + 32896 is a valid u16 for every byte pair."""
+    row = np.asarray(row, np.int64)
+    neg = mode.endswith("-")
+    if mode.startswith("dot"):
+        pos = balanced_np(row) > 0
+        return np.where(pos ^ neg, 65535, 0).astype(np.int64)
+    a, b = split_i8_np(row)
+    ch, cl = (b, a) if mode.startswith("d2") else (a, b)
+    h = np.where((ch > 0) ^ neg, 127, -128)
+    l = np.where((cl > 0) ^ neg, 127, -128)
+    return (256 * h + l + 32896).astype(np.int64)
+
+
+def craft_columns(M, targets, modes, cols):
+    """(k, cols) int64 columns, one per (target, mode) pair, cycling through
+    the pairs; `targets` as extreme_targets gives them (a scaled target is
+    crafted against s * row).  Round r gives target i the mode i + r, so a
+    prefix shorter than all pairs still holds every target and every mode.
+    Returns (X, meta), meta[j] = (row, s, mode) of column j."""
+    pairs = [(t, s, modes[(i + r) % len(modes)])
+             for r in range(len(modes)) for i, (t, s) in enumerate(targets)]
+    X = np.zeros((M.shape[1], cols), np.int64)
+    meta = []
+    for j in range(cols):
+        t, s, mode = pairs[j % len(pairs)]
+        X[:, j] = craft_column(M[t] * s % Q, mode)
+        meta.append((t, s, mode))
+    return X, meta
+
+
+def model_sums(row, X):
+    """The kernels' integer sums for one output row over the columns of X
+    (k, n), before any fold: the dot2 sum of c (x - 32768) with balanced c,
+    and the matrix cores' D0 = sum a h', D1 = sum b l', D2 = sum (b h' + a l')
+    over the byte planes h' = (x >> 8) - 128, l' = (x & 255) - 128."""
+    row = np.asarray(row, np.int64)
+    X = np.asarray(X, np.int64)
+    a, b = split_i8_np(row)
+    h = (X >> 8) - 128
+    l = (X & 255) - 128
+    return {"dot": balanced_np(row) @ (X - 32768),
+            "d0": a @ h, "d1": b @ l, "d2": b @ h + a @ l}
+
+
+def closed_form(row, mode):
+    """What craft_column(row, mode) must reach: {sum name: value}."""
+    row = np.asarray(row, np.int64)
+    sg = -1 if mode.endswith("-") else 1
+
+    def l1(c, wpos, wneg):
+        c = sg * c
+        return sg * int((np.where(c > 0, c * wpos, 0) - np.where(c < 0, c * wneg, 0)).sum())
+    if mode.startswith("dot"):
+        return {"dot": l1(balanced_np(row), 32767, 32768)}
+    a, b = split_i8_np(row)
+    if mode.startswith("d2"):
+        return {"d2": l1(b, 127, 128) + l1(a, 127, 128)}
+    return {"d0": l1(a, 127, 128), "d1": l1(b, 127, 128)}
+
+
+_PATTERN_PLANES = (0x0000, 0xFFFF, 0x8000, 0x7FFF, 0x8080, 0x7F7F, 0x807F, 0x7F80)
+
+
+def pattern_rows(k, P):
+    """(k, P) uint16: column j holds pattern j mod 10 down its k rows -- the
+    constant planes 0x0000, 0xFFFF, 0x8000, 0x7FFF, 0x8080, 0x7F7F, 0x807F,
+    0x7F80 (the ends of the u16 range and of both byte planes), 0x0000 /
+    0xFFFF alternating by row parity, and by row index mod 32 < 16."""
+    i = np.arange(k)[:, None]
+    j = np.arange(P)[None, :] % (len(_PATTERN_PLANES) + 2)
+    X = np.asarray(_PATTERN_PLANES + (0, 0), np.int64)[j] + 0 * i
+    X = np.where(j == 8, np.where(i % 2 == 0, 0x0000, 0xFFFF), X)
+    X = np.where(j == 9, np.where(i % 32 < 16, 0x0000, 0xFFFF), X)
+    return X.astype(np.uint16)
+
+
+def craft_received(k, m, sys_, ids, cols, rng, n_spread=8):
+    """Decode-side extremes inside valid use: received symbols r crafted
+    against decode_matrix(ids) (every 8th column with its one to three
+    largest-|c| entries at 65536, the true maximum of a received symbol,
+    which arrives as an OOR mark; systematic: parity positions only, data
+    rows carry no marks), d = M r mod q their data.  A column whose data
+    holds a 65536 is not representable and is replaced by random data.
+    Returns (d (k, cols) uint16, r (k, cols) int64 as received, kept (cols)
+    bool, M, meta)."""
+    ids = np.asarray(ids, np.int64)
+    M = decode_matrix(k, m, sys_, ids)
+    r, meta = craft_columns(M, extreme_targets(M, n_spread), ALL_MODES, cols)
+    markable = np.flatnonzero(ids >= k) if sys_ else np.arange(k)
+    for n, j in enumerate(range(0, cols, 8)):
+        t, s, _ = meta[j]
+        mag = np.abs(balanced_np(M[t] * s % Q))[markable]
+        top = markable[np.argsort(-mag, kind="stable")[:1 + n % 3]]
+        r[top, j] = 65536
+    d = matvec_mod(M, r)
+    kept = (d < 65536).all(axis=0)
+    nrep = int((~kept).sum())
+    if nrep:
+        d[:, ~kept] = rng.integers(0, 65536, (k, nrep))
+    return d.astype(np.uint16), r, kept, M, meta
