@@ -128,6 +128,29 @@ class RsFnt {
                                 std::vector<bool>& wanted_idxs,
                                 size_t block_size_bytes);
 
+    // Fused repair: rebuild the fragments `targets` (ids in the decode's id
+    // space: systematic f < n_data is data row f, otherwise parity
+    // f - n_data; non-systematic: coded row f) straight from the first
+    // n_data present fragments, chosen as decode_blocks_vertical chooses
+    // them, in one pass on the device (qi_gpu_repair).  out_bufs[j]
+    // receives target j (block_size_bytes each) and out_props[j] its marks
+    // (ascending, counts exact; none for a data row).  Every target must be
+    // flagged missing.  Returns false when fewer than n_data fragments are
+    // present.  Throws std::invalid_argument where repair_supported() is
+    // false, or a target is present or out of range.
+    bool repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                std::vector<uint8_t*>& parities_bufs,
+                                std::vector<Properties>& parities_props,
+                                std::vector<int>& missing_idxs,
+                                const std::vector<int>& targets,
+                                std::vector<uint8_t*>& out_bufs,
+                                std::vector<Properties>& out_props,
+                                size_t block_size_bytes);
+    // n_data <= 256, 1 <= n_targets <= min(64, n_parities), and a block that
+    // fits the single-chunk device staging with every fragment row of the
+    // code in its own slot (at most 256 MiB of rows)
+    bool repair_supported(size_t n_targets, size_t block_size_bytes) const;
+
     void encode_streams_vertical(
         const std::vector<std::istream*>& input_data_bufs,
         std::vector<std::ostream*>& output_parities_bufs,

@@ -179,6 +179,57 @@ int qi_gpu_take_error(qi_plan* plan);
  * profiles.  The string is per calling thread, valid until its next call. */
 const char* qi_gpu_kernels(const qi_plan* plan, long long words);
 
+/* ---- Fused fragment repair: rebuild lost fragments straight from k
+ * received ones, in one pass (a decode followed by an encode writes the k
+ * data rows to memory and reads them back to compute every output).
+ * Fragment f of a column is P(r^f) in both code types, so target t is the
+ * Lagrange evaluation out_t = sum_i L_i(r^t) in[ids[i]]: one R x k matrix
+ * per stripe (R = n_targets), applied by the kernels of the decode.
+ *
+ * Ids and targets are fragment ids in the decode's id space (systematic:
+ * f < k is data row f, otherwise parity f - k; non-systematic: coded row f),
+ * and the received rows and their OOR buckets are addressed exactly as
+ * qi_gpu_decode addresses them.  1 <= n_targets <= min(64, m)
+ * (QI_REPAIR_MAX_TARGETS), the same count for every stripe of a call; the
+ * targets themselves may differ per stripe.  Output row j of a stripe is target j
+ * (d_out + s*oss + j*ors), and its marks go to bucket slot j (slots =
+ * n_targets): a rebuilt coded symbol equal to 65536 is stored as 0 and
+ * recorded, as by qi_gpu_encode; rebuilt data rows never hold one.  Clear
+ * d_out_counts first (qi_gpu_oor_clear); NULL skips the recording.
+ *
+ * Supported for plans with k <= 256, at any width and row alignment (the
+ * matrix cores take the whole 1024-column tiles of addressable rows, the
+ * dot2 kernel the tail and everything else).  For k > 256
+ * qi_gpu_repair_ctx_bytes returns 0 and the two calls return
+ * QI_ERR_UNSUPPORTED; n_targets out of range returns -1 (nothing is
+ * launched).  A context is valid for the `words` and n_targets it was built
+ * with.  Bad ids raise bit 2 of qi_gpu_take_error and leave the stripe's
+ * context unusable: received ids repeated or not below n, a target not
+ * below k + m, a repeated target, or a target that is also a received id.
+ * An input bucket over its capacity raises bit 1, as for a decode.  With
+ * NULL counts at context time the marks are read from the buckets given to
+ * qi_gpu_repair. */
+#define QI_REPAIR_MAX_TARGETS 64
+#define QI_ERR_UNSUPPORTED (-5)
+size_t qi_gpu_repair_ctx_bytes(const qi_plan* plan, int n_targets, int n_stripes,
+                               long long words);
+int qi_gpu_repair_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][k]*/,
+                      const uint16_t* d_targets /*[S][R]*/, int n_targets,
+                      int n_stripes, const uint32_t* d_oor_counts,
+                      const uint32_t* d_oor_entries, int oor_cap,
+                      long long words, void* d_ctx, void* stream);
+int qi_gpu_repair(qi_plan* plan, const void* d_ctx, int n_targets,
+                  const uint16_t* d_data, long long dss, long long drs,
+                  const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_in_counts, const uint32_t* d_in_entries,
+                  int in_cap, uint16_t* d_out, long long oss, long long ors,
+                  uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                  long long words, int n_stripes, void* stream);
+/* Names of the kernels a repair of n_targets fragments over `words` columns
+ * launches (rows at 8-byte aligned offsets), as "repair=<kernels>"; "" when
+ * unsupported.  Per calling thread, valid until its next call. */
+const char* qi_gpu_repair_kernels(const qi_plan* plan, int n_targets, long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -200,6 +251,22 @@ int qi_fec_decode_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
                          const uint32_t* oor, const uint32_t* oor_count,
                          uint32_t oor_cap, const int* missing,
                          const int* wanted, size_t block_bytes);
+
+/* Fused repair of n_targets missing fragments (RsFnt::repair_blocks_vertical,
+ * include/qi_fec.hpp): `targets` are fragment ids in the decode's id space
+ * (systematic: f < k data row f, else parity f - k; non-systematic: coded row
+ * f), each flagged in `missing`; the first k present fragments are used, as
+ * by qi_fec_decode_blocks.  out[j] receives target j (block_bytes), its marks
+ * ascending in out_oor[j * out_cap ..] with the exact count in out_count[j].
+ * `data` may be NULL for non-systematic codes.  Returns 1 rebuilt, 0 fewer
+ * than k fragments, -1 error (a target present or out of range), -2 shape not
+ * supported (k > 256, n_targets outside 1 .. min(64, m), or a block wider
+ * than the single-chunk staging): decode and encode instead. */
+int qi_fec_repair_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
+                         const uint32_t* oor, const uint32_t* oor_count,
+                         uint32_t oor_cap, const int* missing, const int* targets,
+                         int n_targets, uint8_t** out, uint32_t* out_oor,
+                         uint32_t* out_count, uint32_t out_cap, size_t block_bytes);
 
 /* Stream API (encode_streams_vertical / decode_streams_vertical,
  * src/fec_base.h:463-542, 898-1048) over caller memory: each fragment is a

@@ -55,6 +55,11 @@ def _declare(lib):
         "qi_gpu_decode_ctx_packed": (I, [V, V, V, I, V, V, I, LL, V, V]),
         "qi_gpu_decode_packed": (I, [V, V, V, LL, LL, V, V, I, V, LL, LL, LL,
                                      I, V]),
+        "qi_gpu_repair_ctx_bytes": (SZ, [V, I, I, LL]),
+        "qi_gpu_repair_ctx": (I, [V, V, V, I, I, V, V, I, LL, V, V]),
+        "qi_gpu_repair": (I, [V, V, I, V, LL, LL, V, LL, LL, V, V, I, V, LL,
+                              LL, V, V, I, LL, I, V]),
+        "qi_gpu_repair_kernels": (C.c_char_p, [V, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -63,6 +68,8 @@ def _declare(lib):
         "qi_fec_n_outputs": (I, [V]),
         "qi_fec_encode_blocks": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32]),
         "qi_fec_decode_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
+        "qi_fec_repair_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, c_u8pp, V,
+                                     V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
                                       c_u8pp]),
@@ -302,6 +309,77 @@ class Plan:
             raise RuntimeError(f"qi_gpu_decode_packed failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    ERR_UNSUPPORTED = -5  # QI_ERR_UNSUPPORTED
+
+    def repair_kernels(self, n_targets, words):
+        """'repair=<kernels>' a repair of n_targets fragments launches over
+        `words` columns (qi_gpu_repair_kernels); '' when unsupported."""
+        return lib().qi_gpu_repair_kernels(self.h, n_targets, words).decode()
+
+    def repair_ctx_bytes(self, n_targets, n_stripes, words):
+        """0 when the plan (k > 256) or n_targets is not supported."""
+        return lib().qi_gpu_repair_ctx_bytes(self.h, n_targets, n_stripes,
+                                             words)
+
+    def repair_ctx(self, ids, targets, ctx, words, counts=None, entries=None,
+                   cap=0, stream=None):
+        """ids: int16 tensor [S, k] (received fragment ids); targets: int16
+        tensor [S, R] (the fragments to rebuild); OOR buckets of the coded
+        rows as produced by encode (routed into the contexts)."""
+        import torch
+        if ids.dim() != 2 or targets.dim() != 2 or ids.shape[0] != targets.shape[0]:
+            raise ValueError("ids: expected [S, k], targets: [S, R]")
+        S, R = targets.shape
+        need = self.repair_ctx_bytes(R, S, words)
+        if need == 0 and S > 0:
+            raise ValueError(f"repair of {R} targets is not supported on "
+                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        _flat(ids, "ids", S * self.k, (torch.int16, torch.uint16))
+        _flat(targets, "targets", S * R, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, self.n_outputs)
+        rc = lib().qi_gpu_repair_ctx(
+            self.h, ids.data_ptr(), targets.data_ptr(), R, S,
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            words, ctx.data_ptr(), self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_repair_ctx failed: {rc}")
+
+    def repair(self, ctx, coded, out, data=None, counts=None, entries=None,
+               cap=0, out_counts=None, out_entries=None, out_cap=0,
+               stream=None, check=True):
+        """coded: [S, n_out, P] (fragment slot rows, with their OOR buckets
+        counts / entries); out: [S, R, P], row j = target j of the context,
+        its marks in out_counts / out_entries (slots = R; cleared by the
+        caller).  Returns the sticky error flags when check."""
+        _rows(out, "out")
+        S, R, P = out.shape
+        _rows(coded, "coded", self.n_outputs, S)
+        if data is not None:
+            _rows(data, "data", self.k, S)
+        need = self.repair_ctx_bytes(R, S, P)
+        if need == 0 and S > 0:
+            raise ValueError(f"repair of {R} targets is not supported on "
+                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        import torch
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, self.n_outputs)
+        _oor(out_counts, out_entries, out_cap, S, R)
+        d = data if data is not None else coded
+        rc = lib().qi_gpu_repair(
+            self.h, ctx.data_ptr(), R, d.data_ptr(), d.stride(0), d.stride(1),
+            coded.data_ptr(), coded.stride(0), coded.stride(1),
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            out.data_ptr(), out.stride(0), out.stride(1),
+            out_counts.data_ptr() if out_counts is not None else None,
+            out_entries.data_ptr() if out_entries is not None else None,
+            int(out_cap), P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_repair failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -316,6 +394,41 @@ class Fec:
         if not self.h:
             raise ValueError("qi_fec_new failed")
         self.n_outputs = lib().qi_fec_n_outputs(self.h)
+
+    def repair_blocks(self, data, parities, oor, counts, missing, targets,
+                      out_cap=64):
+        """Rebuild the missing fragments `targets` (fragment ids) from the
+        first k present ones in one pass (qi_fec_repair_blocks).  data: k
+        uint8 rows or None entries (None as a whole for non-systematic
+        codes); parities: n_outputs rows or None; oor (n_outputs, cap) uint32
+        and counts (n_outputs,) uint32: the coded rows' marks; missing: k + m
+        flags.  Returns (rows, out_oor, out_counts): the rebuilt uint8 rows,
+        their ascending marks (len(targets), out_cap) and exact counts; None
+        when fewer than k fragments are present.  Raises ValueError for an
+        unsupported shape (k > 256, more than min(64, m) targets, a block
+        wider than one staging chunk)."""
+        import numpy as np
+        rows = [r for r in list(data or []) + list(parities) if r is not None]
+        B = len(rows[0])
+        tg = np.ascontiguousarray(targets, np.int32)
+        miss = np.ascontiguousarray(missing, np.int32)
+        oor = np.ascontiguousarray(oor, np.uint32)
+        counts = np.ascontiguousarray(counts, np.uint32)
+        outs = [np.zeros(B, np.uint8) for _ in range(len(tg))]
+        o_oor = np.zeros((len(tg), out_cap), np.uint32)
+        o_cnt = np.zeros(len(tg), np.uint32)
+        rc = lib().qi_fec_repair_blocks(
+            self.h, ptr_array(list(data)) if data is not None else None,
+            ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p), oor.shape[1],
+            miss.ctypes.data_as(C.c_void_p), tg.ctypes.data_as(C.c_void_p),
+            len(tg), ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
+            o_cnt.ctypes.data_as(C.c_void_p), out_cap, B)
+        if rc == -2:
+            raise ValueError("repair_blocks: shape not supported")
+        if rc < 0:
+            raise RuntimeError(f"qi_fec_repair_blocks failed: {rc}")
+        return (outs, o_oor, o_cnt) if rc == 1 else None
 
     def close(self):
         if self.h:

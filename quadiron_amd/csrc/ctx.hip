@@ -164,6 +164,8 @@ __device__ __forceinline__ uint32_t grp_add(uint32_t v, int lpr)
         v += __shfl_xor(v, m, lpr);
     return v;
 }
+// ME: entries per lane the unrolled passes cover (kin <= ME * lpr)
+template <int ME = 16>
 __device__ __forceinline__ void pack_row_grp(uint32_t* row, const uint32_t* cscale, const MatLayout& L,
                              int t, int32_t* block, int sub, int lpr, bool dot2)
 {
@@ -171,7 +173,6 @@ __device__ __forceinline__ void pack_row_grp(uint32_t* row, const uint32_t* csca
     // registers: every row load is issued up front (rows in global memory
     // for k > 128), and the packed pairs take the odd entry from the
     // neighbour lane by shuffle instead of re-reading the row
-    constexpr int ME = 16;
     const int kin = L.kin, KP = L.KP;
     uint32_t v[ME];
 #pragma unroll
@@ -1520,6 +1521,260 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
         hipLaunchKernelGGL((decode_ctx_lds_kernel<128>), dim3(S), dim3(128), lds, st, k, rp, lgn,
                            mode, L, d_ids, d_ctx, ctx_stride, in_oor ? *in_oor : none,
                            slot_base, by_pos, words, dot2, err);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---------------------------------------------------------------------------
+// Repair context: the R x k matrix that rebuilds the R lost fragments
+// `targets` of a stripe straight from its k received ones,
+//   M[j][i] = L_i(y_j) = A(y_j) / ((y_j - x_i) A'(x_i)),
+//   x_i = r^{ids[i]}, y_j = r^{targets[j]}, A(x) = prod_i (x - x_i),
+// packed as a complete MatLayout{R, k, KP} block (pack_row's row scale,
+// kcorr / kmf / rscale, `plain`, the dot2 pairs and the operand tiles),
+// followed by the sections of a decode context: the ids as dwords (data
+// fragments first for systematic plans, order_ids), the route table of the
+// received rows' marks, the slow-tile list and the lazy word (both dot2
+// sections are written here, so the word says so).
+// A(y_j) / (y_j - x_i) is the product of the other k - 1 differences, so a
+// row needs no inversion at all: prefix and suffix products of (y_j - x_l)
+// over the row, TPR lanes per row each taking a slice (their slice products
+// exchanged by shuffles).  The only inversions are the k column scales
+// 1 / A'(x_i), one addition chain per lane (inv_lz).  A'(x_i) = prod_{l != i}
+// (x_i - x_l) directly: k - 1 lazy multiplies per lane, no A(x) chain.
+// One block per stripe; k <= 256, R <= 64.  NT = 64 for the small contexts
+// (k <= 64, R <= 16: one wave, so the block barriers cost nothing and 4x as
+// many stripes are resident; the headline k = 16 context has 16 to 64
+// entries), 256 otherwise.
+// Bad input raises kErrBadIds (sticky): ids repeated (A'(x_i) = 0) or not
+// below n, a target not below the code length, repeated, or equal to a
+// received id (y_j - x_i = 0).  Such a context holds garbage; nothing outside
+// it is written.
+// ---------------------------------------------------------------------------
+constexpr int kRepairMaxR = 64;
+
+template <int NT>
+__global__ __launch_bounds__(NT) void repair_ctx_kernel(
+    int k, int code_len, RPow2 rp, int lgn, int sys, MatLayout L,
+    const uint16_t* __restrict__ ids, const uint16_t* __restrict__ targets,
+    int32_t* __restrict__ ctx, long long ctx_stride, Oor in_oor, int slot_base, long long words,
+    uint32_t* err)
+{
+    __shared__ uint32_t xs[256];
+    __shared__ uint32_t ys[kRepairMaxR];
+    __shared__ uint32_t tg[kRepairMaxR];
+    __shared__ uint32_t cinv[256];  // 1 / A'(x_i), canonical
+    __shared__ uint16_t pid[256];   // the ids in the context's order
+    __shared__ int wtot[NT / 64];
+    extern __shared__ __attribute__((aligned(16))) uint32_t qi_ctx_lds[];  // R x kp
+    const int s = blockIdx.x, tid = threadIdx.x, R = L.R;
+    int32_t* mat = ctx + s * ctx_stride;
+    const int kp = ctx_pitch(k);
+    uint32_t* Mt = qi_ctx_lds;
+    int32_t* cids = mat + L.words();
+    uint32_t* route = reinterpret_cast<uint32_t*>(cids + 2 * L.KP);
+    const long long ntiles = route_tiles(words);
+
+    for (int i = k + tid; i < 2 * L.KP; i += NT)
+        cids[i] = 0;
+    // (ids only, no buckets: every tile unrouted, as the decode contexts)
+    const uint32_t rt0 = in_oor.counts ? 0u : static_cast<uint32_t>(kRouteCap) + 1u;
+    for (long long t = tid; t < ntiles; t += NT)
+        route[t * kRouteStride] = rt0;
+    if (tid == 0) {
+        route[ntiles * kRouteStride] = 0;          // the slow-tile list starts empty
+        route[lazy_word_off(words)] = kLazyDot2;   // the dot2 sections are built here
+    }
+    order_ids<NT>(ids + static_cast<long long>(s) * k, k, sys != 0, pid, wtot);
+    if (tid < k) {
+        const uint32_t id = pid[tid];
+        xs[tid] = canon_lz(rpow_lz(rp, id, lgn));
+        cids[tid] = static_cast<int32_t>(id);
+        if (id >= (1u << lgn))  // not a point of the code
+            atomicOr(err, kErrBadIds);
+    }
+    if (tid < R) {
+        const uint32_t t = targets[static_cast<long long>(s) * R + tid];
+        tg[tid] = t;
+        ys[tid] = canon_lz(rpow_lz(rp, t, lgn));
+        if (t >= static_cast<uint32_t>(code_len))  // not a fragment of the code
+            atomicOr(err, kErrBadIds);
+    }
+    // this lane's bucket: its count and first entry are loaded here, ahead
+    // of the arithmetic, so the routing below finds them arrived
+    long long bk = -1;
+    uint32_t bcnt = 0, bent0 = 0;
+    if (in_oor.counts && tid < k) {
+        const int slot = static_cast<int>(pid[tid]) - slot_base;
+        // rows outside the bucket array (systematic data rows below
+        // slot_base; bad ids past it) have no marks here
+        if (slot >= 0 && slot < in_oor.slots) {
+            bk = static_cast<long long>(s) * in_oor.slots + slot;
+            bcnt = in_oor.counts[bk];
+            if (in_oor.cap > 0)  // (read whatever the count: inside the bucket)
+                bent0 = in_oor.entries[bk * in_oor.cap];
+        }
+    }
+    __syncthreads();  // xs, ys, tg
+    if (tid < R) {
+        bool dup = false;
+        for (int j = 0; j < tid; j++)
+            dup |= tg[j] == tg[tid];
+        if (dup)  // a repeated target
+            atomicOr(err, kErrBadIds);
+    }
+    // the column scales 1 / A'(x_i), A'(x_i) = prod_{l != i} (x_i - x_l)
+    if (tid < k) {
+        const uint32_t xi = xs[tid];
+        int32_t p = 1;  // lazy, |p| < 65600
+        for (int l = 0; l < k; l++) {
+            const uint32_t d = subm(xi, xs[l]);
+            p = mul_lz(p, l == tid ? 1 : balanced(d));
+        }
+        const uint32_t ap = canon_lz(p);
+        cinv[tid] = inv_lz(ap);
+        if (ap == 0u)  // repeated ids
+            atomicOr(err, kErrBadIds);
+    }
+    // the rows before the column scale: Mt[j][i] = prod_{l != i} (y_j - x_l),
+    // TPR lanes per row (a power of two: the group's lanes share a wave)
+    int TPR = 1;
+    while (TPR < 16 && 2 * TPR * R <= NT && 2 * TPR <= k)
+        TPR *= 2;
+    {
+        const int j = tid / TPR, sub = tid % TPR;
+        const bool live = j < R;  // uniform in the row's lane group
+        const int seg = (k + TPR - 1) / TPR;
+        const int i0 = min(k, sub * seg), i1 = min(k, i0 + seg);
+        uint32_t* row = Mt + (live ? j : 0) * kp;
+        const uint32_t y = ys[live ? j : 0];
+        int32_t pre = 1;  // lazy products, |pre| < 65600
+        if (live)
+            for (int i = i0; i < i1; i++) {
+                row[i] = static_cast<uint32_t>(pre);
+                pre = mul_lz(pre, balanced(subm(y, xs[i])));
+            }
+        // the product of the other lanes' slices: those left of this one
+        // (into the prefixes) and right of it (into the suffixes)
+        int32_t left = 1, right = 1;
+        for (int o = 0; o < TPR; o++) {
+            const int32_t po = __shfl(pre, o, TPR);
+            left = o < sub ? mul_lz(left, po) : left;
+            right = o > sub ? mul_lz(right, po) : right;
+        }
+        if (live) {
+            if (sub == 0 && canon_lz(mul_lz(pre, right)) == 0u)
+                atomicOr(err, kErrBadIds);  // A(y_j) = 0: the target was received
+            int32_t suf = right;
+            for (int i = i1 - 1; i >= i0; i--) {
+                const int32_t v = mul_lz(mul_lz(static_cast<int32_t>(row[i]), left), suf);
+                suf = mul_lz(suf, balanced(subm(y, xs[i])));
+                row[i] = canon_lz(v);
+            }
+        }
+    }
+    // The route table is filled here, behind the Lagrange arithmetic: its
+    // clears (top of the kernel) must have reached memory before any
+    // thread's atomicAdd (each wave waits for its own stores, then the
+    // barrier: DESIGN.md section 4.6), and by now they have -- waiting for
+    // them at the top stalled the one-wave form for a store round trip
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    if (bk >= 0) {
+        uint32_t c = bcnt;
+        if (c > static_cast<uint32_t>(in_oor.cap)) {
+            atomicOr(err, kErrOorTruncated);
+            c = static_cast<uint32_t>(in_oor.cap);
+        }
+        for (uint32_t e = 0; e < c; e++) {
+            const uint32_t w = e ? in_oor.entries[bk * in_oor.cap + e] : bent0;
+            if (w >= words)
+                continue;
+            uint32_t* rt = route + (w / kRouteTile) * kRouteStride;
+            const uint32_t p = atomicAdd(rt, 1u);
+            if (p < static_cast<uint32_t>(kRouteCap))
+                rt[1 + p] = (static_cast<uint32_t>(tid) << 16) | (w % kRouteTile);
+        }
+    }
+    {
+        // the column scale, pack_row's row scale, the packed pairs, `plain`,
+        // kcorr / rscale / kmf; the row-scaled entries back into the LDS rows
+        const int q4 = (k + 3) / 4;
+        const int lpr = q4 <= 4 ? 4 : q4 <= 8 ? 8 : 16;
+        // (NT = 64: k <= 64, at most 4 entries per lane)
+        for (int t = tid / lpr; t < R; t += NT / lpr)
+            pack_row_grp<NT == 64 ? 4 : 16>(Mt + t * kp, cinv, L, t, mat, tid & (lpr - 1), lpr,
+                                            true);
+    }
+    __syncthreads();
+    // the complete operand tiles (pack_mf_dword's layout: [a | 0], [0 | b],
+    // [b | a], zeros past the rows and entries), from the LDS rows: per (row
+    // t, 4 consecutive entries) split once, items rows-fastest so a wave's
+    // stores cover whole 128-byte tile lines
+    const int KS = L.KS(), KH = 16 * KS, nj = KH / 4, RB = L.RB();
+    int32_t* mf = mat + L.mf();
+    for (int it = tid; it < RB * nj * 16; it += NT) {
+        const int tl4 = it & 15, jj = it >> 4;
+        const int j = jj % nj, rb = jj / nj;
+        const int t = 16 * rb + tl4, i0 = 4 * j;
+        uint32_t aw = 0, bw = 0;
+        if (t < R && i0 < k) {
+            const uint4 e4 = *reinterpret_cast<const uint4*>(Mt + t * kp + i0);
+            const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+            for (int jb = 0; jb < 4; jb++) {
+                if (i0 + jb < k) {
+                    int32_t a, b;
+                    split_i8(e[jb], a, b);
+                    aw |= (static_cast<uint32_t>(a) & 0xffu) << (8 * jb);
+                    bw |= (static_cast<uint32_t>(b) & 0xffu) << (8 * jb);
+                }
+            }
+        }
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const int K = half * KH + i0;
+            const int ks = K >> 5, g = (K & 31) >> 3, dw = (K & 7) >> 2;
+            const size_t base =
+                static_cast<size_t>((rb * KS + ks) * 3) * 128 + (16 * g + tl4) * 2 + dw;
+            mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
+            mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
+            mf[base + 256] = static_cast<int32_t>(half ? aw : bw);  // [b | a]
+        }
+    }
+}
+
+int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const MatLayout& L,
+                      const uint16_t* d_ids, const uint16_t* d_targets, int S, int32_t* d_ctx,
+                      long long ctx_stride, const Oor* in_oor, int slot_base, long long words,
+                      uint32_t* err, hipStream_t st)
+{
+    if (k > 256 || L.kin != k || L.R < 1 || L.R > kRepairMaxR || S <= 0)
+        return -3;
+    Oor none{nullptr, nullptr, 0, 0};
+    RPow2 rp{};
+    uint32_t e = r;
+    for (int b = 0; b < 16; b++, e = mulmod_c(e, e))
+        rp.v[b] = balanced(e);
+    int lgn = 0;
+    while (lgn < 16 && (1u << lgn) < static_cast<uint32_t>(n))
+        lgn++;
+    // up to 65 KB of rows (R = 64, k = 256): opted in per launch (cheap; the
+    // device may differ between calls)
+    const size_t lds = static_cast<size_t>(L.R) * ctx_pitch(k) * 4;
+    if (k <= 64 && L.R <= 16) {  // at most 16 x 68 words of rows
+        hipLaunchKernelGGL(repair_ctx_kernel<64>, dim3(S), dim3(64), lds, st, k, code_len, rp,
+                           lgn, sys, L, d_ids, d_targets, d_ctx, ctx_stride,
+                           in_oor ? *in_oor : none, slot_base, words, err);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
+    if (lds > 32768 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&repair_ctx_kernel<256>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(lds)) != hipSuccess)
+        return -2;
+    hipLaunchKernelGGL(repair_ctx_kernel<256>, dim3(S), dim3(256), lds, st, k, code_len, rp, lgn,
+                       sys, L, d_ids, d_targets, d_ctx, ctx_stride, in_oor ? *in_oor : none,
+                       slot_base, words, err);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

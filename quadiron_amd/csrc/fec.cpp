@@ -428,6 +428,149 @@ size_t read_full(std::istream* is, uint8_t* p, size_t len)
 
 }  // namespace
 
+// ---- fused repair (single chunk; qi_gpu_repair_ctx / qi_gpu_repair) ----
+bool RsFnt::repair_supported(size_t n_targets, size_t block_size_bytes) const
+{
+    const size_t words = block_size_bytes / word_size;
+    if (n_data > 256 || n_targets < 1 || n_targets > std::min<size_t>(64, n - n_data))
+        return false;
+    if (words == 0 || words > chunk_bytes(buf_size) / 2)
+        return false;  // wider blocks go through the chunk pipeline
+    // every fragment of the code has a row slot on the device (the context
+    // addresses rows by fragment id)
+    return static_cast<size_t>(code_len) * pad_words(words) * 2 <= (size_t{256} << 20);
+}
+
+bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                   std::vector<uint8_t*>& parities_bufs,
+                                   std::vector<Properties>& parities_props,
+                                   std::vector<int>& missing_idxs,
+                                   const std::vector<int>& targets,
+                                   std::vector<uint8_t*>& out_bufs,
+                                   std::vector<Properties>& out_props,
+                                   size_t block_size_bytes)
+{
+    const bool sys = type == FecType::SYSTEMATIC;
+    const size_t R = targets.size();
+    if (!repair_supported(R, block_size_bytes))
+        throw std::invalid_argument("RsFnt::repair_blocks_vertical: unsupported shape");
+    if (out_bufs.size() < R)
+        throw std::invalid_argument("RsFnt::repair_blocks_vertical: out_bufs");
+    std::vector<int> present(code_len);
+    for (unsigned i = 0; i < code_len; i++)
+        present[i] = missing_idxs[i] ? 0 : 1;
+    for (int t : targets)
+        if (t < 0 || t >= static_cast<int>(code_len) || present[t])
+            throw std::invalid_argument("RsFnt::repair_blocks_vertical: target not missing");
+    std::vector<int> ids;
+    if (!select_fragments(present, ids))
+        return false;
+    for (auto& p : parities_props)
+        p.sort();
+    out_props.assign(R, Properties());
+    const size_t words = block_size_bytes / word_size;
+    const size_t P = pad_words(words);
+    const int k = static_cast<int>(n_data);
+    const size_t no = n_outputs;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // the received rows in their own slots: data rows (systematic) first,
+    // then the coded rows; OOR buckets of the coded rows by slot
+    const size_t data_rows = sys ? n_data : 0;
+    std::vector<std::vector<uint32_t>> marks(no);
+    size_t cap = 1;
+    for (int i = 0; i < k; i++) {
+        const int id = ids[i];
+        if (sys && id < k)
+            continue;
+        const size_t slot = sys ? id - k : id;
+        for (auto const& it : parities_props[slot].get_map())
+            if (it.first < words)
+                marks[slot].push_back(static_cast<uint32_t>(it.first));
+        cap = std::max(cap, marks[slot].size());
+    }
+    std::vector<uint32_t> hcnt(no, 0), hent(no * cap, 0);
+    for (size_t i = 0; i < no; i++) {
+        hcnt[i] = static_cast<uint32_t>(marks[i].size());
+        std::copy(marks[i].begin(), marks[i].end(), hent.begin() + i * cap);
+    }
+    std::vector<uint16_t> hids(k + R);
+    for (int i = 0; i < k; i++)
+        hids[i] = static_cast<uint16_t>(ids[i]);
+    for (size_t j = 0; j < R; j++)
+        hids[k + j] = static_cast<uint16_t>(targets[j]);
+    const size_t ctx_bytes = qi_gpu_repair_ctx_bytes(pl, static_cast<int>(R), 1,
+                                                     static_cast<long long>(words));
+    if (ctx_bytes == 0)
+        throw std::invalid_argument("RsFnt::repair_blocks_vertical: unsupported shape");
+    size_t ocap = 64 + words / 512;
+    // counts buffer: input counts, input entries, output counts
+    const size_t ent_off = 64 * ((no * 4 + 63) / 64);
+    const size_t oc_off = ent_off + 64 * ((hent.size() * 4 + 63) / 64);
+    if (!h.in.reserve((data_rows + no) * P * 2) || !h.out.reserve(R * P * 2) ||
+        !h.counts.reserve(oc_off + R * 4) || !h.ids.reserve((k + R) * 2) ||
+        !h.ctx.reserve(ctx_bytes))
+        throw std::runtime_error("RsFnt: device allocation failed");
+    uint16_t* din = static_cast<uint16_t*>(h.in.p);
+    uint16_t* dcoded = din + data_rows * P;
+    uint16_t* dout = static_cast<uint16_t*>(h.out.p);
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + ent_off);
+    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + oc_off);
+    for (int i = 0; i < k; i++) {
+        const int id = ids[i];
+        const bool d = sys && id < k;
+        const uint8_t* src = d ? data_bufs[id] : parities_bufs[sys ? id - k : id];
+        uint16_t* dst = d ? din + id * P : dcoded + (sys ? id - k : id) * P;
+        check(hipMemcpyAsync(dst, src, words * 2, hipMemcpyHostToDevice, s), "H2D");
+    }
+    check(hipMemcpyAsync(dcnt, hcnt.data(), no * 4, hipMemcpyHostToDevice, s), "H2D");
+    check(hipMemcpyAsync(dent, hent.data(), hent.size() * 4, hipMemcpyHostToDevice, s), "H2D");
+    check(hipMemcpyAsync(h.ids.p, hids.data(), (k + R) * 2, hipMemcpyHostToDevice, s), "H2D");
+    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
+    check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, dcnt, dent,
+                               static_cast<int>(cap), static_cast<long long>(words), h.ctx.p, s),
+             "repair context");
+    std::vector<uint32_t> ocnt(R);
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if (!h.entries.reserve(R * ocap * 4))
+            throw std::runtime_error("RsFnt: device allocation failed");
+        check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+        check_rc(qi_gpu_repair(pl, h.ctx.p, static_cast<int>(R), din, 0,
+                               static_cast<long long>(P), dcoded, 0, static_cast<long long>(P),
+                               dcnt, dent, static_cast<int>(cap), dout, 0,
+                               static_cast<long long>(P), docnt,
+                               static_cast<uint32_t*>(h.entries.p), static_cast<int>(ocap),
+                               static_cast<long long>(words), 1, s),
+                 "repair");
+        check(hipMemcpyAsync(ocnt.data(), docnt, R * 4, hipMemcpyDeviceToHost, s), "D2H");
+        check(hipStreamSynchronize(s), "sync");
+        const uint32_t mx = *std::max_element(ocnt.begin(), ocnt.end());
+        if (mx <= ocap)
+            break;
+        ocap = mx;  // adversarial data: re-run with exact capacity
+    }
+    std::vector<uint32_t> ent(R * ocap);
+    check(hipMemcpyAsync(ent.data(), h.entries.p, R * ocap * 4, hipMemcpyDeviceToHost, s),
+          "D2H");
+    for (size_t j = 0; j < R; j++)
+        if (out_bufs[j])
+            check(hipMemcpyAsync(out_bufs[j], dout + j * P, words * 2, hipMemcpyDeviceToHost, s),
+                  "D2H");
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: repair failed (bad ids or OOR bucket capacity)");
+    for (size_t j = 0; j < R; j++) {
+        uint32_t* b = ent.data() + j * ocap;
+        std::sort(b, b + ocnt[j]);
+        for (uint32_t e = 0; e < ocnt[j]; e++)
+            out_props[j].add(b[e], OOR_MARK);
+    }
+    return true;
+}
+
 namespace {
 
 // One stage of the pipelined stream API: pinned host staging, device
@@ -1285,6 +1428,49 @@ int qi_fec_decode_blocks(qi_fec* h, uint8_t** data, uint8_t** parities,
             want[i] = wanted[i] != 0;
         return f.decode_blocks_vertical(dv, pv, props, miss, want, block_bytes) ? 1
                                                                                 : 0;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_repair_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const uint32_t* oor,
+                         const uint32_t* oor_count, uint32_t cap, const int* missing,
+                         const int* targets, int n_targets, uint8_t** out, uint32_t* out_oor,
+                         uint32_t* out_count, uint32_t out_cap, size_t block_bytes)
+{
+    try {
+        if (!h || n_targets < 0)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.repair_supported(static_cast<size_t>(n_targets), block_bytes))
+            return -2;
+        std::vector<uint8_t*> dv(f.n_data, nullptr);
+        if (data)
+            dv.assign(data, data + f.n_data);
+        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
+        std::vector<qi::Properties> props(f.n_outputs);
+        for (unsigned i = 0; i < f.n_outputs; i++) {
+            const uint32_t c = oor_count[i] < cap ? oor_count[i] : cap;
+            for (uint32_t e = 0; e < c; e++)
+                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
+        }
+        std::vector<int> miss(missing, missing + f.code_len);
+        std::vector<int> tg(targets, targets + n_targets);
+        std::vector<uint8_t*> ov(out, out + n_targets);
+        std::vector<qi::Properties> oprops;
+        if (!f.repair_blocks_vertical(dv, pv, props, miss, tg, ov, oprops, block_bytes))
+            return 0;
+        for (int j = 0; j < n_targets; j++) {
+            uint32_t c = 0;
+            for (auto const& it : oprops[j].get_map()) {
+                if (c < out_cap)
+                    out_oor[static_cast<size_t>(j) * out_cap + c] =
+                        static_cast<uint32_t>(it.first);
+                c++;
+            }
+            out_count[j] = c;
+        }
+        return 1;
     } catch (...) {
         return -1;
     }

@@ -559,8 +559,14 @@ struct OorScan {
 // the decode context); matrix_redo_kernel, launched right after them on the
 // same stream, recomputes every column of the tile that holds a mark from
 // scratch -- all marks of the column restored, plain canonical arithmetic
-// -- and stores it again.  Only decodes carry input marks, and their
-// outputs are data symbols (< 65536), so nothing is recorded as OOR here.
+// -- and stores it again.  A decode's outputs are data symbols (< 65536):
+// nothing to record.  A repair carries input marks and records output marks
+// in the same launch (the BOTH instantiations, chosen by the launchers when
+// both kinds of bucket are given): there the first pass records nothing in
+// a slow tile -- its outputs came from partly restored inputs -- and the
+// redo recomputes every column of the tile, marked or not, and records each
+// output equal to 65536 exactly once.  The other instantiations compile to
+// what they were before BOTH existed.
 // Keeping this out of the hot kernels keeps their registers: inlined at
 // their end it held the bucket and row pointers live across the MFMA loop
 // (SGPR spills, 2x slower decode).
@@ -580,22 +586,23 @@ __device__ __forceinline__ void push_slow_tile(const SlowList& sl, int s, long l
 // buckets), then lane c of wave wv recomputes column c for the output rows
 // wv, wv + 4, ... (the coefficient, read back from the operand tiles by
 // mf_entry, is wave-uniform: scalar loads) -- only in columns that hold a
-// mark.  Work per chunk is
+// mark (BOTH: in every column of the tile).  Work per chunk is at most
 // R * kin * 64 multiply-adds whatever the mark density (walking the marks
 // per (mark, row, input) was quadratic in the density).  The stripe's list
 // is emptied afterwards (a context can serve several decodes).
 constexpr int kRedoCols = 64;
 
 // Recompute, from scratch, every column of stripe s's columns [t0c, t1c)
-// that holds a mark (all marks of the column restored, plain canonical
-// arithmetic) and store it again: NT threads, LDS scratch xs (kin x
+// that holds a mark -- BOTH: every column of the range, and record its
+// outputs equal to 65536 in a.out_oor -- (all marks of the column restored,
+// plain canonical arithmetic) and store it again: NT threads, LDS scratch xs (kin x
 // kRedoCols u16), mk (kin x kRedoCols / 32 u32), colmk (kRedoCols / 32 u32).
 // The caller has waited for its own stores of these columns.  Only the
 // output rows of row blocks gq, gq + G, gq + 2G, ... (16 rows each) are
 // recomputed: a block of matrix_os_kernel redoes just the rows it stored
 // itself (G row-block groups share a column range), so no two blocks write
 // the same outputs; other callers pass gq = 0, G = 1 (every row).
-template <int NT>
+template <int NT, bool BOTH = false>
 __device__ void redo_columns(const MatArgs& a, int s, long long t0c, long long t1c,
                              uint16_t* xs, uint32_t* mk, uint32_t* colmk, int gq = 0,
                              int G = 1)
@@ -642,7 +649,10 @@ __device__ void redo_columns(const MatArgs& a, int s, long long t0c, long long t
             }
         }
         __syncthreads();
-        if ((colmk[c / 32] >> (c % 32)) & 1u) {
+        bool redo = (colmk[c / 32] >> (c % 32)) & 1u;
+        if constexpr (BOTH)
+            redo = redo || c0 + c < t1c;
+        if (redo) {
             const int nrows = 16 * ((L.RB() - gq + G - 1) / G);
             for (int it = wv; it < nrows; it += NT / 64) {
                 const int t = 16 * (gq + G * (it >> 4)) + (it & 15);
@@ -663,6 +673,9 @@ __device__ void redo_columns(const MatArgs& a, int s, long long t0c, long long t
                                               65537u);
                 dst.base[s * dst.ss + a.rowmap[t] * dst.rs + c0 + c] =
                     static_cast<uint16_t>(y == 65536u ? 0u : y);
+                if constexpr (BOTH)
+                    if (y == 65536u)
+                        record_oor(a.out_oor, s, a.rowmap[t], c0 + c);
             }
         }
         __syncthreads();
@@ -685,46 +698,17 @@ __device__ __forceinline__ void drain_block_stores()
 // stripes holding slow tiles.
 constexpr int kRedoSpan = 64;
 
+
 __global__ __launch_bounds__(kBlock) void matrix_redo_kernel(MatArgs a, int n_stripes)
 {
-    // (the dot2 tails' slow tiles: k <= 256; the operand-stationary kernel
-    // redoes its own in its dynamic LDS)
-    __shared__ uint16_t xs[kMatGenMaxKin * kRedoCols];  // [input i][column]
-    __shared__ uint32_t mk[kMatGenMaxKin * (kRedoCols / 32)];
-    __shared__ uint32_t colmk[kRedoCols / 32];
-    const int tid = threadIdx.x, c = tid & 63, wv = tid >> 6;
-    // this block's stripes with a non-empty list (wave 0, one lane each;
-    // broadcast to the block through LDS)
-    __shared__ uint64_t todo;
-    const int s0 = blockIdx.x * kRedoSpan;
-    if (wv == 0) {
-        const int sl = s0 + c;
-        const uint32_t nl = sl < n_stripes
-                                ? __hip_atomic_load(a.slow.base + sl * a.slow.stride,
-                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                : 0u;
-        const uint64_t m = __builtin_amdgcn_ballot_w64(nl != 0);
-        if (c == 0)
-            todo = m;
-    }
-    __syncthreads();
-    uint64_t pend = todo;
-    while (pend) {
-        const int s = s0 + __builtin_ctzll(pend);  // block-uniform
-        pend &= pend - 1;
-        uint32_t* l = a.slow.base + s * a.slow.stride;
-        const uint32_t n = *l;
-        for (uint32_t e = 0; e < n; e++) {
-            const uint32_t code = l[1 + e];
-            const long long t0 = static_cast<long long>(code >> 3) * kSlowGrain;
-            const long long t1 = min(t0 + (static_cast<long long>(kSlowGrain) << (code & 7)),
-                                     a.words);
-            redo_columns<kBlock>(a, s, t0, t1, xs, mk, colmk);
-        }
-        __syncthreads();
-        if (tid == 0)
-            *l = 0;
-    }
+    constexpr bool BOTH = false;
+#include "matrix_redo_body.h"
+}
+// input and output marks in one launch (a repair)
+__global__ __launch_bounds__(kBlock) void matrix_redo_kernel_both(MatArgs a, int n_stripes)
+{
+    constexpr bool BOTH = true;
+#include "matrix_redo_body.h"
 }
 
 // the context's routed marks of this tile (count <= kRouteCap, entries
@@ -953,138 +937,23 @@ __device__ __forceinline__ void matrix_compute(
     }
 }
 
+
 template <int KP, int COLS, bool BUF>
 __global__ __launch_bounds__(kBlock) void matrix_kernel(MatArgs a)
 {
-    const MatLayout L = a.L;
-    const int32_t* __restrict__ mat = a.mat;
-    const long long mat_stride = a.ms;
-    const int32_t* __restrict__ ids = a.ids;
-    const long long ids_stride = a.is;
-    const RowSrc src = a.src;
-    const RowDst dst = a.dst;
-    const MatExt ext = a.ext;
-    const long long words = a.words;
-    const int tiles = a.tiles;
-    const Oor in_oor = a.in_oor;
-    const int slot_base = a.slot_base;
-    const Oor out_oor = a.out_oor;
-    const uint32_t* __restrict__ route = a.route;
-    const long long route_stride = a.rstride;
-    const SlowList slow = a.slow;
-    uint32_t* err = a.err;
-    __shared__ int s_cnt;
-    __shared__ int s_i[kMaxTileOor];
-    __shared__ uint32_t s_col[kMaxTileOor];
-
-    int s, tile;
-    block_map(blockIdx.x, tiles, s, tile);
-    const int kin = L.kin;
-    const long long col0 = ext.c0 + static_cast<long long>(tile) * kBlock * COLS;
-    const long long col1 = col0 + kBlock * COLS;
-    const long long col = col0 + static_cast<long long>(threadIdx.x) * COLS;
-    const uint32_t voff = static_cast<uint32_t>(col * 2);
-    const int32_t* M = mat + s * mat_stride;
-    // fragment ids as dwords (scalar loads; a u16 array would need vector
-    // loads + readfirstlane, draining vmcnt between the row loads)
-    const int32_t* sid = ids ? ids + s * ids_stride : nullptr;
-    const bool full = col1 <= words;  // block-uniform
-    const Region<BUF> g0(src.base0 + s * src.ss0, ext.e0);
-    const Region<BUF> g1(src.base1 ? src.base1 + s * src.ss1 : src.base0,
-                         ext.e1);
-    const Region<BUF> go(dst.base + s * dst.ss, ext.eo);
-
-    // the OOR marks of the received rows in this tile (decode_prepare,
-    // src/fec_base.h:1361-1404): from the context's route table (scalar
-    // loads, issued with the row loads), or -- when the table overflowed or
-    // is absent -- by scanning the OOR buckets
-    int n_rm = 0;
-    const uint32_t* rm = nullptr;
-    bool scan = in_oor.counts != nullptr;
-    if (route) {
-        const uint32_t* rt =
-            route + s * route_stride + (col0 / kRouteTile) * kRouteStride;
-        const uint32_t rc = rt[0];
-        if (rc <= static_cast<uint32_t>(kRouteCap)) {
-            n_rm = static_cast<int>(rc);
-            rm = rt + 1;
-            scan = false;
-        }
-    }
-
-    // source row of input i: its position (by_pos) or its fragment id; rows
-    // past kin are clamped to a valid row (their coefficients are 0).
-    // KP <= 32: all ids up front in SGPRs (2*KP dwords, the context pads
-    // past kin), so the scalar loads batch into a few s_load_dwordxN.
-    // KP >= 64 (the column tails of k > 64): 128-256 ids do not fit the
-    // SGPRs (they spilled to VGPR lanes and scratch), so lane c of
-    // idl[i / 64] holds id i and the row loads read it with v_readlane.
-    constexpr int NIL = KP >= 64 ? 2 * KP / 64 : 1;
-    constexpr int NIV = KP >= 64 ? 1 : 2 * KP;
-    int idl[NIL];
-    int idv[NIV];
-    if constexpr (KP >= 64) {
-        const int ln = static_cast<int>(threadIdx.x & 63);
-#pragma unroll
-        for (int c = 0; c < NIL; c++) {
-            const int i = 64 * c + ln;
-            const int ii = i < kin ? i : kin - 1;
-            idl[c] = src.by_pos ? ii : (sid ? sid[i < kin ? i : 0] : (i < kin ? i : 0));
-        }
-        (void)idv;
-    } else {
-        (void)idl;
-        if (sid) {
-#pragma unroll
-            for (int i = 0; i < 2 * KP; i++)
-                idv[i] = sid[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2 * KP; i++)
-                idv[i] = i;
-        }
-#pragma unroll
-        for (int i = 0; i < 2 * KP; i++) {
-            const int ii = i < kin ? i : kin - 1;
-            idv[i] = src.by_pos ? ii : (i < kin ? idv[i] : idv[0]);
-        }
-    }
-    auto id_of = [&](int i) {
-        if constexpr (KP >= 64)
-            return __builtin_amdgcn_readlane(idl[i / 64], i % 64);
-        else
-            return idv[i];
-    };
-    int32_t xp[COLS][KP];
-    if (full) {
-        matrix_load<KP, COLS, true, BUF>(id_of, src, g0, g1, voff, COLS, xp);
-    } else if (col < words) {
-        matrix_load<KP, COLS, false, BUF>(id_of, src, g0, g1, voff,
-                                          words - col, xp);
-    }
-    OorScan sc{in_oor, sid, src.by_pos, slot_base, kin, s, false};
-    int n_lm = 0;
-    if (scan) {  // block-uniform
-        const int cnt = scan_tile_marks(sc, col0, col1, words, &s_cnt, s_i, s_col, err);
-        sc.slow = cnt > kMaxTileOor;
-        n_lm = min(cnt, kMaxTileOor);
-    } else if (n_rm > 0) {  // block-uniform: the routed marks into the same list
-        stage_route_marks(rm, n_rm, col0, s_i, s_col);
-        __syncthreads();
-        n_lm = n_rm;
-    }
-    const uint32_t ors = static_cast<uint32_t>(dst.rs * 2);
-    if (full) {
-        matrix_compute<KP, COLS, true, BUF>(L, M, xp, go, ors, voff, col, col0,
-                                            COLS, s, n_lm, s_i, s_col, out_oor,
-                                            a.rowmap);
-    } else if (col < words) {
-        matrix_compute<KP, COLS, false, BUF>(L, M, xp, go, ors, voff, col, col0,
-                                             words - col, s, n_lm, s_i, s_col,
-                                             out_oor, a.rowmap);
-    }
-    if (sc.slow && threadIdx.x == 0)  // rare: see matrix_redo_kernel
-        push_slow_tile(slow, s, col0, kBlock * COLS);
+    // (An include, not a template flag or a shared inline body: a shared
+    // __forceinline__ body changed the register allocation of the plain
+    // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
+    // form keeps its text and its resource report; do not fold the two.)
+    constexpr bool BOTH = false;
+#include "matrix_kernel_body.h"
+}
+// input and output marks in one launch (a repair): see push_slow_tile
+template <int KP, int COLS, bool BUF>
+__global__ __launch_bounds__(kBlock) void matrix_kernel_both(MatArgs a)
+{
+    constexpr bool BOTH = true;
+#include "matrix_kernel_body.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -1155,449 +1024,23 @@ struct MfmaTile {
     static_assert(kRg >= 1 && kThreads % kTpr == 0 && kRows % kRg == 0, "staging");
 };
 
+
 template <int KS, int NST, int NW, bool RSPLIT>
 __global__ __launch_bounds__(64 * NW) void matrix_mfma_kernel(MatArgs a)
 {
-    const MatLayout L = a.L;
-    const int32_t* __restrict__ mat = a.mat;
-    const long long mat_stride = a.ms;
-    const int32_t* __restrict__ ids = a.ids;
-    const long long ids_stride = a.is;
-    const RowSrc src = a.src;
-    const RowDst dst = a.dst;
-    const MatExt ext = a.ext;
-    const long long words = a.words;
-    const int tiles = a.tiles;
-    const Oor in_oor = a.in_oor;
-    const int slot_base = a.slot_base;
-    const Oor out_oor = a.out_oor;
-    const uint32_t* __restrict__ route = a.route;
-    const long long route_stride = a.rstride;
-    uint32_t* err = a.err;
-    using G = MfmaTile<KS, NST, NW>;
-    constexpr int NCOL = G::kCols, KH = G::kRows, RSB = G::kPitch;
-    constexpr int CPL = G::kCpl, RG = G::kRg;
-    // one dynamic region (16-byte aligned base: no static LDS in front)
-    extern __shared__ __attribute__((aligned(16))) uint8_t qi_lds[];
-    uint8_t* img = qi_lds;
-    int* s_i = reinterpret_cast<int*>(qi_lds + G::kImg);
-    uint32_t* s_col = reinterpret_cast<uint32_t*>(s_i + kMaxTileOor);
-    int* s_cnt = reinterpret_cast<int*>(s_col + kMaxTileOor);
-
-    int s, tile;
-    block_map(blockIdx.x, tiles, s, tile);
-    const int kin = L.kin;
-    const long long col0 = static_cast<long long>(tile) * NCOL;
-    const long long col1 = col0 + NCOL;
-    // staging: this thread's first column and its row group
-    const uint32_t cl = (RG == 1 ? threadIdx.x : threadIdx.x % G::kTpr) * CPL;
-    const int rg = RG == 1 ? 0 : static_cast<int>(threadIdx.x / G::kTpr);
-    const uint32_t voff = static_cast<uint32_t>((col0 + cl) * 2);
-    const int32_t* M = mat + s * mat_stride;
-    const int32_t* sid = ids ? ids + s * ids_stride : nullptr;
-    const Region<true> g0(src.base0 + s * src.ss0, ext.e0);
-    const Region<true> g1(src.base1 ? src.base1 + s * src.ss1 : src.base0,
-                          ext.e1);
-    const Region<true> go(dst.base + s * dst.ss, ext.eo);
-
-    // OOR marks of the received rows in this tile: route table (scalar
-    // loads) or bucket scan, as matrix_kernel
-    int n_rm = 0;
-    const uint32_t* rm = nullptr;
-    bool scan = in_oor.counts != nullptr;
-    if (route) {
-        const uint32_t* rt =
-            route + s * route_stride + (col0 / kRouteTile) * kRouteStride;
-        const uint32_t rc = rt[0];
-        if (rc <= static_cast<uint32_t>(kRouteCap)) {
-            n_rm = static_cast<int>(rc);
-            rm = rt + 1;
-            scan = false;
-        }
-    }
-
-    // operand tiles of output block 0 (per-lane loads; issued before the row
-    // loads so their latency hides behind the staging)
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int g = l >> 4, q = (l & 15) >> 1, p = l & 1, tl = l & 15;
-    const int RB = L.RB();
-    const int32_t* mf = M + L.mf();
-    const int32_t* kmf = M + L.kmf();
-    const int32_t* rscale = M + L.rscale_mf();
-    const int32_t* __restrict__ rowmap = a.rowmap;
-    auto load_ops = [&](int rb, qi_v2i (&b)[KS][3], int32_t& kt, int32_t& rs, int32_t (&pr)[3]) {
-        // [b | a] is [0 | b] of the l' half over the h' K-steps and [a | 0]
-        // of the h' half over the l' K-steps, lane for lane (the same K
-        // offset within the half): from those registers at KS >= 2 (the
-        // contexts do not store it); at KS = 1 the halves share a K-step
-        // and sit in other lanes, so it is loaded
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-            for (int ty = 0; ty < (KS >= 2 ? 2 : 3); ty++)
-                b[ks][ty] = *reinterpret_cast<const qi_v2i*>(
-                    mf + ((rb * KS + ks) * 3 + ty) * 128 + l * 2);
-        if constexpr (KS >= 2) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++)
-                b[ks][2] = ks < KS / 2 ? b[ks + KS / 2][1] : b[ks - KS / 2][0];
-        }
-        // unconditional loads (a clamped row), selected after: an exec-masked
-        // load leaves the compiler unsure how many vector-memory ops are in
-        // flight, and it then drains vmcnt further than needed
-        const int t = 16 * rb + tl, tc = t < L.R ? t : L.R - 1;
-        const int32_t k0 = kmf[tc], r0 = rscale[tc];
-        kt = t < L.R ? k0 : 0;
-        rs = t < L.R ? r0 : 1;
-        // output rows: this lane's epilogue row and its two store rows
-        pr[0] = rowmap[tc];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int ot = 16 * rb + 8 * h + (l >> 3);
-            pr[1 + h] = rowmap[ot < L.R ? ot : L.R - 1];
-        }
-    };
-    // tall matrices (RSPLIT, the encode generators): wave wv takes row
-    // blocks wv, wv + NW, ... over all the block's super tiles, so each wave
-    // fetches only its own operand tiles (NW x fewer L2 operand reads than
-    // every wave walking every row block); otherwise every wave takes every
-    // row block over its own super tiles
-    constexpr bool rsplit = RSPLIT;
-    const int rb0 = rsplit ? wv : 0, rbs = rsplit ? NW : 1;
-    constexpr int nst = rsplit ? NST : NST / NW;
-    static_assert(rsplit || NST % NW == 0, "super tiles per wave");
-
-    // the first row block's operands, issued ahead of the row loads
-    qi_v2i bA[KS][3], bB[KS][3];
-    int32_t ktA, rsA, ktB, rsB, prA[3], prB[3];
-    const int rlast = RB - 1;
-    const bool single = rb0 + rbs >= RB;
-    load_ops(min(rb0, rlast), bA, ktA, rsA, prA);
-
-    // stage the tile as byte planes h' (rows 0..KH-1) and l' (rows KH..):
-    // this thread's CPL columns of every RG-th row, all row loads issued back
-    // to back; rows past kin load a clamped row (their operand bytes are 0)
-    uint32_t w[KH / RG][CPL / 2];
-    if constexpr (G::kTpr % 64 == 0) {
-        // the row group is wave-uniform: every id of the thread's rows in
-        // SGPRs first (the scalar loads issue together; loading each id
-        // next to its row load made a chain of KH dependent scalar loads,
-        // one lgkmcnt(0) per row), then the row loads back to back -- with
-        // one source region (every decode but the systematic one, and the
-        // encode) a row offset is one scalar multiply
-        int idv[KH / RG];
-        if (sid && !src.by_pos) {
-#pragma unroll
-            for (int r = 0; r < KH / RG; r++) {
-                const int i = r * RG + rg;
-                idv[r] = sid[i < kin ? i : kin - 1];
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < KH / RG; r++) {
-                const int i = r * RG + rg;
-                idv[r] = i < kin ? i : kin - 1;
-            }
-        }
-        if (!src.base1) {
-            const uint32_t rsb = static_cast<uint32_t>(src.rs0 * 2);
-#pragma unroll
-            for (int r = 0; r < KH / RG; r++)
-                ld_dw<CPL / 2, true, kAuxLd>(g0, static_cast<uint32_t>(idv[r]) * rsb, voff,
-                                             w[r]);
-        } else {
-#pragma unroll
-            for (int r = 0; r < KH / RG; r++) {
-                const int id = idv[r];
-                const bool lo = id < src.split;
-                Region<true> g = g0;
-                g.r = lo ? g0.r : g1.r;
-                const uint32_t off = static_cast<uint32_t>(
-                    lo ? id * src.rs0 * 2 : (id - src.split) * src.rs1 * 2);
-                ld_dw<CPL / 2, true, kAuxLd>(g, off, voff, w[r]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < KH / RG; r++) {
-            const int i = r * RG + rg;
-            const int ii = i < kin ? i : kin - 1;
-            const int id = src.by_pos ? ii : (sid ? sid[ii] : ii);
-            const bool lo = id < src.split;
-            Region<true> g = g0;
-            g.r = lo ? g0.r : g1.r;
-            const uint32_t off = static_cast<uint32_t>(
-                lo ? id * src.rs0 * 2 : (id - src.split) * src.rs1 * 2);
-            ld_dw<CPL / 2, true, kAuxLd>(g, off, voff, w[r]);
-        }
-    }
-    const uint32_t lpos = 64 * (cl / 64) + 16 * ((cl % 16) / 4) +
-                          4 * ((cl % 64) / 16) + cl % 4;
-#pragma unroll
-    for (int r = 0; r < KH / RG; r++) {
-        const int i = r * RG + rg;
-        if constexpr (CPL == 4) {
-            // [c0 lo, c0 hi, c1 lo, c1 hi] [c2 lo, ...] -> hi / lo planes
-            const uint32_t hi =
-                __builtin_amdgcn_perm(w[r][1], w[r][0], 0x07050301u) ^ 0x80808080u;
-            const uint32_t lo =
-                __builtin_amdgcn_perm(w[r][1], w[r][0], 0x06040200u) ^ 0x80808080u;
-            *reinterpret_cast<uint32_t*>(img + i * RSB + lpos) = hi;
-            *reinterpret_cast<uint32_t*>(img + (KH + i) * RSB + lpos) = lo;
-        } else {
-            const uint32_t hi =
-                __builtin_amdgcn_perm(0u, w[r][0], 0x0c0c0301u) ^ 0x8080u;
-            const uint32_t lo =
-                __builtin_amdgcn_perm(0u, w[r][0], 0x0c0c0200u) ^ 0x8080u;
-            *reinterpret_cast<uint16_t*>(img + i * RSB + lpos) =
-                static_cast<uint16_t>(hi);
-            *reinterpret_cast<uint16_t*>(img + (KH + i) * RSB + lpos) =
-                static_cast<uint16_t>(lo);
-        }
-    }
-    OorScan sc{in_oor, sid, src.by_pos, slot_base, kin, s, false};
-    int n_lm = 0;
-    if (scan) {  // block-uniform; the scan's barriers also publish the image
-        const int cnt = scan_tile_marks(sc, col0, col1, words, s_cnt, s_i, s_col, err);
-        sc.slow = cnt > kMaxTileOor;
-        n_lm = min(cnt, kMaxTileOor);
-    } else {
-        // the routed marks into the same LDS list: the epilogue then reads
-        // only LDS (no memory loads in the hot loop)
-        stage_route_marks(rm, n_rm, col0, s_i, s_col);
-        __syncthreads();
-        n_lm = n_rm;
-    }
-
-    // matrix cores: wave wv covers nst super tiles of 64 columns, for each
-    // block of 16 output rows in turn (the next block's operands prefetched)
-    const bool rec = out_oor.counts != nullptr;
-    const uint32_t ors = static_cast<uint32_t>(dst.rs * 2);
-    // generic -> LDS address space (C-style cast: reinterpret_cast cannot
-    // change the address space)
-    auto* lds = (__attribute__((address_space(3))) uint8_t*)img;
-    const uint32_t abase = static_cast<uint32_t>((8 * g + q) * RSB + 8 * p);
-    // One row block: every super tile's MFMAs, epilogue and stores, with
-    // the block's operand tiles b / kt / rs.
-    auto rb_body = [&](int rb, const qi_v2i (&bop)[KS][3], const int32_t kt,
-                       const int32_t rs, const int32_t (&pr)[3]) {
-        const int t = 16 * rb + tl;
-        const bool trow = t < L.R;
-        // MFMAs of super tile ST into acc
-        auto tile_mfma = [&](const int ST, qi_v4i (&acc)[4][3]) {
-#pragma unroll
-            for (int T = 0; T < 4; T++) {
-                acc[T][0] = qi_v4i{0, 0, 0, 0};
-                acc[T][1] = qi_v4i{kt, kt, kt, kt};
-                acc[T][2] = qi_v4i{0, 0, 0, 0};
-                auto rd_a = [&](int ks) {
-                    auto* pa = (__attribute__((address_space(3))) qi_v2i*)(
-                        lds + abase + 32 * ks * RSB + (4 * ST + T) * 16);
-                    return __builtin_amdgcn_ds_read_tr8_b64_v2i32(pa);
-                };
-                if constexpr (KS == 1) {
-                    const long a = __builtin_bit_cast(long, rd_a(0));
-#pragma unroll
-                    for (int ty = 0; ty < 3; ty++)
-                        acc[T][ty] = __builtin_amdgcn_mfma_i32_16x16x32_i8(
-                            a, __builtin_bit_cast(long, bop[0][ty]), acc[T][ty], 0,
-                            0, 0);
-                } else {
-                    // two K-steps per v_mfma_i32_16x16x64_i8 (CDNA4: the
-                    // cycles of 16x16x32_i8 at twice the K).  Lane l holds
-                    // the 8 A bytes of steps ks and ks + 1 (and the same
-                    // two B halves): A and B share their lane/byte -> K
-                    // map, so the 64-K product is the sum of the two
-                    // 32-K products whatever that map is
-#pragma unroll
-                    for (int ks = 0; ks < KS; ks += 2) {
-                        const qi_v2i a0 = rd_a(ks), a1 = rd_a(ks + 1);
-                        const qi_v4i a{a0.x, a0.y, a1.x, a1.y};
-#pragma unroll
-                        for (int ty = 0; ty < 3; ty++) {
-                            // [a | 0] is zero over the l' half of K and
-                            // [0 | b] over the h' half: skip the pairs
-                            // that lie in a zero half (KS = 4)
-                            if ((ty == 0 && ks >= KS / 2) ||
-                                (ty == 1 && ks + 1 < KS / 2))
-                                continue;
-                            const qi_v4i b{bop[ks][ty].x, bop[ks][ty].y,
-                                           bop[ks + 1][ty].x, bop[ks + 1][ty].y};
-                            acc[T][ty] = __builtin_amdgcn_mfma_i32_16x16x64_i8(
-                                a, b, acc[T][ty], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        };
-        // epilogue element math of one super tile: lane (g, t) holds row t,
-        // columns 16 g .. 16 g + 15 of the super tile; result j of chunk T is
-        // LDS byte 4 g + j = column 16 g + 4 T + j (straight-line VALU, so
-        // it can share a scheduling region with the next tile's MFMAs)
-        auto tile_y = [&](const qi_v4i (&acc)[4][3], int32_t (&y)[16]) {
-#pragma unroll
-            for (int T = 0; T < 4; T++)
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    y[4 * T + j] =
-                        fold(fold(((KS >= 16 ? fold(acc[T][2][j]) : acc[T][2][j]) << 8) +
-                                  acc[T][1][j] - acc[T][0][j]));
-        };
-        // the rest of the epilogue + stores of super tile ST
-        auto tile_fin = [&](const int ST, int32_t (&y)[16]) {
-            const long long cb = col0 + 64 * ST + 16 * g;
-            // restored OOR symbols of the received rows: 65536 == -1 where
-            // the stored word is 0 (decode_prepare, src/fec_base.h:1361-1404)
-            // Branch-free per lane: the marks come from LDS and the
-            // coefficient load is unconditional and consumed at once.  A gather load under a lane-divergent branch left a
-            // possibly pending load into a reused VGPR at the loop exit,
-            // and the compiler then drained vmcnt(0) -- every outstanding
-            // store and operand prefetch -- after every super tile, with or
-            // without marks (cfg3 encode: wait_any 34 % of wave cycles).
-            // (One loop body, no lambda: as a lambda the compiler indexed
-            // y[] dynamically and moved it to scratch memory.)
-            // Only the marks inside this super tile's 64 columns are applied
-            // (a wave-uniform test on the LDS list: the list holds the route
-            // tile's marks, 1024 columns, so without it every super tile
-            // paid 80 VALU per mark of its whole route tile).
-            const uint32_t st0 = static_cast<uint32_t>(col0 + 64 * ST);
-            for (int e = 0; e < n_lm; e++) {
-                const uint32_t wcu = __builtin_amdgcn_readfirstlane(s_col[e]);
-                if (wcu - st0 >= 64u)
-                    continue;
-                const int pos = __builtin_amdgcn_readfirstlane(s_i[e]);
-                const long long wc = wcu;
-                const long long d = wc - cb;
-                // from the operand tile in registers (bop[ks][2] = [b | a])
-                const int32_t corr = coef_from_tiles<KS>(
-                    [&](int idx) {
-                        int32_t r = 0;
-#pragma unroll
-                        for (int q = 0; q < 2 * KS; q++)
-                            r = idx == q ? bop[q >> 1][2][q & 1] : r;
-                        return r;
-                    },
-                    pos, l);
-#pragma unroll
-                for (int c = 0; c < 16; c++) {
-                    const int32_t yc = fold(fold(y[c] - corr));
-                    y[c] = (trow && d == c) ? yc : y[c];
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(rs != 1)) {
-                // every lane (rs = 1 keeps its value's residue: y is in
-                // [-1, 65536] either way): no per-element exec masking
-#pragma unroll
-                for (int c = 0; c < 16; c++)
-                    y[c] = fold(fold(mul_rs(y[c], rs)));
-            }
-            uint32_t bad = 0;
-#pragma unroll
-            for (int c = 0; c < 16; c++)
-                bad |= static_cast<uint32_t>(y[c]);
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64((bad >> 16) != 0) != 0, 0)) {
-#pragma unroll
-                for (int c = 0; c < 16; c++) {
-                    if (static_cast<uint32_t>(y[c]) > 65535u) {
-                        if (rec && trow)
-                            record_oor(out_oor, s, pr[0], cb + c);
-                        y[c] = 0;  // 65536 (or its alias -1) is stored as 0
-                    }
-                }
-            }
-            qi_v4u o0, o1;
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                o0[c] = pack_lo(static_cast<uint32_t>(y[2 * c]),
-                                static_cast<uint32_t>(y[2 * c + 1]));
-                o1[c] = pack_lo(static_cast<uint32_t>(y[8 + 2 * c]),
-                                static_cast<uint32_t>(y[8 + 2 * c + 1]));
-            }
-            // the 16 x 64 output tile is transposed through LDS and stored
-            // as 8 whole 128-byte lines per instruction, which can stream
-            // (nt|sc1).  One block of output rows: through this super
-            // tile's input bytes, dead once its MFMAs are done (row t at
-            // image rows 2t, 2t+1, bytes 64 ST..); several: through the
-            // wave's own staging tile behind the image (144-byte rows).
-            uint8_t* stg;
-            int pitch, half;
-            if (RB == 1) {
-                stg = img + 64 * ST;
-                pitch = 2 * RSB;
-                half = RSB - 64;  // bytes 64..127 of a row sit one image row down
-            } else {
-                stg = qi_lds + G::kLds + wv * G::kStage;
-                pitch = G::kStagePitch;
-                half = 0;
-            }
-            auto at = [&](int row, int byte) {
-                return stg + row * pitch + byte + (byte >= 64 ? half : 0);
-            };
-            *reinterpret_cast<qi_v4u*>(at(tl, 32 * g)) = o0;
-            *reinterpret_cast<qi_v4u*>(at(tl, 32 * g + 16)) = o1;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int orow = 8 * h + (l >> 3), c = l & 7;
-                const qi_v4u v = *reinterpret_cast<const qi_v4u*>(at(orow, 16 * c));
-                // rows >= R get an offset past the buffer resource's extent
-                // (< 2^31): the hardware drops those stores.  Unconditional,
-                // so the compiler keeps an exact count of the stores in flight
-                const int ot = 16 * rb + orow;
-                const uint32_t vo =
-                    ot < L.R ? static_cast<uint32_t>(pr[1 + h]) * ors +
-                                   static_cast<uint32_t>((col0 + 64 * ST + 8 * c) * 2)
-                             : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(v, go.r, static_cast<int>(vo), 0,
-                                                       kAuxStMf);
-            }
-            // the staging tile is rewritten by the next (ST, rb): keep this
-            // iteration's reads ahead of those writes
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        };
-        auto st_of = [&](int st) { return rsplit ? st : wv * nst + st; };
-#pragma unroll 1
-        for (int st = 0; st < nst; st++) {
-            qi_v4i acc[4][3];
-            int32_t y[16];
-            tile_mfma(st_of(st), acc);
-            tile_y(acc, y);
-            tile_fin(st_of(st), y);
-        }
-    };
-    // Row blocks in ping-pong over two operand buffers, each prefetch one row
-    // block ahead and unconditional (a clamped row block past the end).  On
-    // gfx9 loads and stores share the in-order vmcnt: copying a prefetched
-    // buffer (or a conditional prefetch) made the compiler drain vmcnt(0) at
-    // every row block -- i.e. wait for all the previous block's streaming
-    // stores before the next MFMA could issue.
-    if (single) {
-        // one row block for this wave (every decode up to k = 64): its
-        // operands were loaded before the row loads, nothing to prefetch
-        if (rb0 < RB)
-            rb_body(rb0, bA, ktA, rsA, prA);
-    } else {
-        for (int rb = rb0; rb < RB; rb += 2 * rbs) {
-            load_ops(min(rb + rbs, rlast), bB, ktB, rsB, prB);
-            rb_body(rb, bA, ktA, rsA, prA);
-            if (rb + rbs >= RB)
-                break;
-            load_ops(min(rb + 2 * rbs, rlast), bA, ktA, rsA, prA);
-            rb_body(rb + rbs, bB, ktB, rsB, prB);
-        }
-    }
-    if (sc.slow) {
-        // rare (block-uniform): more marks than the LDS list held; this
-        // block redoes its columns once its stores are done, with the image
-        // as scratch (kin x 136 bytes <= the image)
-        drain_block_stores();
-        redo_columns<64 * NW>(a, s, col0, col1, reinterpret_cast<uint16_t*>(qi_lds),
-                              reinterpret_cast<uint32_t*>(qi_lds + kin * 2 * kRedoCols),
-                              reinterpret_cast<uint32_t*>(qi_lds + kin * (2 * kRedoCols + 8)));
-    }
+    // (An include, not a template flag or a shared inline body: a shared
+    // __forceinline__ body changed the register allocation of the plain
+    // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
+    // form keeps its text and its resource report; do not fold the two.)
+    constexpr bool BOTH = false;
+#include "matrix_mfma_body.h"
+}
+// input and output marks in one launch (a repair): see push_slow_tile
+template <int KS, int NST, int NW, bool RSPLIT>
+__global__ __launch_bounds__(64 * NW) void matrix_mfma_kernel_both(MatArgs a)
+{
+    constexpr bool BOTH = true;
+#include "matrix_mfma_body.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -1915,615 +1358,23 @@ struct OsTile {
     static_assert(kRpt >= 1 && kRows % kRpp == 0, "staging");
 };
 
+
 template <int KS, int WR, int RPW, bool TWO>
 __global__ __launch_bounds__(512) void matrix_os_kernel(MatArgs a, int G, int C, int TS)
 {
-    constexpr int NCH = OsK<KS>::NCH, KC = OsK<KS>::KC;
-    using O = OsTile<KC, WR>;  // one chunk's image (the whole K when NCH = 1)
-    constexpr int KH = O::kRows, RSB = O::kPitch, RPT = O::kRpt, NCOL = O::kCols;
-    static_assert(KS % 4 == 0 && KC % 4 == 0, "x64 pairs with zero halves");
-    static_assert(NCH == 1 || RPW == 1, "K chunks: one row block per wave");
-    extern __shared__ __attribute__((aligned(16))) uint8_t qi_lds[];
-    const MatLayout L = a.L;
-    const RowSrc src = a.src;
-    const RowDst dst = a.dst;
-    const MatExt ext = a.ext;
-    const Oor in_oor = a.in_oor;
-    const Oor out_oor = a.out_oor;
-    const int kin = L.kin;
-    const int tid = threadIdx.x, wv = tid >> 6, l = tid & 63;
-    const int g = l >> 4, q = (l & 15) >> 1, p = l & 1, tl = l & 15;
-
-    // block -> (stripe, row-block group, column range); every block of one
-    // stripe on the same XCD (block b runs on XCD b % 8), consecutive in its
-    // dispatch order, when the stripes tile the 8 XCDs: the stripe's context
-    // tiles (256 KB per stripe at k = 256, 4 KiB packets: a quarter of its
-    // data bytes) and the input tiles its G groups share are read from HBM
-    // once and hit that XCD's L2 after (round 6: the C column ranges had
-    // landed on different XCDs, k256 decode reads 1.23x algorithmic);
-    // otherwise the G groups of one (stripe, range) on one XCD
-    int s, gq, cr;
-    {
-        const int L0 = blockIdx.x;
-        int unit;
-        const int S = static_cast<int>(gridDim.x) / (G * C);
-        if ((S & 7) == 0) {
-            const int x = L0 & 7, j = L0 >> 3, per = G * C;
-            const int sg = j / per, rem = j - sg * per;
-            s = sg * 8 + x;
-            cr = rem / G;
-            gq = rem - cr * G;
-            unit = s * C + cr;
-        } else if (((S * C) & 7) == 0) {
-            const int x = L0 & 7, j = L0 >> 3;
-            gq = j % G;
-            unit = (j / G) * 8 + x;
-        } else {
-            gq = L0 % G;
-            unit = L0 / G;
-        }
-        s = unit / C;
-        cr = unit - s * C;
-    }
-    const int t0 = static_cast<int>(static_cast<long long>(cr) * TS / C);
-    const int t1 = static_cast<int>(static_cast<long long>(cr + 1) * TS / C);
-    // one bit per tile of the block (<= kOsMaxTiles, os_launch), behind the
-    // other LDS sections; cleared before the first mark scan's barrier
-    uint32_t* slow_bits = reinterpret_cast<uint32_t*>(qi_lds + O::kLds);
-    for (int wd = tid; wd <= (t1 - t0 - 1) >> 5; wd += 512)
-        slow_bits[wd] = 0u;
-
-    const int RB = L.RB();
-    const int slot = wv % WR, st = wv / WR;  // row-block slot, super tile
-    const int32_t* M = a.mat + s * a.ms;
-    const int32_t* mf = M + L.mf();
-    const int32_t* kmf = M + L.kmf();
-    const int32_t* rscale = M + L.rscale_mf();
-    const int32_t* __restrict__ rowmap = a.rowmap;
-    const int32_t* sid = a.ids ? a.ids + s * a.is : nullptr;
-
-    // this wave's row blocks and their operand tiles, for the block's whole
-    // life: [a|0] over the h' K-steps, [0|b] over the l' K-steps (x64
-    // pairs); [b|a] over the h' half is b1 and over the l' half b0, lane for
-    // lane (see matrix_mfma_kernel's load_ops), so it is neither stored in
-    // the context nor held twice
-    int rbj[RPW];
-    bool act[RPW];
-    qi_v4i b0[RPW][KS / 4], b1[RPW][KS / 4];
-    int32_t kt[RPW], rs[RPW], pr[RPW][3];
-#pragma unroll
-    for (int j = 0; j < RPW; j++) {
-        // row blocks dealt round-robin over the G groups (their counts
-        // differ by at most one): a group with fewer busy waves ran ahead of
-        // the others, and the input tiles it had fetched were evicted from
-        // L2 before they came by (k300: 1.88x the input bytes read)
-        const int rb = gq + G * (slot + WR * j);
-        act[j] = rb < RB;  // wave-uniform
-        const int rbc = act[j] ? rb : RB - 1;
-        rbj[j] = rbc;
-        auto ld2 = [&](int ks, int ty) {
-            return *reinterpret_cast<const qi_v2i*>(mf + ((rbc * KS + ks) * 3 + ty) * 128 + l * 2);
-        };
-#pragma unroll
-        for (int i = 0; i < KS / 4; i++) {
-            const qi_v2i x0 = ld2(2 * i, 0), x1 = ld2(2 * i + 1, 0);
-            b0[j][i] = qi_v4i{x0.x, x0.y, x1.x, x1.y};
-            const qi_v2i y0 = ld2(KS / 2 + 2 * i, 1), y1 = ld2(KS / 2 + 2 * i + 1, 1);
-            b1[j][i] = qi_v4i{y0.x, y0.y, y1.x, y1.y};
-        }
-        const int t = 16 * rbc + tl;
-        const int tcl = t < L.R ? t : L.R - 1;
-        const int32_t k0 = kmf[tcl], r0 = rscale[tcl];
-        kt[j] = t < L.R ? k0 : 0;
-        rs[j] = t < L.R ? r0 : 1;
-        pr[j][0] = rowmap[tcl];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int ot = 16 * rbc + 8 * h + (l >> 3);
-            pr[j][1 + h] = rowmap[ot < L.R ? ot : L.R - 1];
-        }
-    }
-
-    // staging: lane (rowgrp, cl) loads 4 columns (b64) of rows kRpp r +
-    // rowgrp; per-lane row offsets fixed for the block (rows past kin
-    // clamped: their operand bytes are 0); chunk c stages the received rows
-    // KH c .. KH c + KH - 1.
-    //   TWO (two source regions, the systematic decodes): one offset per
-    // row, in its own region.  The context lists the received rows region by
-    // region (order_ids, ctx.hip), so a wave's load of pass (c, r) reads one
-    // region, through that region's descriptor (bit c RPT + r of sel), but
-    // for at most one pass (xcr) that straddles the boundary: its region-1
-    // lanes take an extra load (wx, one per item, past the extent in every
-    // other item: zeros), ORed into that row when it is written to LDS.
-    // (Each row loaded through both descriptors, past the extent in the
-    // other region, took the k600 systematic decode 1.11 -> 1.92 ms:
-    // twice the load instructions, gpurun_out/r6l.)
-    const Region<true> g0(src.base0 + s * src.ss0, ext.e0);
-    const Region<true> g1(src.base1 ? src.base1 + s * src.ss1 : src.base0, ext.e1);
-    const Region<true> go(dst.base + s * dst.ss, ext.eo);
-    const int rowgrp = tid / O::kTpr, cl = (tid % O::kTpr) * 4;
-    constexpr uint32_t kOob = 0x80000000u;  // past any extent (< 2^31)
-    static_assert(NCH * RPT <= 32, "pass bits");
-    uint32_t off0[NCH][RPT];
-    uint32_t sel = 0, offx = kOob;  // sel: wave-uniform
-    int xcr = -1;                   // wave-uniform: c RPT + r of the straddling pass
-#pragma unroll
-    for (int c = 0; c < NCH; c++)
-#pragma unroll
-        for (int r = 0; r < RPT; r++) {
-            const int i = KH * c + O::kRpp * r + rowgrp;
-            const int ii = i < kin ? i : kin - 1;
-            const int id = src.by_pos ? ii : (sid ? sid[ii] : ii);
-            const uint32_t lane = static_cast<uint32_t>(cl * 2);
-            if constexpr (TWO) {
-                const bool lo = id < src.split;
-                off0[c][r] = (lo ? static_cast<uint32_t>(id * src.rs0 * 2)
-                                 : static_cast<uint32_t>((id - src.split) * src.rs1 * 2)) +
-                             lane;
-                const uint64_t b1 = __ballot(!lo);
-                if (b1 == ~0ull) {
-                    sel |= 1u << (c * RPT + r);
-                } else if (b1 != 0ull) {
-                    if (xcr >= 0 && a.err && l == 0)
-                        atomicOr(a.err, kErrBadIds);  // rows not in region order
-                    xcr = c * RPT + r;
-                    offx = lo ? kOob : off0[c][r];
-                }
-            } else {
-                off0[c][r] = static_cast<uint32_t>(id * src.rs0 * 2) + lane;
-            }
-        }
-    sel = __builtin_amdgcn_readfirstlane(sel);
-    xcr = __builtin_amdgcn_readfirstlane(xcr);
-    const int xc = xcr >= 0 ? xcr / RPT : -1, xr = xcr >= 0 ? xcr % RPT : -1;
-    // DEEP (KS = 4, the short decodes): ND tiles of rows in flight per
-    // block (a ring of ND register sets, 8 VGPRs each) -- with one, a CU
-    // kept ~32 KB of loads in flight and the cfg3 decode was bound by the
-    // load latency; three measured the same as two, four slower (125 / 133
-    // VGPRs: cfg3 decode 0.143 / 0.168 ms, profiles/r5_ab_notes.txt)
-    constexpr int ND = KS == 4 ? 2 : 1;
-    constexpr bool DEEP = ND >= 2;
-    uint32_t w[RPT][2], wring[DEEP ? ND : 1][DEEP ? RPT : 1][2];
-    uint32_t wx[2], wxring[DEEP ? ND : 1][2];  // TWO: the straddling pass's region-1 lanes
-    // rows of `tile` into wr; an invalid tile (past the block's range) loads
-    // from past the buffer's extent (no memory access, zeros), so the number
-    // of loads in flight is the same on every path
-    auto issue_rows_to = [&](int tile, bool valid, auto& wr, auto& wxr, auto cc) {
-        constexpr int c = decltype(cc)::value;  // K chunk
-        const int so = valid ? tile * NCOL * 2 : 0;  // byte offset of the tile's first column
-        const uint32_t oob = valid ? 0u : kOob;
-#pragma unroll
-        for (int r = 0; r < RPT; r++) {
-            uint32_t o = off0[c][r] | oob;
-            auto rsrc = g0.r;
-            if constexpr (TWO) {
-                // (the straddling pass: its region-1 lanes through wx)
-                o = c * RPT + r == xcr && offx != kOob ? kOob : o;
-                rsrc = (sel >> (c * RPT + r)) & 1u ? g1.r : g0.r;
-            }
-            const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, static_cast<int>(o), so,
-                                                                kAuxLdOs);
-            wr[r][0] = v[0];
-            wr[r][1] = v[1];
-        }
-        if constexpr (TWO) {
-            const auto u = __builtin_amdgcn_raw_buffer_load_b64(
-                g1.r, static_cast<int>(c == xc ? offx | oob : kOob), so, kAuxLdOs);
-            wxr[0] = u[0];
-            wxr[1] = u[1];
-        }
-    };
-    using C0 = std::integral_constant<int, 0>;
-    auto issue_rows = [&](int tile, auto cc) { issue_rows_to(tile, true, w, wx, cc); };
-    const uint32_t lpos = 64 * (cl / 64) + 16 * ((cl % 16) / 4) + 4 * ((cl % 64) / 16);
-    auto write_rows_from = [&](uint8_t* img, const auto& w, const auto& wxr) {
-#pragma unroll
-        for (int r = 0; r < RPT; r++) {
-            const int i = O::kRpp * r + rowgrp;
-            uint32_t w0 = w[r][0], w1 = w[r][1];
-            if constexpr (TWO) {
-                // (zeros unless this item's chunk holds the straddling pass)
-                w0 |= r == xr ? wxr[0] : 0u;
-                w1 |= r == xr ? wxr[1] : 0u;
-            }
-            const uint32_t hi = __builtin_amdgcn_perm(w1, w0, 0x07050301u) ^ 0x80808080u;
-            const uint32_t lo = __builtin_amdgcn_perm(w1, w0, 0x06040200u) ^ 0x80808080u;
-            *reinterpret_cast<uint32_t*>(img + i * RSB + lpos) = hi;
-            *reinterpret_cast<uint32_t*>(img + (KH + i) * RSB + lpos) = lo;
-        }
-    };
-    auto write_rows = [&](uint8_t* img) { write_rows_from(img, w, wx); };
-
-    // OOR marks of the received rows in a tile (route table or bucket
-    // scan) into mark list mb; returns the count (all threads)
-    auto s_i = [&](int mb) {
-        return reinterpret_cast<int*>(qi_lds + O::kMarkOff) + mb * 2 * kMaxTileOor;
-    };
-    auto s_col = [&](int mb) { return reinterpret_cast<uint32_t*>(s_i(mb) + kMaxTileOor); };
-    auto s_cnt = [&](int mb) {
-        return reinterpret_cast<int*>(qi_lds + O::kMarkOff + 2 * 2 * 4 * kMaxTileOor) + mb;
-    };
-    const bool marks_in = in_oor.counts != nullptr;
-    // the route-table list each mark buffer holds (block-uniform): the tiles
-    // of one kRouteTile-column route tile share its list (the epilogue keeps
-    // the marks in its own columns), so a buffer that already holds it is not
-    // staged again.  (Staging it every tile cost the cfg3 decode ~8 us: the
-    // wait for the scalar load also drained the LDS accesses in flight,
-    // tools/ab/probe_os_nomarks.patch)
-    // (not at KS = 8, whose kernel measured faster staging every tile from
-    // scalar loads: k128 decode 1.5 %)
-    constexpr bool kOnce = KS != 8;
-    int srt0 = -1, srt1 = -1, scnt0 = 0, scnt1 = 0;
-    auto stage_marks = [&](int tile, int mb) -> int {
-        if (!marks_in)
-            return 0;
-        const long long col0 = static_cast<long long>(tile) * NCOL;
-        if (a.route) {
-            const int rti = static_cast<int>(col0 / kRouteTile);
-            if (kOnce && (mb ? srt1 : srt0) == rti)
-                return mb ? scnt1 : scnt0;
-            const int rc = stage_route_marks_s<kOnce>(
-                a.route + s * a.rstride + static_cast<long long>(rti) * kRouteStride, col0,
-                s_i(mb), s_col(mb));
-            if (rc >= 0) {
-                if constexpr (kOnce) {
-                    if (mb) {
-                        srt1 = rti;
-                        scnt1 = rc;
-                    } else {
-                        srt0 = rti;
-                        scnt0 = rc;
-                    }
-                }
-                return rc;
-            }
-        }
-        if constexpr (kOnce) {
-            if (mb)  // this buffer now holds a bucket scan of one tile
-                srt1 = -1;
-            else
-                srt0 = -1;
-        }
-        OorScan sc{in_oor, sid, src.by_pos, a.slot_base, kin, s, false};
-        const int cnt = scan_tile_marks(sc, col0, col0 + NCOL, a.words, s_cnt(mb), s_i(mb),
-                                        s_col(mb), a.err);
-        if (cnt > kMaxTileOor && tid == 0)  // rare: redone at the block's end
-            atomicOr(&slow_bits[(tile - t0) >> 5], 1u << ((tile - t0) & 31));
-        return min(cnt, kMaxTileOor);
-    };
-    // the block's slow tiles (bits over [t0, t1)), redone by the block once
-    // its stores are done, with the images as scratch
-    auto finish = [&]() {
-        if (!marks_in)
-            return;
-        bool any = false;
-        for (int wd = 0; wd <= (t1 - t0 - 1) >> 5; wd++)
-            any |= slow_bits[wd] != 0u;
-        if (!any)
-            return;  // block-uniform
-        drain_block_stores();
-        for (int wd = 0; wd <= (t1 - t0 - 1) >> 5; wd++) {
-            uint32_t bits = slow_bits[wd];
-            while (bits) {
-                const int tile = t0 + 32 * wd + __builtin_ctz(bits);
-                bits &= bits - 1;
-                const long long c0 = static_cast<long long>(tile) * NCOL;
-                // this group's row blocks only: the G blocks of a column
-                // range each redo (and earlier stored) disjoint rows
-                redo_columns<512>(a, s, c0, c0 + NCOL, reinterpret_cast<uint16_t*>(qi_lds),
-                                  reinterpret_cast<uint32_t*>(qi_lds + kin * 2 * kRedoCols),
-                                  reinterpret_cast<uint32_t*>(qi_lds + kin * (2 * kRedoCols + 8)),
-                                  gq, G);
-            }
-        }
-    };
-
-    const bool rec = out_oor.counts != nullptr;
-    const uint32_t ors = static_cast<uint32_t>(dst.rs * 2);
-    const uint32_t abase = static_cast<uint32_t>((8 * g + q) * RSB + 8 * p + 64 * st);
-    uint8_t* stg = qi_lds + O::kStageOff + wv * O::kStage;
-
-    // row block j of this wave over its super tile (columns col0 ..
-    // col0 + 63) from image img
-    // row block j's accumulators: D0 = 0, D1 = kmf (the byte offsets'
-    // correction), D2 = 0
-    auto init_acc = [&](qi_v4i (&acc)[4][3], auto jc) {
-        constexpr int j = decltype(jc)::value;
-#pragma unroll
-        for (int T = 0; T < 4; T++) {
-            acc[T][0] = qi_v4i{0, 0, 0, 0};
-            acc[T][1] = qi_v4i{kt[j], kt[j], kt[j], kt[j]};
-            acc[T][2] = qi_v4i{0, 0, 0, 0};
-        }
-    };
-    // K chunk cc of row block j over this wave's super tile of image img,
-    // accumulated into acc: the chunk's h' half of K (its pairs: [a|0] and
-    // [b|a]), then its l' half ([0|b] and [b|a]), KC / 4 A pairs live at a
-    // time; operand pair c KC / 4 + i of the row block's registers
-    auto mma = [&](const uint8_t* img, qi_v4i (&acc)[4][3], auto jc, auto cc) {
-        constexpr int j = decltype(jc)::value, c = decltype(cc)::value;
-        auto* lds = (__attribute__((address_space(3))) const uint8_t*)img;
-#pragma unroll
-        for (int T = 0; T < 4; T++) {
-#pragma unroll
-            for (int hf = 0; hf < 2; hf++) {
-                qi_v4i av[KC / 4];
-#pragma unroll
-                for (int i = 0; i < KC / 4; i++) {
-                    auto rd = [&](int ks) {
-                        auto* pa = (__attribute__((address_space(3))) qi_v2i*)(
-                            lds + abase + 32 * ks * RSB + T * 16);
-                        return __builtin_amdgcn_ds_read_tr8_b64_v2i32(pa);
-                    };
-                    const int pi = hf * (KC / 4) + i;
-                    const qi_v2i x0 = rd(2 * pi), x1 = rd(2 * pi + 1);
-                    av[i] = qi_v4i{x0.x, x0.y, x1.x, x1.y};
-                }
-#pragma unroll
-                for (int i = 0; i < KC / 4; i++) {
-                    constexpr int o = c * (KC / 4);
-                    if (hf == 0)
-                        acc[T][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[i], b0[j][o + i],
-                                                                          acc[T][0], 0, 0, 0);
-                    else
-                        acc[T][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[i], b1[j][o + i],
-                                                                          acc[T][1], 0, 0, 0);
-                    acc[T][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(
-                        av[i], hf == 0 ? b1[j][o + i] : b0[j][o + i], acc[T][2], 0, 0, 0);
-                }
-            }
-        }
-    };
-    auto epilogue = [&](const qi_v4i (&acc)[4][3], long long col0, int n_lm, const int* mi,
-                        const uint32_t* mc, auto jc, auto&& before_stores) {
-        constexpr int j = decltype(jc)::value;
-        const int t = 16 * rbj[j] + tl;
-        const bool trow = act[j] && t < L.R;
-        // epilogue: lane (g, t) holds row t, columns cb .. cb + 15
-        const long long cb = col0 + 16 * g;
-        int32_t y[16];
-#pragma unroll
-        for (int T = 0; T < 4; T++)
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++)
-                y[4 * T + jj] =
-                    fold(fold(((KS >= 16 ? fold(acc[T][2][jj]) : acc[T][2][jj]) << 8) +
-                              acc[T][1][jj] - acc[T][0][jj]));
-        // restored OOR symbols of the received rows (decode_prepare,
-        // src/fec_base.h:1361-1404): 65536 == -1 where the stored word is 0
-        const uint32_t st0 = static_cast<uint32_t>(col0);
-        for (int e = 0; e < n_lm; e++) {
-            const uint32_t wcu = __builtin_amdgcn_readfirstlane(mc[e]);
-            if (wcu - st0 >= 64u)
-                continue;
-            const int pos = __builtin_amdgcn_readfirstlane(mi[e]);
-            const long long d = static_cast<long long>(wcu) - cb;
-            // the coefficient from the wave's own operand tiles (no memory
-            // load: waiting for one drained the stores and the prefetch)
-            const int32_t corr = coef_from_tiles<KS>(
-                [&](int idx) {
-                    // [b | a]'s dword idx: b1 over the h' pairs, b0 over the l'
-                    return idx < KS ? pick_v4(b1[j], idx) : pick_v4(b0[j], idx - KS);
-                },
-                pos, l);
-#pragma unroll
-            for (int c = 0; c < 16; c++) {
-                const int32_t yc = fold(fold(y[c] - corr));
-                y[c] = (trow && d == c) ? yc : y[c];
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(rs[j] != 1)) {
-#pragma unroll
-            for (int c = 0; c < 16; c++)
-                y[c] = fold(fold(mul_rs(y[c], rs[j])));
-        }
-        uint32_t bad = 0;
-#pragma unroll
-        for (int c = 0; c < 16; c++)
-            bad |= static_cast<uint32_t>(y[c]);
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64((bad >> 16) != 0) != 0, 0)) {
-#pragma unroll
-            for (int c = 0; c < 16; c++) {
-                if (static_cast<uint32_t>(y[c]) > 65535u) {
-                    if (rec && trow)
-                        record_oor(out_oor, s, pr[j][0], cb + c);
-                    y[c] = 0;  // 65536 (or its alias -1) is stored as 0
-                }
-            }
-        }
-        qi_v4u o0, o1;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            o0[c] = pack_lo(static_cast<uint32_t>(y[2 * c]), static_cast<uint32_t>(y[2 * c + 1]));
-            o1[c] = pack_lo(static_cast<uint32_t>(y[8 + 2 * c]),
-                            static_cast<uint32_t>(y[8 + 2 * c + 1]));
-        }
-        // transposed through the wave's staging tile into whole-line stores
-        *reinterpret_cast<qi_v4u*>(stg + tl * O::kStagePitch + 32 * g) = o0;
-        *reinterpret_cast<qi_v4u*>(stg + tl * O::kStagePitch + 32 * g + 16) = o1;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        qi_v4u v2[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int orow = 8 * h + (l >> 3), c = l & 7;
-            v2[h] = *reinterpret_cast<const qi_v4u*>(stg + orow * O::kStagePitch + 16 * c);
-        }
-        if constexpr (j == RPW - 1)
-            before_stores();
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int orow = 8 * h + (l >> 3), c = l & 7;
-            const qi_v4u v = v2[h];
-            const int ot = 16 * rbj[j] + orow;
-            const uint32_t vo = (act[j] && ot < L.R)
-                                    ? static_cast<uint32_t>(pr[j][1 + h]) * ors +
-                                          static_cast<uint32_t>((col0 + 8 * c) * 2)
-                                    : 0x80000000u;
-            __builtin_amdgcn_raw_buffer_store_b128(v, go.r, static_cast<int>(vo), 0, kAuxStMf);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    // the whole K in one image (NCH = 1)
-    auto compute = [&](const uint8_t* img, long long col0, int n_lm, const int* mi,
-                       const uint32_t* mc, auto jc, auto&& before_stores) {
-        qi_v4i acc[4][3];
-        init_acc(acc, jc);
-        mma(img, acc, jc, C0{});
-        epilogue(acc, col0, n_lm, mi, mc, jc, before_stores);
-    };
-
-    auto idle_stores = [&]() {
-#pragma unroll
-        for (int h = 0; h < 2; h++)
-            __builtin_amdgcn_raw_buffer_store_b128(qi_v4u{0u, 0u, 0u, 0u}, go.r,
-                                                   static_cast<int>(0x80000000u + 16 * h), 0,
-                                                   kAuxStMf);
-    };
-
-    if (t0 >= t1)
-        return;
-    auto img = [&](int b) { return qi_lds + b * O::kImg; };
-    if constexpr (DEEP) {
-        // tiles t0 .. t0 + ND - 1 in flight, the first one into image 0
-#pragma unroll
-        for (int d = 0; d < ND; d++)
-            issue_rows_to(t0 + d, t0 + d < t1, wring[d], wxring[d], C0{});
-        write_rows_from(img(0), wring[0], wxring[0]);
-        int nl[2];
-        nl[0] = stage_marks(t0, 0);
-        nl[1] = 0;
-        __syncthreads();
-        // tile's rows are in image b; set J (tile's, already written) takes
-        // tile + ND's, set J + 1 holds tile + 1's (in flight)
-        auto body = [&](int tile, auto jc) {
-            constexpr int J = decltype(jc)::value;
-            const int b = (tile - t0) & 1;
-            const bool more = tile + 1 < t1;  // block-uniform
-            issue_rows_to(tile + ND, tile + ND < t1, wring[J], wxring[J], C0{});
-            const long long col0 = static_cast<long long>(tile) * NCOL + 64 * st;
-            auto none = [] {};
-            [&]<int... R>(std::integer_sequence<int, R...>) {
-                ((act[R] ? compute(img(b), col0, nl[b], s_i(b), s_col(b),
-                                   std::integral_constant<int, R>{}, none)
-                         : idle_stores()),
-                 ...);
-            }(std::make_integer_sequence<int, RPW>{});
-            // unconditional, so every path waits for the next set's loads
-            // here (a skipped write left them pending on one path, and the
-            // compiler then drained vmcnt(0) before reusing the registers);
-            // past the last tile it writes the invalid tile's zeros into an
-            // image no wave reads again
-            write_rows_from(img(b ^ 1), wring[(J + 1) % ND], wxring[(J + 1) % ND]);
-            if (more)
-                nl[b ^ 1] = stage_marks(tile + 1, b ^ 1);
-            __syncthreads();
-        };
-#pragma unroll 1
-        for (int tile = t0; tile < t1; tile += ND) {
-            bool done = false;
-            [&]<int... J>(std::integer_sequence<int, J...>) {
-                ((done = done || tile + J >= t1, done ? void() : body(tile + J,
-                                                                     std::integral_constant<int, J>{})),
-                 ...);
-            }(std::make_integer_sequence<int, ND>{});
-            if (done)
-                break;
-        }
-        finish();
-        return;
-    }
-    issue_rows(t0, C0{});
-    write_rows(img(0));
-    int nl[2];
-    nl[0] = stage_marks(t0, 0);
-    nl[1] = 0;
-    __syncthreads();
-    if constexpr (NCH > 1) {
-        // (tile, chunk) items, double-buffered: item q's rows in image q & 1
-        // while item q + 1's are in flight; a tile's accumulators live over
-        // its chunks, its epilogue (marks, stores) after the last one
-        static_assert(NCH == 2, "two K chunks");
-        constexpr bool rows_first = true;
-        int ib = 0;
-#pragma unroll 1
-        for (int tile = t0; tile < t1; tile++) {
-            const int mb = (tile - t0) & 1;
-            const bool more = tile + 1 < t1;  // block-uniform
-            const long long col0 = static_cast<long long>(tile) * NCOL + 64 * st;
-            qi_v4i acc[4][3];
-            using J0 = std::integral_constant<int, 0>;
-            // chunk 0; chunk 1's rows in flight, staged right after
-            issue_rows(tile, std::integral_constant<int, 1>{});
-            init_acc(acc, J0{});
-            if (act[0])
-                mma(img(ib), acc, J0{}, C0{});
-            write_rows(img(ib ^ 1));
-            __syncthreads();
-            ib ^= 1;
-            // chunk 1, then the epilogue; the next tile's chunk 0 in flight
-            if (more)
-                issue_rows(tile + 1, C0{});
-            if (act[0])
-                mma(img(ib), acc, J0{}, std::integral_constant<int, 1>{});
-            auto stage_next = [&]() {
-                if (rows_first && more)
-                    write_rows(img(ib ^ 1));
-            };
-            if (act[0])
-                epilogue(acc, col0, nl[mb], s_i(mb), s_col(mb), J0{}, stage_next);
-            else {
-                stage_next();
-                idle_stores();
-            }
-            if (more)
-                nl[mb ^ 1] = stage_marks(tile + 1, mb ^ 1);
-            __syncthreads();
-            ib ^= 1;
-        }
-        finish();
-        return;
-    }
-#pragma unroll 1
-    for (int tile = t0; tile < t1; tile++) {
-        const int b = (tile - t0) & 1;
-        const bool more = tile + 1 < t1;  // block-uniform
-        if (more)
-            issue_rows(tile + 1, C0{});
-        const long long col0 = static_cast<long long>(tile) * NCOL + 64 * st;
-        // an idle wave (row block past RB) issues the same two stores, past
-        // the buffer's extent (dropped): with the store count equal on both
-        // sides of the branch, the compiler's vmcnt wait for the next tile's
-        // rows stays behind them instead of draining this tile's stores
-        // (vmcnt(0) on the merged path)
-        // the next tile's rows go to LDS before this tile's stores issue: on
-        // gfx9 loads and stores share vmcnt, so waiting for the rows after
-        // the stores drained the stores too (the whole store latency per
-        // tile); here the wait covers the rows (issued at the top of the
-        // iteration) and the previous tile's stores
-        // (KS >= 8: k128 encode 0.985 -> 0.917 ms, k200 0.70 -> 0.67 ms; the
-        // short KS = 4 decodes keep the rows after the stores: cfg3 decode
-        // 0.186 vs 0.192 ms, gpurun_out ab_ws)
-        constexpr bool rows_first = KS >= 8;
-        auto stage_next = [&]() {
-            if (rows_first && more)
-                write_rows(img(b ^ 1));
-        };
-        [&]<int... J>(std::integer_sequence<int, J...>) {
-            ((act[J] ? compute(img(b), col0, nl[b], s_i(b), s_col(b),
-                               std::integral_constant<int, J>{}, stage_next)
-                     : (J == RPW - 1 ? (stage_next(), idle_stores()) : idle_stores())),
-             ...);
-        }(std::make_integer_sequence<int, RPW>{});
-        if (!rows_first && more)
-            write_rows(img(b ^ 1));
-        if (more)
-            nl[b ^ 1] = stage_marks(tile + 1, b ^ 1);
-        __syncthreads();
-    }
-    finish();
+    // (An include, not a template flag or a shared inline body: a shared
+    // __forceinline__ body changed the register allocation of the plain
+    // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
+    // form keeps its text and its resource report; do not fold the two.)
+    constexpr bool BOTH = false;
+#include "matrix_os_body.h"
+}
+// input and output marks in one launch (a repair): see push_slow_tile
+template <int KS, int WR, int RPW, bool TWO>
+__global__ __launch_bounds__(512) void matrix_os_kernel_both(MatArgs a, int G, int C, int TS)
+{
+    constexpr bool BOTH = true;
+#include "matrix_os_body.h"
 }
 
 
@@ -2658,8 +1509,12 @@ static int mat_launch(MatArgs a, int S, hipStream_t st)
 {
     if (grid_for(a.words - a.ext.c0, COLS, S, &a.tiles))
         return -1;
-    hipLaunchKernelGGL((matrix_kernel<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock), 0,
-                       st, a);
+    if (a.in_oor.counts && a.out_oor.counts)
+        hipLaunchKernelGGL((matrix_kernel_both<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock),
+                           0, st, a);
+    else
+        hipLaunchKernelGGL((matrix_kernel<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock), 0,
+                           st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2703,7 +1558,24 @@ static int mfma_launch(MatArgs a, long long wfull, int S, hipStream_t st)
                     hipFuncAttributeMaxDynamicSharedMemorySize,
                     static_cast<int>(G::kLdsStaged)) != hipSuccess)
                 return -2;
+            if constexpr (KS <= 2)
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(
+                                            &matrix_mfma_kernel_both<KS, NST, NW, RSPLIT>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        static_cast<int>(G::kLdsStaged)) != hipSuccess)
+                    return -2;
             attr_done.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    // input and output marks together (a repair: at most 4 row blocks; KS >=
+    // 4 runs the operand-stationary kernel)
+    if (a.in_oor.counts && a.out_oor.counts) {
+        if constexpr (KS <= 2) {
+            hipLaunchKernelGGL((matrix_mfma_kernel_both<KS, NST, NW, RSPLIT>), dim3(t * S),
+                               dim3(G::kThreads), lds, st, a);
+            return hipGetLastError() == hipSuccess ? 0 : -2;
+        } else {
+            return -1;
         }
     }
     hipLaunchKernelGGL((matrix_mfma_kernel<KS, NST, NW, RSPLIT>), dim3(t * S),
@@ -2761,6 +1633,12 @@ static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
     // the systematic decodes' two source regions (not at KS = 24 with two
     // row blocks per wave: 28 bytes of scratch; os_geom)
     constexpr bool kTwo = !(KS >= 24 && RPW == 2);
+    // the geometries a repair (at most 4 row blocks, k <= 256) reaches have
+    // a form for input and output marks in one launch
+    constexpr bool kBoth = (KS == 4 && WR == 4) || KS == 8 || (KS == 16 && RPW == 1);
+    const bool both = a.in_oor.counts && a.out_oor.counts;
+    if (both && !kBoth)
+        return -1;
     const long long TS = wfull / O::kCols;
     if (TS <= 0 || TS > 0x7fffffffLL)
         return -1;
@@ -2787,6 +1665,17 @@ static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
                  hipFuncAttributeMaxDynamicSharedMemorySize,
                  static_cast<int>(lds)) != hipSuccess))
             return -2;
+        if constexpr (kBoth)
+            if (lds > 65536 &&
+                (hipFuncSetAttribute(
+                     reinterpret_cast<const void*>(&matrix_os_kernel_both<KS, WR, RPW, true>),
+                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                     static_cast<int>(lds)) != hipSuccess ||
+                 hipFuncSetAttribute(
+                     reinterpret_cast<const void*>(&matrix_os_kernel_both<KS, WR, RPW, false>),
+                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                     static_cast<int>(lds)) != hipSuccess))
+                return -2;
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
                 &per_cu, reinterpret_cast<const void*>(&matrix_os_kernel<KS, WR, RPW, false>),
@@ -2836,6 +1725,19 @@ static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
     if (blocks > 0x7fffffffLL)
         return -1;
     a.tiles = static_cast<int>(TS);
+    if constexpr (kBoth) {
+        if (both) {
+            if (a.src.base1)
+                hipLaunchKernelGGL((matrix_os_kernel_both<KS, WR, RPW, true>),
+                                   dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds,
+                                   st, a, G, static_cast<int>(C), static_cast<int>(TS));
+            else
+                hipLaunchKernelGGL((matrix_os_kernel_both<KS, WR, RPW, false>),
+                                   dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds,
+                                   st, a, G, static_cast<int>(C), static_cast<int>(TS));
+            return hipGetLastError() == hipSuccess ? 0 : -2;
+        }
+    }
     if (a.src.base1) {
         if constexpr (!kTwo)
             return -1;  // not chosen by os_geom
@@ -3018,8 +1920,11 @@ static int launch_matrix_kernels(MatArgs a, int S, hipStream_t st, bool* dot2)
     }
 }
 
-std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two)
+std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
+                                bool both)
 {
+    // both: the forms for input and output marks in one launch (a repair)
+    const std::string sfx = both ? "_both" : "";
     // mirrors launch_matrix_kernels / mfma_dispatch / mat_dispatch for rows
     // at 8-byte aligned offsets inside 31-bit buffer ranges; the names are
     // spelled as the demangler (and rocprofv3) spells the instantiations
@@ -3040,21 +1945,21 @@ std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor
         }
         const OsGeom og = os_geom(KS, RB, two);
         if (og.wr)
-            r = "matrix_os_kernel<" + std::to_string(KS) + ", " + std::to_string(og.wr) + ", " +
+            r = "matrix_os_kernel" + sfx + "<" + std::to_string(KS) + ", " + std::to_string(og.wr) + ", " +
                 std::to_string(og.rpw) + ", " + tf(two) + ">";
         else if (KS == 4 && RB >= 4 && !in_oor && !two)
             r = "gen_mfma_kernel<8, 4>";  // (an encode: no ids, no input marks)
         else
-            r = "matrix_mfma_kernel<" + std::to_string(KS) + ", " + std::to_string(nst) + ", " +
+            r = "matrix_mfma_kernel" + sfx + "<" + std::to_string(KS) + ", " + std::to_string(nst) + ", " +
                 std::to_string(nw) + ", " + tf(rsplit) + ">";
     }
     if (wfull < words) {
         const int cols = L.KP <= 8 ? 4 : L.KP <= 16 ? 2 : 1;
-        r += std::string(r.empty() ? "" : " + ") + "matrix_kernel<" + std::to_string(L.KP) +
+        r += std::string(r.empty() ? "" : " + ") + "matrix_kernel" + sfx + "<" + std::to_string(L.KP) +
              ", " + std::to_string(cols) + ", true> (tail)";
         // the dot2 kernel's slow tiles (the matrix cores redo their own)
         if (in_oor)
-            r += " + matrix_redo_kernel";
+            r += " + matrix_redo_kernel" + sfx;
     }
     return r;
 }
@@ -3088,7 +1993,10 @@ int launch_matrix(const MatLayout& L, const int32_t* mat, long long ms,
     // the dot2 kernel's tiles with more marks than its LDS list (the matrix
     // cores redo theirs themselves): see push_slow_tile
     const int grid = (S + kRedoSpan - 1) / kRedoSpan;
-    hipLaunchKernelGGL(matrix_redo_kernel, dim3(grid), dim3(kBlock), 0, st, a, S);
+    if (out_oor)
+        hipLaunchKernelGGL(matrix_redo_kernel_both, dim3(grid), dim3(kBlock), 0, st, a, S);
+    else
+        hipLaunchKernelGGL(matrix_redo_kernel, dim3(grid), dim3(kBlock), 0, st, a, S);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

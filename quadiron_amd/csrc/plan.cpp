@@ -286,10 +286,11 @@ qi_plan* qi_plan_create_ex(int k, int m, int systematic, int flags)
                  hipMemcpy(p->d_rowmap, perm.data(), perm.size() * 4, hipMemcpyHostToDevice) ==
                      hipSuccess;
         }
-        // identity output rows of the k x k decode matrices
-        std::vector<int32_t> id(k);
-        for (int i = 0; i < k; i++)
-            id[i] = i;
+        // identity output rows of the k x k decode matrices (and of the
+        // repair matrices: up to QI_REPAIR_MAX_TARGETS rows)
+        std::vector<int32_t> id(std::max(k, QI_REPAIR_MAX_TARGETS));
+        for (size_t i = 0; i < id.size(); i++)
+            id[i] = static_cast<int32_t>(i);
         ok = ok && hipMalloc(&p->d_rowid, id.size() * 4) == hipSuccess &&
              hipMemcpy(p->d_rowid, id.data(), id.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
 

@@ -273,6 +273,102 @@ int qi_gpu_decode_packed(qi_plan* p, const void* d_ctx, const uint16_t* d_recv,
                          cs, ctx_slow(p, d_ctx, words), p->d_err, st(stream));
 }
 
+// ---- fused repair (k <= 256): R x k Lagrange matrices applied by
+// launch_matrix with input marks (the received rows') and output marks (the
+// rebuilt rows') in one launch ----
+static bool repair_ok(const qi_plan* p, int R)
+{
+    return R >= 1 && R <= std::min(QI_REPAIR_MAX_TARGETS, p->code_len - p->k);
+}
+
+// per stripe: the packed R x k block, the ids, the route table, the
+// slow-tile list and the lazy word (as a matrix decode context)
+static long long repair_ctx_words(const qi_plan* p, int R, long long words)
+{
+    const MatLayout L{R, p->k, matrix_kp(p->k)};
+    return static_cast<long long>(L.words()) + 2 * L.KP + lazy_word_off(words) + kLazyWords;
+}
+
+size_t qi_gpu_repair_ctx_bytes(const qi_plan* p, int n_targets, int n_stripes, long long words)
+{
+    if (!p || p->ntt || n_stripes < 0 || words < 0 || !repair_ok(p, n_targets))
+        return 0;
+    return static_cast<size_t>(repair_ctx_words(p, n_targets, words)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_repair_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_targets, int R,
+                      int n_stripes, const uint32_t* d_counts, const uint32_t* d_entries,
+                      int cap, long long words, void* d_ctx, void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0 || words < 0)
+        return -1;
+    if (p->ntt)
+        return QI_ERR_UNSUPPORTED;
+    if (!repair_ok(p, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids || !d_targets)
+        return -1;
+    const MatLayout L{R, p->k, matrix_kp(p->k)};
+    Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs, cap};
+    return launch_repair_ctx(p->k, p->n, p->code_len, p->r, p->sys, L, d_ids, d_targets,
+                             n_stripes, static_cast<int32_t*>(d_ctx),
+                             repair_ctx_words(p, R, words), d_counts ? &in : nullptr,
+                             p->sys ? p->k : 0, words, p->d_err, st(stream));
+}
+
+int qi_gpu_repair(qi_plan* p, const void* d_ctx, int R, const uint16_t* d_data, long long dss,
+                  long long drs, const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                  uint16_t* d_out, long long oss, long long ors, uint32_t* d_out_counts,
+                  uint32_t* d_out_entries, int out_cap, long long words, int n_stripes,
+                  void* stream)
+{
+    if (!p || !d_ctx || !d_out || !d_coded || n_stripes < 0 || words < 0)
+        return -1;
+    if (p->ntt)
+        return QI_ERR_UNSUPPORTED;
+    if (!repair_ok(p, R))
+        return -1;
+    if (n_stripes == 0 || words == 0)
+        return 0;
+    const MatLayout L{R, p->k, matrix_kp(p->k)};
+    RowSrc src;
+    if (p->sys)
+        src = RowSrc{d_data ? d_data : d_coded, dss, drs, p->k, d_coded, css, crs, 0,
+                     p->k, p->n_outputs};
+    else
+        src = RowSrc{d_coded, css, crs, 1 << 30, nullptr, 0, 0, 0, p->n_outputs, 0};
+    Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries),
+           p->n_outputs, in_cap};
+    Oor outm{d_out_counts, d_out_entries, R, out_cap};
+    RowDst out{d_out, oss, ors};
+    const long long cs = repair_ctx_words(p, R, words);
+    const int32_t* ctx = static_cast<const int32_t*>(d_ctx);
+    uint32_t* c = static_cast<uint32_t*>(const_cast<void*>(d_ctx));
+    const SlowList slow{c + L.words() + 2 * L.KP + route_tiles(words) * kRouteStride, cs};
+    // output slot j = target j: the identity row map (d_rowid holds at least
+    // QI_REPAIR_MAX_TARGETS entries)
+    return launch_matrix(L, ctx, cs, ctx + L.words(), cs, src, out, words, n_stripes,
+                         d_in_counts ? &in : nullptr, p->sys ? p->k : 0,
+                         d_out_counts ? &outm : nullptr, p->d_rowid,
+                         reinterpret_cast<const uint32_t*>(ctx + L.words() + 2 * L.KP), cs, slow,
+                         p->d_err, st(stream));
+}
+
+const char* qi_gpu_repair_kernels(const qi_plan* p, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || p->ntt || words <= 0 || !repair_ok(p, R))
+        return "";
+    const MatLayout L{R, p->k, matrix_kp(p->k)};
+    names = std::string("repair=repair_ctx_kernel<") + (p->k <= 64 && R <= 16 ? "64" : "256") +
+            "> + " + matrix_kernel_names(L, words, true, p->sys != 0, true);
+    return names.c_str();
+}
+
 const char* qi_gpu_kernels(const qi_plan* p, long long words)
 {
     static thread_local std::string names;

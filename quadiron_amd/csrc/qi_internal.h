@@ -142,6 +142,16 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
                       long long ctx_stride, const Oor* in_oor, int slot_base,
                       int by_pos, long long words, int dot2, uint32_t* d_err,
                       hipStream_t stream);
+// per-stripe repair contexts (S x k received ids, S x L.R target ids): the
+// L.R x k matrices M[j][i] = L_i(r^{targets[j]}) as complete MatLayout blocks
+// (every section written), followed by the sections of a decode context
+// (ids as dwords -- data fragments first when sys --, route table, cleared
+// slow-tile list, lazy word); k <= 256, L.R <= 64.  code_len = k + m: a
+// target must lie below it
+int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const MatLayout& L,
+                      const uint16_t* d_ids, const uint16_t* d_targets, int n_stripes,
+                      int32_t* d_ctx, long long ctx_stride, const Oor* in_oor, int slot_base,
+                      long long words, uint32_t* d_err, hipStream_t stream);
 // the dot2 sections of n_stripes contexts built with dot2 = 0 for `words`
 // columns, from their operand tiles (before a decode that runs the dot2
 // kernel over them); a stripe whose lazy word has kLazyDot2 set is skipped,
@@ -158,7 +168,8 @@ bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long wo
 // names of the kernels launch_matrix runs for L over `words` columns
 // (aligned rows; diagnostics: qi_gpu_kernels); two: rows from two source
 // regions (the systematic decode)
-std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two);
+std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
+                                bool both = false);
 // the register-codelet encode kernel launch_encode_fnt runs (aligned rows)
 std::string encode_fnt_kernel_name(int k);
 

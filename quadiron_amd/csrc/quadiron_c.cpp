@@ -3,6 +3,8 @@
 // caught at the boundary (-1 / NULL), never propagated into C callers.
 #include <cctype>
 #include <cstdio>
+#include <cstring>
+#include <cstdlib>
 #include <exception>
 #include <vector>
 
@@ -176,6 +178,28 @@ int quadiron_fnt32_reconstruct(struct QuadironFnt32* fecp, uint8_t** data,
             return -1;
         for (unsigned i = 0; i < k; i++)
             data_vec[i] = data[i] ? data[i] + md : nullptr;
+        // The fused route: one 1 x k repair on the device straight from the
+        // first k present fragments (RsFnt::repair_blocks_vertical), where
+        // the plan and the block allow it (k <= 256, single-chunk staging).
+        // QI_RECONSTRUCT_ROUTE=two-pass, read at call time, keeps the decode
+        // followed by the encode below (a test switch: both routes must give
+        // the same bytes and headers).
+        const char* route = std::getenv("QI_RECONSTRUCT_ROUTE");
+        const bool two_pass = route && std::strcmp(route, "two-pass") == 0;
+        if (!two_pass && dest < k + m && fec->repair_supported(1, block_size)) {
+            uint8_t* target = dest < k ? data[dest] : parity[dest - k];
+            if (target) {
+                std::vector<int> miss_t = miss;
+                miss_t[dest] = 1;  // rebuilt, whatever the caller flagged
+                std::vector<int> tg{static_cast<int>(dest)};
+                std::vector<uint8_t*> ov{target + md};
+                std::vector<Properties> op;
+                if (fec->repair_blocks_vertical(data_vec, par_vec, props, miss_t, tg, ov, op,
+                                                block_size))
+                    return op[0].fnt_serialize(hdr(target), md / 4) == -1 ? -1 : 0;
+                // fewer than k other fragments: the route below decides
+            }
+        }
         if (sys && dest < k) {
             // src/quadiron_c.cpp:289-320
             std::vector<bool> w(k, false);
