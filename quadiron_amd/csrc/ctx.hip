@@ -1431,9 +1431,8 @@ int fill_dot2_sections(const MatLayout& L, int32_t* d_ctx, long long ctx_stride,
 {
     if (S <= 0)
         return 0;
-    const long long lazy_off = L.words() + 2LL * L.KP + lazy_word_off(words);
     hipLaunchKernelGGL(fill_dot2_kernel, dim3(S), dim3(256), 0, st, L, d_ctx, ctx_stride,
-                       lazy_off);
+                       MatCtxView(L, d_ctx, ctx_stride, words).lazy_off);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1445,7 +1444,8 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
     if (k > kMatMaxKin || S <= 0)
         return -3;
     Oor none{nullptr, nullptr, 0, 0};
-    if (k > 128) {
+    const int threads = decode_ctx_threads(k);
+    if (threads == 1024) {
         // the matrix rows in the context itself (no LDS image); 1024 threads
         // keep 4x more of the packing and tile passes' row loads in flight
         // (k256 decode 0.81 -> 0.77 ms, k200 2.09 -> 2.05 ms)
@@ -1455,18 +1455,14 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
         const size_t lds =
             !dot2 ? static_cast<size_t>(ctx_chunk(k)) * ((k + 3) & ~3) * 4 : 0;
         static std::atomic<uint64_t> attr_done{0};
-        static std::atomic<int> cus_of[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess)
-            return -2;
-        const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-        if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
+        static std::atomic<int> cus_of[kOnceDevices];
+        const int dev = once_per_device(attr_done, [](int d) {
             int cus = 0;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) !=
                 hipSuccess)
-                return -2;
-            if (bit)
-                cus_of[dev].store(std::max(1, cus), std::memory_order_relaxed);
+                return false;
+            if (d < kOnceDevices)
+                cus_of[d].store(std::max(1, cus), std::memory_order_relaxed);
             const void* fn = reinterpret_cast<const void*>(&decode_ctx_kernel<1024, true>);
             constexpr size_t kDynMax =
                 std::max(static_cast<size_t>(kCtxChunk) * kMatGenMaxKin, size_t{32} * kMatMaxKin) * 4;
@@ -1474,19 +1470,19 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
             // the largest chunk must fit a CU (160 KiB): an added __shared__
             // would make every k > 256 context launch fail, so say so here
             hipFuncAttributes fa{};
-            if (hipFuncGetAttributes(&fa, fn) != hipSuccess ||
-                fa.sharedSizeBytes + kDynMax > static_cast<size_t>(kCtxLdsCap))
-                return -2;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(kDynMax)) != hipSuccess)
-                return -2;
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
+            return hipFuncGetAttributes(&fa, fn) == hipSuccess &&
+                   fa.sharedSizeBytes + kDynMax <= static_cast<size_t>(kCtxLdsCap) &&
+                   hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(kDynMax)) == hipSuccess;
+        });
+        if (dev < 0)
+            return -2;
         // the whole-tile forms split a stripe's row chunks over up to (CUs /
         // stripes) blocks (one block per CU each)
         int nb = 1;
         if (!dot2) {
-            const int cus = bit ? cus_of[dev].load(std::memory_order_relaxed) : 256;
+            const int cus =
+                dev < kOnceDevices ? cus_of[dev].load(std::memory_order_relaxed) : 256;
             const int nch = (k + ctx_chunk(k) - 1) / ctx_chunk(k);
             nb = std::max(1, std::min(nch, cus / S));
         }
@@ -1512,8 +1508,7 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(lds)) != hipSuccess)
         return -2;
-    // 2 waves at k <= 32: wave 1 routes the marks while wave 0 builds A(x)
-    if (k > 32)
+    if (threads == 256)
         hipLaunchKernelGGL((decode_ctx_lds_kernel<256>), dim3(S), dim3(256), lds, st, k, rp, lgn,
                            mode, L, d_ids, d_ctx, ctx_stride, in_oor ? *in_oor : none,
                            slot_base, by_pos, words, dot2, err);
@@ -1761,7 +1756,7 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
     // up to 65 KB of rows (R = 64, k = 256): opted in per launch (cheap; the
     // device may differ between calls)
     const size_t lds = static_cast<size_t>(L.R) * ctx_pitch(k) * 4;
-    if (k <= 64 && L.R <= 16) {  // at most 16 x 68 words of rows
+    if (repair_ctx_threads(k, L.R) == 64) {
         hipLaunchKernelGGL(repair_ctx_kernel<64>, dim3(S), dim3(64), lds, st, k, code_len, rp,
                            lgn, sys, L, d_ids, d_targets, d_ctx, ctx_stride,
                            in_oor ? *in_oor : none, slot_base, words, err);

@@ -1480,166 +1480,86 @@ int launch_encode_fnt(int k, int n, int n_out, const int32_t* d_twist,
     return -3;  // K > 64: caller uses the matrix path
 }
 
-int matrix_kp(int kin)
+// The launchers below run what matrix_route (matrix_route.h) chose: each
+// takes its template parameters and the runtime forms (`both`, `two`) from
+// the route and decides only its grid.
+
+// dynamic LDS above the default limit needs opting in per kernel
+static bool lds_opt_in(const void* fn, size_t bytes)
 {
-    const int pairs = (kin + 1) / 2;
-    if (pairs <= 2)
-        return 2;
-    if (pairs <= 4)
-        return 4;
-    if (pairs <= 8)
-        return 8;
-    if (pairs <= 16)
-        return 16;
-    if (pairs <= 32)
-        return 32;
-    if (pairs <= 64)
-        return 64;
-    if (pairs <= 128)
-        return 128;
-    if (2 * pairs <= kMatGenMaxKin + 1)
-        return 256;  // 256 < k <= 384: matrix cores only (no dot2 tails)
-    if (2 * pairs <= kMatMaxKin + 1)
-        return 320;  // 384 < k <= 640: (the context layout's unused section)
-    return -1;  // larger k runs the NTT path (ntt.hip)
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(bytes)) == hipSuccess;
 }
 
 template <int KP, int COLS, bool BUF>
-static int mat_launch(MatArgs a, int S, hipStream_t st)
+static int mat_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 {
     if (grid_for(a.words - a.ext.c0, COLS, S, &a.tiles))
         return -1;
-    if (a.in_oor.counts && a.out_oor.counts)
-        hipLaunchKernelGGL((matrix_kernel_both<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock),
-                           0, st, a);
-    else
-        hipLaunchKernelGGL((matrix_kernel<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock), 0,
-                           st, a);
+    const auto fn = r.both ? &matrix_kernel_both<KP, COLS, BUF> : &matrix_kernel<KP, COLS, BUF>;
+    hipLaunchKernelGGL(fn, dim3(a.tiles * S), dim3(kBlock), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// columns per lane: 4 (b64 row loads) while the packed rows fit in
-// registers, 2 up to KP 16, else 1; cols 1 is also the flat (BUF=false) path
-template <int KP>
-static int mat_dispatch(int cols, const MatArgs& a, int S, hipStream_t st)
-{
-    const bool buf = a.ext.e0 && a.ext.eo && (!a.src.base1 || a.ext.e1);
-    if (!buf)
-        return mat_launch<KP, 1, false>(a, S, st);
-    if constexpr (KP <= 8)
-        if (cols == 4)
-            return mat_launch<KP, 4, true>(a, S, st);
-    if constexpr (KP <= 16)
-        if (cols >= 2)
-            return mat_launch<KP, 2, true>(a, S, st);
-    return mat_launch<KP, 1, true>(a, S, st);
 }
 
 template <int KS, int NST, int NW, bool RSPLIT>
-static int mfma_launch(MatArgs a, long long wfull, int S, hipStream_t st)
+static int mfma_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 {
     using G = MfmaTile<KS, NST, NW>;
-    const long long t = wfull / G::kCols;
-    if (t <= 0 || t * S > 0x7fffffffLL)
+    using Fn = void (*)(MatArgs);
+    const Fn one = &matrix_mfma_kernel<KS, NST, NW, RSPLIT>;
+    // input and output marks together (a repair: at most 4 row blocks; KS >=
+    // 4 runs the operand-stationary kernel)
+    Fn both = nullptr;
+    if constexpr (mfma_has_both(KS))
+        both = &matrix_mfma_kernel_both<KS, NST, NW, RSPLIT>;
+    const Fn run = r.both ? both : one;
+    const long long t = r.wfull / G::kCols;
+    if (!run || t <= 0 || t * S > 0x7fffffffLL)
         return -1;
     a.tiles = static_cast<int>(t);
     const size_t lds = a.L.RB() > 1 ? G::kLdsStaged : G::kLds;
-    // dynamic LDS above 64 KiB needs opting in, once per device (a bit per
-    // device; a race only repeats the idempotent call)
     static std::atomic<uint64_t> attr_done{0};
-    if (G::kLdsStaged > 65536) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess)
-            return -2;
-        const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-        if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(&matrix_mfma_kernel<KS, NST, NW, RSPLIT>),
-                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                    static_cast<int>(G::kLdsStaged)) != hipSuccess)
-                return -2;
-            if constexpr (KS <= 2)
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(
-                                            &matrix_mfma_kernel_both<KS, NST, NW, RSPLIT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        static_cast<int>(G::kLdsStaged)) != hipSuccess)
-                    return -2;
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    // input and output marks together (a repair: at most 4 row blocks; KS >=
-    // 4 runs the operand-stationary kernel)
-    if (a.in_oor.counts && a.out_oor.counts) {
-        if constexpr (KS <= 2) {
-            hipLaunchKernelGGL((matrix_mfma_kernel_both<KS, NST, NW, RSPLIT>), dim3(t * S),
-                               dim3(G::kThreads), lds, st, a);
-            return hipGetLastError() == hipSuccess ? 0 : -2;
-        } else {
-            return -1;
-        }
-    }
-    hipLaunchKernelGGL((matrix_mfma_kernel<KS, NST, NW, RSPLIT>), dim3(t * S),
-                       dim3(G::kThreads), lds, st, a);
+    if (G::kLdsStaged > 65536 && once_per_device(attr_done, [&](int) {
+            return lds_opt_in(reinterpret_cast<const void*>(one), G::kLdsStaged) &&
+                   (!both || lds_opt_in(reinterpret_cast<const void*>(both), G::kLdsStaged));
+        }) < 0)
+        return -2;
+    hipLaunchKernelGGL(run, dim3(t * S), dim3(G::kThreads), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-
-static int gen_launch(MatArgs a, long long wfull, int S, hipStream_t st)
+template <int NST, int NW>
+static int gen_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 {
-    constexpr int NST = 8, NW = 4;
     using G = MfmaTile<4, NST, NW>;
-    const long long t = wfull / G::kCols;
+    const long long t = r.wfull / G::kCols;
     if (t <= 0 || t * S > 0x7fffffffLL)
         return -1;
     a.tiles = static_cast<int>(t);
     static std::atomic<uint64_t> attr_done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
+    if (once_per_device(attr_done, [](int) {
+            return lds_opt_in(reinterpret_cast<const void*>(&gen_mfma_kernel<NST, NW>),
+                              G::kLdsStaged);
+        }) < 0)
         return -2;
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-    if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_mfma_kernel<NST, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(G::kLdsStaged)) != hipSuccess)
-            return -2;
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
     hipLaunchKernelGGL((gen_mfma_kernel<NST, NW>), dim3(t * S), dim3(G::kThreads),
                        G::kLdsStaged, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// Block geometry by matrix shape (kRouteTile = 1024 must be a multiple of
-// the block width):
-//  - short matrices (RB < 4: decodes, k x k): 4 waves, each on its own super
-//    tiles; 1024 columns at KS = 1 (35 KB LDS), 512 at KS = 2, 4 (one u16
-//    column per lane at KS = 4 -- 256 columns -- slowed the cfg3 decode,
-//    profiles/r1_ab_mfma_cols1.txt);
-//  - tall ones (RB >= 4: encode generators): the waves split the row blocks
-//    over the whole image.  8 waves over 256 columns (54 KB LDS: 2 blocks =
-//    4 waves per SIMD instead of 2) measured slower on the 1024 x 64 cfg3
-//    generator (1.37 vs 1.22 ms, gpurun_out r2f), so the block stays at 4
-//    waves.
-
-// operand-stationary kernel (KS = 8, 16): G row-block groups of 8 waves, C
-// column ranges per stripe; about two blocks per CU over the launch
-static constexpr bool kMmOs = true;
-constexpr long long kOsMaxTiles = 4096;  // tiles per block (slow-tile bitmask)
-
 template <int KS, int WR, int RPW>
-static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
+static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 {
     using O = OsTile<OsK<KS>::KC, WR>;
-    // the systematic decodes' two source regions (not at KS = 24 with two
-    // row blocks per wave: 28 bytes of scratch; os_geom)
-    constexpr bool kTwo = !(KS >= 24 && RPW == 2);
-    // the geometries a repair (at most 4 row blocks, k <= 256) reaches have
-    // a form for input and output marks in one launch
-    constexpr bool kBoth = (KS == 4 && WR == 4) || KS == 8 || (KS == 16 && RPW == 1);
-    const bool both = a.in_oor.counts && a.out_oor.counts;
-    if (both && !kBoth)
-        return -1;
-    const long long TS = wfull / O::kCols;
+    // the forms the library has (matrix_route.h), indexed by two + 2 * both
+    void (*fns[4])(MatArgs, int, int, int) = {&matrix_os_kernel<KS, WR, RPW, false>};
+    if constexpr (os_has_two(KS, RPW))
+        fns[1] = &matrix_os_kernel<KS, WR, RPW, true>;
+    if constexpr (os_has_both(KS, WR, RPW)) {
+        fns[2] = &matrix_os_kernel_both<KS, WR, RPW, false>;
+        fns[3] = &matrix_os_kernel_both<KS, WR, RPW, true>;
+    }
+    const long long TS = r.wfull / O::kCols;
     if (TS <= 0 || TS > 0x7fffffffLL)
         return -1;
     const int RB = a.L.RB();
@@ -1648,48 +1568,24 @@ static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
     // per device, once: the dynamic-LDS attribute and the number of blocks
     // the device holds at once (CUs x blocks per CU)
     static std::atomic<uint64_t> attr_done{0};
-    static std::atomic<int> slots_of[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-        return -2;
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-    if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
-        const void* two_fn = nullptr;
-        if constexpr (kTwo)
-            two_fn = reinterpret_cast<const void*>(&matrix_os_kernel<KS, WR, RPW, true>);
-        if (lds > 65536 &&
-            ((two_fn && hipFuncSetAttribute(two_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            static_cast<int>(lds)) != hipSuccess) ||
-             hipFuncSetAttribute(
-                 reinterpret_cast<const void*>(&matrix_os_kernel<KS, WR, RPW, false>),
-                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                 static_cast<int>(lds)) != hipSuccess))
-            return -2;
-        if constexpr (kBoth)
-            if (lds > 65536 &&
-                (hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&matrix_os_kernel_both<KS, WR, RPW, true>),
-                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                     static_cast<int>(lds)) != hipSuccess ||
-                 hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&matrix_os_kernel_both<KS, WR, RPW, false>),
-                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                     static_cast<int>(lds)) != hipSuccess))
-                return -2;
+    static std::atomic<int> slots_of[kOnceDevices];
+    const int dev = once_per_device(attr_done, [&](int d) {
+        for (const auto fn : fns)
+            if (fn && lds > 65536 && !lds_opt_in(reinterpret_cast<const void*>(fn), lds))
+                return false;
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, reinterpret_cast<const void*>(&matrix_os_kernel<KS, WR, RPW, false>),
-                O::kThreads, lds) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                hipSuccess)
-            return -2;
-        if (bit) {
-            slots_of[dev].store(std::max(1, per_cu) * std::max(1, cus),
-                                std::memory_order_relaxed);
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    const long long slots = bit ? slots_of[dev].load(std::memory_order_relaxed) : 256;
+                &per_cu, reinterpret_cast<const void*>(fns[0]), O::kThreads, lds) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess)
+            return false;
+        if (d < kOnceDevices)
+            slots_of[d].store(std::max(1, per_cu) * std::max(1, cus), std::memory_order_relaxed);
+        return true;
+    });
+    if (dev < 0)
+        return -2;
+    const long long slots =
+        dev < kOnceDevices ? slots_of[dev].load(std::memory_order_relaxed) : 256;
     // blocks wanted over the launch: ~2 per CU, or ~8 for the short KS = 4
     // decodes (cfg3: two column ranges per stripe, 0.168 -> 0.158 ms; the
     // KS >= 8 decodes and generators lose at 2048, gpurun_out ab_x4)
@@ -1725,121 +1621,59 @@ static int os_launch(MatArgs a, long long wfull, int S, hipStream_t st)
     if (blocks > 0x7fffffffLL)
         return -1;
     a.tiles = static_cast<int>(TS);
-    if constexpr (kBoth) {
-        if (both) {
-            if (a.src.base1)
-                hipLaunchKernelGGL((matrix_os_kernel_both<KS, WR, RPW, true>),
-                                   dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds,
-                                   st, a, G, static_cast<int>(C), static_cast<int>(TS));
-            else
-                hipLaunchKernelGGL((matrix_os_kernel_both<KS, WR, RPW, false>),
-                                   dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds,
-                                   st, a, G, static_cast<int>(C), static_cast<int>(TS));
-            return hipGetLastError() == hipSuccess ? 0 : -2;
-        }
-    }
-    if (a.src.base1) {
-        if constexpr (!kTwo)
-            return -1;  // not chosen by os_geom
-        else
-            hipLaunchKernelGGL((matrix_os_kernel<KS, WR, RPW, true>),
-                               dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds, st,
-                               a, G, static_cast<int>(C), static_cast<int>(TS));
-    } else
-        hipLaunchKernelGGL((matrix_os_kernel<KS, WR, RPW, false>),
-                           dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds, st,
-                           a, G, static_cast<int>(C), static_cast<int>(TS));
+    const auto fn = fns[(r.two ? 1 : 0) + (r.both ? 2 : 0)];
+    if (!fn)
+        return -1;  // (matrix_route reports these as errors)
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds, st, a, G,
+                       static_cast<int>(C), static_cast<int>(TS));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// operand-stationary geometry by shape: (WR row-block slots, RPW row blocks
-// per wave); 0 = the per-launch kernel
-struct OsGeom {
-    int wr, rpw;
-};
-inline OsGeom os_geom(int KS, int RB, bool two)
+// The one map from a route to its instantiation: every matrix kernel of the
+// library appears here, and nothing else launches one (the redo launch,
+// which has no parameters, is launch_matrix's).
+static int launch_route(const MatRoute& r, MatArgs a, int S, hipStream_t st)
 {
-    if (!kMmOs)
-        return {0, 0};
-    // KS = 16, 20, 24 with more than one block of 8 row blocks, one source
-    // region: two row blocks per wave, so one group (k200, k256) or two
-    // (k300, k384) stage each input tile instead of two or three (k200
-    // decode 0.757 -> 0.66 ms, k300 0.704 -> 0.653, k256 0.30 -> 0.278,
-    // k384 0.88 -> 0.83; encodes ~10 % faster).  The systematic decodes'
-    // two regions too since their rows load once (round 6), but not at KS =
-    // 24 (28 bytes of scratch); not at KS = 8 (k128 encode 0.725 -> 0.757
-    // ms; gpurun_out/ab_r5k, ab_r5l)
-    if ((KS == 16 || KS == 20 || (KS == 24 && !two)) && RB > 8)
-        return {8, 2};
-    // KS = 40 (384 < k <= 640, K chunks): one row block per wave (80
-    // operand VGPRs), one or two source regions
-    if (KS > 24)
-        return {8, 1};
-    if (KS >= 8)
-        return {8, 1};
-    // KS = 4: the short decode matrices (2 super tiles per 128-column tile)
-    // and up to 8 row blocks; the tall generators (RB = 64 at cfg3) stay on
-    // matrix_mfma_kernel (os at 1 or 4 row blocks per wave: 1.48 / 1.37 vs
-    // 1.05 ms, gpurun_out ab_os2 / ab_os3)
-    if (KS == 4 && RB <= 8)
-        return RB <= 4 ? OsGeom{4, 1} : OsGeom{8, 1};
-    return {0, 0};
-}
-
-template <int KS>
-static int mfma_dispatch(const MatArgs& a, long long wfull, int S, hipStream_t st)
-{
-    if constexpr (KS == 4) {
-        const OsGeom og = os_geom(KS, a.L.RB(), a.src.base1 != nullptr);
-        if (og.wr == 4 && og.rpw == 1)
-            return os_launch<KS, 4, 1>(a, wfull, S, st);
-        if (og.wr == 8 && og.rpw == 1)
-            return os_launch<KS, 8, 1>(a, wfull, S, st);
-    } else if constexpr (KS == 8) {
-        if (os_geom(KS, a.L.RB(), a.src.base1 != nullptr).wr)
-            return os_launch<KS, 8, 1>(a, wfull, S, st);
-    } else if constexpr (KS == 16 || KS == 20 || KS == 24) {
-        const OsGeom og = os_geom(KS, a.L.RB(), a.src.base1 != nullptr);
-        if (og.wr && og.rpw == 2)
-            return os_launch<KS, 8, 2>(a, wfull, S, st);
-        if (og.wr)
-            return os_launch<KS, 8, 1>(a, wfull, S, st);
-    } else if constexpr (KS == 40) {
-        if (os_geom(KS, a.L.RB(), a.src.base1 != nullptr).wr)
-            return os_launch<KS, 8, 1>(a, wfull, S, st);
+    if (r.err == -1)
         return -1;
-    }
-    constexpr int NSTS = KS == 1 ? 16 : 8;
-    const int RB = a.L.RB();
-    if constexpr (KS > 16) {
-        return -1;  // only the operand-stationary kernel takes kin > 256
-    } else if constexpr (KS == 16) {
-        // 128 < k <= 256: a 512-row byte-plane image of 64 columns (41 KB);
-        // 8 waves over 128 columns (94 KB, 1 block per CU) measured the
-        // same at k200 / k256 (profiles/r2_ab_round2b.txt)
-        (void)RB;
-        return mfma_launch<KS, 1, 4, true>(a, wfull, S, st);
-    } else if constexpr (KS == 8) {
-        // 65 <= k <= 128: a 256-row byte-plane image, the waves always
-        // splitting the row blocks (a wave past the last row block idles)
-        // (256 columns, 81 KB with the staging tiles: 2 blocks per CU as
-        // the VGPRs allow anyway; 128 columns measured 5 % slower at k128)
-        (void)RB;
-        return mfma_launch<KS, 4, 4, true>(a, wfull, S, st);
-    } else {
-        if constexpr (KS == 4) {
-            // a tall generator over one source region (every encode):
-            // the lean generator kernel
-            if (RB >= 4 && !a.in_oor.counts && !a.route && !a.ids &&
-                !a.src.base1)
-                return gen_launch(a, wfull, S, st);
+#define QI_OS(KS_, WR_, RPW_)                                  \
+    if (r.KS == KS_ && r.WR == WR_ && r.RPW == RPW_)           \
+        rc = os_launch<KS_, WR_, RPW_>(a, r, S, st);
+#define QI_MFMA(KS_, NST_, NW_, RS_)                                          \
+    if (r.KS == KS_ && r.NST == NST_ && r.NW == NW_ && r.RSPLIT == RS_)       \
+        rc = mfma_launch<KS_, NST_, NW_, RS_>(a, r, S, st);
+    if (r.core != MatCore::kNone) {
+        int rc = -1;
+        if (r.core == MatCore::kGen) {
+            if (r.NST == 8 && r.NW == 4)
+                rc = gen_launch<8, 4>(a, r, S, st);
+        } else if (r.core == MatCore::kOs) {
+            QI_OS(4, 4, 1) QI_OS(4, 8, 1) QI_OS(8, 8, 1) QI_OS(16, 8, 1) QI_OS(16, 8, 2)
+            QI_OS(20, 8, 1) QI_OS(20, 8, 2) QI_OS(24, 8, 1) QI_OS(24, 8, 2) QI_OS(40, 8, 1)
+        } else {
+            QI_MFMA(1, 16, 4, false) QI_MFMA(1, 16, 4, true) QI_MFMA(2, 8, 4, false)
+            QI_MFMA(2, 8, 4, true) QI_MFMA(4, 8, 4, false) QI_MFMA(4, 8, 4, true)
+            QI_MFMA(8, 4, 4, true) QI_MFMA(16, 1, 4, true)
         }
-        if (RB >= 4)
-            return mfma_launch<KS, NSTS, 4, true>(a, wfull, S, st);
-        return mfma_launch<KS, NSTS, 4, false>(a, wfull, S, st);
+        if (rc || !r.tail)
+            return rc;
+        a.ext.c0 = r.wfull;
     }
+#undef QI_OS
+#undef QI_MFMA
+#define QI_TAIL(KP_, COLS_, BUF_)                                \
+    if (r.KP == KP_ && r.COLS == COLS_ && r.BUF == BUF_)         \
+        return mat_launch<KP_, COLS_, BUF_>(a, r, S, st);
+    QI_TAIL(2, 1, false) QI_TAIL(2, 1, true) QI_TAIL(2, 2, true) QI_TAIL(2, 4, true)
+    QI_TAIL(4, 1, false) QI_TAIL(4, 1, true) QI_TAIL(4, 2, true) QI_TAIL(4, 4, true)
+    QI_TAIL(8, 1, false) QI_TAIL(8, 1, true) QI_TAIL(8, 2, true) QI_TAIL(8, 4, true)
+    QI_TAIL(16, 1, false) QI_TAIL(16, 1, true) QI_TAIL(16, 2, true)
+    QI_TAIL(32, 1, false) QI_TAIL(32, 1, true)
+    QI_TAIL(64, 1, false) QI_TAIL(64, 1, true)
+    QI_TAIL(128, 1, false) QI_TAIL(128, 1, true)
+#undef QI_TAIL
+    return -3;
 }
-
 
 // rows at `cols`-word aligned offsets (source regions and destination)
 static bool rows_aligned(int cols, const RowSrc& src, const RowDst& dst)
@@ -1855,113 +1689,32 @@ static MatExt mat_ext(const RowSrc& src, int R, const RowDst& dst, long long wor
                   extent(R, dst.rs, words), 0};
 }
 
+// what matrix_route reads of a launch
+static MatRouteIn route_in(const MatArgs& a)
+{
+    const bool buf = a.ext.e0 && a.ext.eo && (!a.src.base1 || a.ext.e1);
+    const int align = !rows_aligned(2, a.src, a.dst) ? 1 : rows_aligned(4, a.src, a.dst) ? 4 : 2;
+    return MatRouteIn{a.L, a.words, buf, align, a.in_oor.counts != nullptr,
+                      a.out_oor.counts != nullptr, a.ids != nullptr, a.route != nullptr,
+                      a.src.base1 != nullptr};
+}
+
 bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long words)
 {
-    const MatExt e = mat_ext(src, R, dst, words);
-    const bool buf = e.e0 && e.eo && (!src.base1 || e.e1);
-    return buf && rows_aligned(2, src, dst) && rows_aligned(4, src, dst) &&
-           words >= kRouteTile;
+    MatArgs a{};
+    a.src = src;
+    a.dst = dst;
+    a.ext = mat_ext(src, R, dst, words);
+    const MatRouteIn in = route_in(a);
+    return in.buf && in.align == 4 && words >= kRouteTile;
 }
 
-static int launch_matrix_kernels(MatArgs a, int S, hipStream_t st, bool* dot2)
-{
-    *dot2 = false;
-    const MatLayout& L = a.L;
-    const RowSrc& src = a.src;
-    const RowDst& dst = a.dst;
-    const long long words = a.words;
-    const bool a2 = rows_aligned(2, src, dst);
-    const bool buf = a.ext.e0 && a.ext.eo && (!src.base1 || a.ext.e1);
-    const bool a4 = a2 && rows_aligned(4, src, dst);
-    const int cols = !buf ? 1 : a4 ? 4 : a2 ? 2 : 1;
-    // whole kRouteTile column tiles on the matrix cores, the tail (and
-    // everything the MFMA kernel does not take) on the dot2 kernel
-    const long long wfull = words / kRouteTile * kRouteTile;
-    if (L.KS() > 0 && buf && a4 && wfull > 0) {
-        int rc;
-        if (L.KS() == 1)
-            rc = mfma_dispatch<1>(a, wfull, S, st);
-        else if (L.KS() == 2)
-            rc = mfma_dispatch<2>(a, wfull, S, st);
-        else if (L.KS() == 4)
-            rc = mfma_dispatch<4>(a, wfull, S, st);
-        else if (L.KS() == 8)
-            rc = mfma_dispatch<8>(a, wfull, S, st);
-        else if (L.KS() == 16)
-            rc = mfma_dispatch<16>(a, wfull, S, st);
-        else if (L.KS() == 20)
-            rc = mfma_dispatch<20>(a, wfull, S, st);
-        else if (L.KS() == 24)
-            rc = mfma_dispatch<24>(a, wfull, S, st);
-        else
-            rc = mfma_dispatch<40>(a, wfull, S, st);
-        if (rc || wfull == words)
-            return rc;
-        a.ext.c0 = wfull;
-    }
-    *dot2 = true;
-    switch (L.KP) {
-    case 2:
-        return mat_dispatch<2>(cols, a, S, st);
-    case 4:
-        return mat_dispatch<4>(cols, a, S, st);
-    case 8:
-        return mat_dispatch<8>(cols, a, S, st);
-    case 16:
-        return mat_dispatch<16>(cols, a, S, st);
-    case 32:
-        return mat_dispatch<32>(cols, a, S, st);
-    case 64:
-        return mat_dispatch<64>(cols, a, S, st);
-    case 128:
-        return mat_dispatch<128>(cols, a, S, st);
-    default:
-        return -3;
-    }
-}
-
+// for aligned rows in buffer range; a decode's ids and route table come with
+// its input marks.  both: input and output marks in one launch (a repair)
 std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
                                 bool both)
 {
-    // both: the forms for input and output marks in one launch (a repair)
-    const std::string sfx = both ? "_both" : "";
-    // mirrors launch_matrix_kernels / mfma_dispatch / mat_dispatch for rows
-    // at 8-byte aligned offsets inside 31-bit buffer ranges; the names are
-    // spelled as the demangler (and rocprofv3) spells the instantiations
-    std::string r;
-    const long long wfull = words / kRouteTile * kRouteTile;
-    const int KS = L.KS();
-    auto tf = [](bool b) { return std::string(b ? "true" : "false"); };
-    if (KS > 0 && wfull > 0) {
-        const int RB = L.RB();
-        int nst = KS == 1 ? 16 : 8, nw = 4;
-        bool rsplit = RB >= 4;
-        if (KS == 16) {
-            nst = 1;
-            rsplit = true;
-        } else if (KS == 8) {
-            nst = 4;
-            rsplit = true;
-        }
-        const OsGeom og = os_geom(KS, RB, two);
-        if (og.wr)
-            r = "matrix_os_kernel" + sfx + "<" + std::to_string(KS) + ", " + std::to_string(og.wr) + ", " +
-                std::to_string(og.rpw) + ", " + tf(two) + ">";
-        else if (KS == 4 && RB >= 4 && !in_oor && !two)
-            r = "gen_mfma_kernel<8, 4>";  // (an encode: no ids, no input marks)
-        else
-            r = "matrix_mfma_kernel" + sfx + "<" + std::to_string(KS) + ", " + std::to_string(nst) + ", " +
-                std::to_string(nw) + ", " + tf(rsplit) + ">";
-    }
-    if (wfull < words) {
-        const int cols = L.KP <= 8 ? 4 : L.KP <= 16 ? 2 : 1;
-        r += std::string(r.empty() ? "" : " + ") + "matrix_kernel" + sfx + "<" + std::to_string(L.KP) +
-             ", " + std::to_string(cols) + ", true> (tail)";
-        // the dot2 kernel's slow tiles (the matrix cores redo their own)
-        if (in_oor)
-            r += " + matrix_redo_kernel" + sfx;
-    }
-    return r;
+    return to_string(matrix_route(MatRouteIn{L, words, true, 4, in_oor, both, in_oor, in_oor, two}));
 }
 
 std::string encode_fnt_kernel_name(int k)
@@ -1986,17 +1739,15 @@ int launch_matrix(const MatLayout& L, const int32_t* mat, long long ms,
     const Oor none{nullptr, nullptr, 0, 0};
     MatArgs a{L, mat, ms, ids, is, src, dst, mat_ext(src, L.R, dst, words), words, 0, in_oor ? *in_oor : none, slot_base, out_oor ? *out_oor : none,
               rowmap, route, rstride, in_oor ? slow : SlowList{nullptr, 0}, err};
-    bool dot2 = false;
-    const int rc = launch_matrix_kernels(a, S, st, &dot2);
-    if (rc || !in_oor || !dot2)
+    const MatRoute r = matrix_route(route_in(a));
+    const int rc = launch_route(r, a, S, st);
+    if (rc || !r.redo)
         return rc;
     // the dot2 kernel's tiles with more marks than its LDS list (the matrix
     // cores redo theirs themselves): see push_slow_tile
     const int grid = (S + kRedoSpan - 1) / kRedoSpan;
-    if (out_oor)
-        hipLaunchKernelGGL(matrix_redo_kernel_both, dim3(grid), dim3(kBlock), 0, st, a, S);
-    else
-        hipLaunchKernelGGL(matrix_redo_kernel, dim3(grid), dim3(kBlock), 0, st, a, S);
+    const auto redo = r.both ? &matrix_redo_kernel_both : &matrix_redo_kernel;
+    hipLaunchKernelGGL(redo, dim3(grid), dim3(kBlock), 0, st, a, S);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -36,14 +36,45 @@ bool use_matrix(const qi_plan* p, long long words)
     return !p->ntt || (p->mbig && words % kRouteTile == 0);
 }
 
-// the matrix-format part of a context: packed block, ids, route table,
-// slow-tile list, lazy-section word
-long long mat_ctx_words(const qi_plan* p, long long words)
+// the R x k matrices of a repair
+MatLayout repair_layout(const qi_plan* p, int R)
 {
-    const MatLayout L = ctx_layout(p);
-    return static_cast<long long>(L.words()) + 2 * L.KP + lazy_word_off(words) + kLazyWords;
+    return MatLayout{R, p->k, matrix_kp(p->k)};
 }
 
+// the matrix-format part of a context: packed block, ids, route table,
+// slow-tile list, lazy-section word
+long long mat_ctx_words(const MatLayout& L, long long words)
+{
+    return MatCtxView(L, nullptr, 0, words).size();
+}
+
+// the plan's fragment rows: a systematic code's data fragments (ids below
+// k; in the coded region's place when the caller holds none) and its coded
+// ones, or the n coded fragments
+RowSrc plan_src(const qi_plan* p, const uint16_t* d_data, long long dss, long long drs,
+                const uint16_t* d_coded, long long css, long long crs)
+{
+    if (p->sys)
+        return RowSrc{d_data ? d_data : d_coded, dss, drs, p->k, d_coded, css, crs, 0,
+                      p->k, p->n_outputs};
+    return RowSrc{d_coded, css, crs, 1 << 30, nullptr, 0, 0, 0, p->n_outputs, 0};
+}
+
+// apply the matrices of the contexts `v` (decode or repair) to the rows
+int apply_ctx(const qi_plan* p, const MatLayout& L, const MatCtxView& v, const RowSrc& src,
+              const RowDst& out, long long words, int S, const Oor* in, int slot_base,
+              const Oor* out_marks, hipStream_t s)
+{
+    // output row t = matrix row t (d_rowid: the identity, at least
+    // QI_REPAIR_MAX_TARGETS entries)
+    return launch_matrix(L, v.ctx, v.stride, v.ids(), v.stride, src, out, words, S, in, slot_base,
+                         out_marks, p->d_rowid, v.route(), v.stride, v.slow(), p->d_err, s);
+}
+
+// The decode of qi_gpu_decode and qi_gpu_decode_packed, which differ in the
+// rows (src, by id or by position) and in the marks' slots (`slots` per
+// stripe, slot = position or id - slot_base).
 // A context built for a whole-tile width carries only the matrix-core
 // form.  Rows the matrix cores cannot address send every column to the dot2
 // kernel (k <= 256), whose sections are filled from the tiles by the first
@@ -51,18 +82,30 @@ long long mat_ctx_words(const qi_plan* p, long long words)
 // by the first such decode from the ids the matrix context holds; the
 // context's lazy word records both, so each is filled once (qi_gpu.h: a
 // decode may write its context)
-int complete_lazy(const qi_plan* p, const void* d_ctx, long long cs, long long words, int S,
-                  hipStream_t s)
+int decode_rows(qi_plan* p, const void* d_ctx, const RowSrc& src, const uint32_t* d_counts,
+                const uint32_t* d_entries, int slots, int cap, int slot_base, const RowDst& out,
+                long long words, int S, hipStream_t s)
 {
-    if (words % kRouteTile != 0)
-        return 0;  // built with them
-    int32_t* c = static_cast<int32_t*>(const_cast<void*>(d_ctx));
+    const Oor marks{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), slots, cap};
+    const Oor* in = d_counts ? &marks : nullptr;
+    const long long cs = ctx_stride(p, words);
+    if (!use_matrix(p, words))
+        return ntt_decode(p, static_cast<const int32_t*>(d_ctx), cs, src, in, slot_base, out,
+                          words, S, s);
     const MatLayout L = ctx_layout(p);
-    if (p->mbig)
-        return ntt_build_ctx_lazy(
-            p, c + L.words(), S, c + mat_ctx_words(p, words), cs,
-            reinterpret_cast<uint32_t*>(c + L.words() + 2 * L.KP + lazy_word_off(words)), s);
-    return fill_dot2_sections(L, c, cs, words, S, s);
+    const MatCtxView v(L, d_ctx, cs, words);
+    // (a context with a column tail was built with every section)
+    if (!matrix_cores_take(src, out, L.R, words) && words % kRouteTile == 0) {
+        if (!p->mbig) {
+            if (int rc = fill_dot2_sections(L, v.ctx, cs, words, S, s))
+                return rc;
+        } else {
+            if (int rc = ntt_build_ctx_lazy(p, v.ids(), S, v.ctx + v.size(), cs, v.lazy(), s))
+                return rc;
+            return ntt_decode(p, v.ctx + v.size(), cs, src, in, slot_base, out, words, S, s);
+        }
+    }
+    return apply_ctx(p, L, v, src, out, words, S, in, slot_base, nullptr, s);
 }
 
 }  // namespace
@@ -75,16 +118,7 @@ long long ctx_stride(const qi_plan* p, long long words)
         return ntt_ctx_words(p);
     // 256 < k <= 384: the NTT engine's context follows the matrix one, for
     // rows the matrix cores cannot address (matrix_cores_take)
-    return mat_ctx_words(p, words) + (p->mbig ? ntt_ctx_words(p) : 0);
-}
-
-// the slow-tile lists of n contexts (behind each route table)
-SlowList ctx_slow(const qi_plan* p, const void* d_ctx, long long words)
-{
-    const MatLayout L = ctx_layout(p);
-    uint32_t* c = static_cast<uint32_t*>(const_cast<void*>(d_ctx));
-    return SlowList{c + L.words() + 2 * L.KP + route_tiles(words) * kRouteStride,
-                    ctx_stride(p, words)};
+    return mat_ctx_words(ctx_layout(p), words) + (p->mbig ? ntt_ctx_words(p) : 0);
 }
 
 // Decode contexts for n_stripes stripes, built on the device inside the
@@ -104,7 +138,7 @@ int build_ctx(qi_plan* p, const uint16_t* d_ids, int n_stripes, const Oor* in,
         return ntt_build_ctx(p, d_ids, n_stripes, static_cast<int32_t*>(d_ctx), cs, s);
     const MatLayout L = ctx_layout(p);
     // (256 < k <= 384: the NTT engine's half only when a decode needs it,
-    // complete_lazy)
+    // decode_rows)
     // the dot2 sections only for widths with a column tail (below 256 < k:
     // no dot2 kernel at all); a whole-tile decode that needs them after all
     // fills them from the tiles (qi_gpu_decode)
@@ -194,35 +228,10 @@ int qi_gpu_decode(qi_plan* p, const void* d_ctx, const uint16_t* d_ids,
         return -1;
     if (n_stripes == 0 || words == 0)
         return 0;
-    const MatLayout L = ctx_layout(p);
-    RowSrc src;
-    if (p->sys)
-        src = RowSrc{d_data ? d_data : d_coded, dss, drs, p->k, d_coded, css, crs, 0,
-                     p->k, p->n_outputs};
-    else
-        src = RowSrc{d_coded, css, crs, 1 << 30, nullptr, 0, 0, 0, p->n_outputs, 0};
-    Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries),
-           p->n_outputs, cap};
-    RowDst out{d_out, oss, ors};
-    const long long cs = ctx_stride(p, words);
-    const int32_t* ctx = static_cast<const int32_t*>(d_ctx);
-    (void)d_ids;  // the context carries the ids (as dwords)
-    if (!use_matrix(p, words))
-        return ntt_decode(p, ctx, cs, src, d_counts ? &in : nullptr, p->sys ? p->k : 0, out,
-                          words, n_stripes, st(stream));
-    if (!matrix_cores_take(src, out, L.R, words)) {
-        if (int rc = complete_lazy(p, d_ctx, cs, words, n_stripes, st(stream)))
-            return rc;
-        if (p->mbig)
-            return ntt_decode(p, ctx + mat_ctx_words(p, words), cs, src,
-                              d_counts ? &in : nullptr, p->sys ? p->k : 0, out, words,
-                              n_stripes, st(stream));
-    }
-    return launch_matrix(L, ctx, cs, ctx + L.words(), cs, src, out, words,
-                         n_stripes, d_counts ? &in : nullptr, p->sys ? p->k : 0,
-                         nullptr, p->d_rowid,
-                         reinterpret_cast<const uint32_t*>(ctx + L.words() + 2 * L.KP),
-                         cs, ctx_slow(p, d_ctx, words), p->d_err, st(stream));
+    // (the context carries the ids, as dwords)
+    return decode_rows(p, d_ctx, plan_src(p, d_data, dss, drs, d_coded, css, crs), d_counts,
+                       d_entries, p->n_outputs, cap, p->sys ? p->k : 0, RowDst{d_out, oss, ors},
+                       words, n_stripes, st(stream));
 }
 
 int qi_gpu_decode_ctx_packed(qi_plan* p, const uint16_t* d_ids,
@@ -249,52 +258,26 @@ int qi_gpu_decode_packed(qi_plan* p, const void* d_ctx, const uint16_t* d_recv,
         return -1;
     if (n_stripes == 0 || words == 0)
         return 0;
-    const MatLayout L = ctx_layout(p);
-    RowSrc src{d_recv, rss, rrs, 1 << 30, nullptr, 0, 0, 1, p->k, 0};
-    Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries),
-           p->k, cap};
-    RowDst out{d_out, oss, ors};
-    const long long cs = ctx_stride(p, words);
-    const int32_t* ctx = static_cast<const int32_t*>(d_ctx);
-    if (!use_matrix(p, words))
-        return ntt_decode(p, ctx, cs, src, d_counts ? &in : nullptr, 0, out, words,
-                          n_stripes, st(stream));
-    if (!matrix_cores_take(src, out, L.R, words)) {
-        if (int rc = complete_lazy(p, d_ctx, cs, words, n_stripes, st(stream)))
-            return rc;
-        if (p->mbig)
-            return ntt_decode(p, ctx + mat_ctx_words(p, words), cs, src,
-                              d_counts ? &in : nullptr, 0, out, words, n_stripes,
-                              st(stream));
-    }
-    return launch_matrix(L, ctx, cs, ctx + L.words(), cs, src, out, words,
-                         n_stripes, d_counts ? &in : nullptr, 0, nullptr, p->d_rowid,
-                         reinterpret_cast<const uint32_t*>(ctx + L.words() + 2 * L.KP),
-                         cs, ctx_slow(p, d_ctx, words), p->d_err, st(stream));
+    return decode_rows(p, d_ctx, RowSrc{d_recv, rss, rrs, 1 << 30, nullptr, 0, 0, 1, p->k, 0},
+                       d_counts, d_entries, p->k, cap, 0, RowDst{d_out, oss, ors}, words,
+                       n_stripes, st(stream));
 }
 
 // ---- fused repair (k <= 256): R x k Lagrange matrices applied by
 // launch_matrix with input marks (the received rows') and output marks (the
-// rebuilt rows') in one launch ----
+// rebuilt rows') in one launch; per stripe the packed R x k block, then the
+// sections of a matrix decode context ----
 static bool repair_ok(const qi_plan* p, int R)
 {
     return R >= 1 && R <= std::min(QI_REPAIR_MAX_TARGETS, p->code_len - p->k);
-}
-
-// per stripe: the packed R x k block, the ids, the route table, the
-// slow-tile list and the lazy word (as a matrix decode context)
-static long long repair_ctx_words(const qi_plan* p, int R, long long words)
-{
-    const MatLayout L{R, p->k, matrix_kp(p->k)};
-    return static_cast<long long>(L.words()) + 2 * L.KP + lazy_word_off(words) + kLazyWords;
 }
 
 size_t qi_gpu_repair_ctx_bytes(const qi_plan* p, int n_targets, int n_stripes, long long words)
 {
     if (!p || p->ntt || n_stripes < 0 || words < 0 || !repair_ok(p, n_targets))
         return 0;
-    return static_cast<size_t>(repair_ctx_words(p, n_targets, words)) * sizeof(int32_t) *
-           static_cast<size_t>(n_stripes);
+    return static_cast<size_t>(mat_ctx_words(repair_layout(p, n_targets), words)) *
+           sizeof(int32_t) * static_cast<size_t>(n_stripes);
 }
 
 int qi_gpu_repair_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_targets, int R,
@@ -311,12 +294,12 @@ int qi_gpu_repair_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_targe
         return 0;
     if (!d_ids || !d_targets)
         return -1;
-    const MatLayout L{R, p->k, matrix_kp(p->k)};
+    const MatLayout L = repair_layout(p, R);
     Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs, cap};
     return launch_repair_ctx(p->k, p->n, p->code_len, p->r, p->sys, L, d_ids, d_targets,
-                             n_stripes, static_cast<int32_t*>(d_ctx),
-                             repair_ctx_words(p, R, words), d_counts ? &in : nullptr,
-                             p->sys ? p->k : 0, words, p->d_err, st(stream));
+                             n_stripes, static_cast<int32_t*>(d_ctx), mat_ctx_words(L, words),
+                             d_counts ? &in : nullptr, p->sys ? p->k : 0, words, p->d_err,
+                             st(stream));
 }
 
 int qi_gpu_repair(qi_plan* p, const void* d_ctx, int R, const uint16_t* d_data, long long dss,
@@ -334,28 +317,14 @@ int qi_gpu_repair(qi_plan* p, const void* d_ctx, int R, const uint16_t* d_data, 
         return -1;
     if (n_stripes == 0 || words == 0)
         return 0;
-    const MatLayout L{R, p->k, matrix_kp(p->k)};
-    RowSrc src;
-    if (p->sys)
-        src = RowSrc{d_data ? d_data : d_coded, dss, drs, p->k, d_coded, css, crs, 0,
-                     p->k, p->n_outputs};
-    else
-        src = RowSrc{d_coded, css, crs, 1 << 30, nullptr, 0, 0, 0, p->n_outputs, 0};
+    const MatLayout L = repair_layout(p, R);
     Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries),
            p->n_outputs, in_cap};
-    Oor outm{d_out_counts, d_out_entries, R, out_cap};
-    RowDst out{d_out, oss, ors};
-    const long long cs = repair_ctx_words(p, R, words);
-    const int32_t* ctx = static_cast<const int32_t*>(d_ctx);
-    uint32_t* c = static_cast<uint32_t*>(const_cast<void*>(d_ctx));
-    const SlowList slow{c + L.words() + 2 * L.KP + route_tiles(words) * kRouteStride, cs};
-    // output slot j = target j: the identity row map (d_rowid holds at least
-    // QI_REPAIR_MAX_TARGETS entries)
-    return launch_matrix(L, ctx, cs, ctx + L.words(), cs, src, out, words, n_stripes,
-                         d_in_counts ? &in : nullptr, p->sys ? p->k : 0,
-                         d_out_counts ? &outm : nullptr, p->d_rowid,
-                         reinterpret_cast<const uint32_t*>(ctx + L.words() + 2 * L.KP), cs, slow,
-                         p->d_err, st(stream));
+    Oor outm{d_out_counts, d_out_entries, R, out_cap};  // output slot j = target j
+    return apply_ctx(p, L, MatCtxView(L, d_ctx, mat_ctx_words(L, words), words),
+                     plan_src(p, d_data, dss, drs, d_coded, css, crs), RowDst{d_out, oss, ors},
+                     words, n_stripes, d_in_counts ? &in : nullptr, p->sys ? p->k : 0,
+                     d_out_counts ? &outm : nullptr, st(stream));
 }
 
 const char* qi_gpu_repair_kernels(const qi_plan* p, int R, long long words)
@@ -363,9 +332,8 @@ const char* qi_gpu_repair_kernels(const qi_plan* p, int R, long long words)
     static thread_local std::string names;
     if (!p || p->ntt || words <= 0 || !repair_ok(p, R))
         return "";
-    const MatLayout L{R, p->k, matrix_kp(p->k)};
-    names = std::string("repair=repair_ctx_kernel<") + (p->k <= 64 && R <= 16 ? "64" : "256") +
-            "> + " + matrix_kernel_names(L, words, true, p->sys != 0, true);
+    names = "repair=" + repair_ctx_kernel_name(p->k, R) + " + " +
+            matrix_kernel_names(repair_layout(p, R), words, true, p->sys != 0, true);
     return names.c_str();
 }
 
@@ -385,12 +353,8 @@ const char* qi_gpu_kernels(const qi_plan* p, long long words)
             enc = encode_fnt_kernel_name(p->k);
         else
             enc = matrix_kernel_names(p->gen, words, false, false);
-        const MatLayout L = ctx_layout(p);
-        // launch_decode_ctx's choice (ctx.hip)
-        dec = std::string(p->k > 128  ? "decode_ctx_kernel<1024, true>"
-               : p->k > 32 ? "decode_ctx_lds_kernel<256>"
-                           : "decode_ctx_lds_kernel<128>") +
-              " + " + matrix_kernel_names(L, words, true, p->sys != 0);
+        dec = decode_ctx_kernel_name(p->k) + " + " +
+              matrix_kernel_names(ctx_layout(p), words, true, p->sys != 0);
     }
     names = "encode=" + enc + "; decode=" + dec;
     return names.c_str();

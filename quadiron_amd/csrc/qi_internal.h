@@ -6,18 +6,20 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
-#include "matrix_pack.h"  // MatLayout: the packed matrix block
+#include "matrix_pack.h"   // MatLayout: the packed matrix block
+#include "matrix_route.h"  // kRouteTile, matrix_kp, matrix_route
 
 namespace qi {
 
 // OOR routing: the decode context keeps, per stripe and per tile of
-// kRouteTile columns, the marks of the received rows that fall in the tile
-// (count + up to kRouteCap entries packed as position << 16 | column-in-tile).
-// A count above kRouteCap makes the decode kernel scan the OOR buckets.
-constexpr int kRouteTile = 1024;  // a multiple of every block width (256*COLS)
+// kRouteTile (matrix_route.h) columns, the marks of the received rows that
+// fall in the tile (count + up to kRouteCap entries packed as position << 16
+// | column-in-tile).  A count above kRouteCap makes the decode kernel scan
+// the OOR buckets.
 constexpr int kRouteCap = 15;
 constexpr int kRouteStride = kRouteCap + 1;
 
@@ -99,6 +101,76 @@ __host__ __device__ inline long long lazy_word_off(long long words)
 // words reserved for it (keeps the following section's alignment)
 constexpr int kLazyWords = 4;
 
+// The sections of a matrix context (decode or repair) behind its packed block
+// L, for `words` columns, stripes `stride` words apart: the ids as dwords
+// (padded to 2 KP), the route table, the slow-tile list, the lazy word.  The
+// context builders' kernels write them at these offsets (ctx.hip).
+struct MatCtxView {
+    int32_t* ctx;
+    long long stride;
+    long long ids_off, route_off, slow_off, lazy_off;
+    MatCtxView(const MatLayout& L, const void* d_ctx, long long stride_, long long words)
+        : ctx(static_cast<int32_t*>(const_cast<void*>(d_ctx))), stride(stride_),
+          ids_off(static_cast<long long>(L.words())), route_off(ids_off + 2 * L.KP),
+          slow_off(route_off + route_tiles(words) * kRouteStride),
+          lazy_off(route_off + lazy_word_off(words))
+    {
+    }
+    // words of a stripe's matrix-format context
+    long long size() const { return lazy_off + kLazyWords; }
+    const int32_t* ids() const { return ctx + ids_off; }
+    const uint32_t* route() const { return reinterpret_cast<const uint32_t*>(ctx + route_off); }
+    SlowList slow() const { return {reinterpret_cast<uint32_t*>(ctx + slow_off), stride}; }
+    uint32_t* lazy() const { return reinterpret_cast<uint32_t*>(ctx + lazy_off); }
+};
+
+// Once-per-device setup of a kernel (dynamic-LDS opt-in, cached device
+// facts).  `done` is the kernel's own bit per device index below
+// kOnceDevices: setup(dev) runs until it has succeeded once on the current
+// device (a race only repeats the idempotent calls), and on every call for
+// an index of kOnceDevices or above, where nothing can be cached.  Returns
+// the device index, or -2 when the device query or the setup fails (the bit
+// stays unset).
+constexpr int kOnceDevices = 64;
+template <class F>
+int once_per_device(std::atomic<uint64_t>& done, F&& setup)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        return -2;
+    const uint64_t bit = dev < kOnceDevices ? 1ull << dev : 0;
+    if (!bit || !(done.load(std::memory_order_acquire) & bit)) {
+        if (!setup(dev))
+            return -2;
+        done.fetch_or(bit, std::memory_order_release);
+    }
+    return dev;
+}
+
+// The context builders' kernel by shape, as their block size: launch_decode_ctx
+// runs decode_ctx_kernel<1024, true> (the matrix rows in the context itself)
+// above k = 128, else decode_ctx_lds_kernel<256 or 128> (2 waves at k <= 32:
+// wave 1 routes the marks while wave 0 builds A(x)); launch_repair_ctx runs
+// repair_ctx_kernel<64> for at most 16 x 68 words of rows, else <256>.
+inline int decode_ctx_threads(int k)
+{
+    return k > 128 ? 1024 : k > 32 ? 256 : 128;
+}
+inline int repair_ctx_threads(int k, int R)
+{
+    return k <= 64 && R <= 16 ? 64 : 256;
+}
+inline std::string decode_ctx_kernel_name(int k)
+{
+    const int t = decode_ctx_threads(k);
+    return t == 1024 ? "decode_ctx_kernel<1024, true>"
+                     : "decode_ctx_lds_kernel<" + std::to_string(t) + ">";
+}
+inline std::string repair_ctx_kernel_name(int k, int R)
+{
+    return "repair_ctx_kernel<" + std::to_string(repair_ctx_threads(k, R)) + ">";
+}
+
 // ---- launchers (kernels.hip) ----
 // non-systematic encode by twisted register-resident sub-NTTs
 int launch_encode_fnt(int k, int n, int n_out, const int32_t* d_twist,
@@ -159,14 +231,13 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
 int fill_dot2_sections(const MatLayout& L, int32_t* d_ctx, long long ctx_stride, long long words,
                        int n_stripes, hipStream_t stream);
 
-// matrix kernel instantiation choice
-int matrix_kp(int kin);
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.
 bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long words);
-// names of the kernels launch_matrix runs for L over `words` columns
-// (aligned rows; diagnostics: qi_gpu_kernels); two: rows from two source
+// names of the kernels launch_matrix runs for L over `words` columns: the
+// same matrix_route launch_matrix dispatches on, printed (aligned rows in
+// buffer range; diagnostics: qi_gpu_kernels); two: rows from two source
 // regions (the systematic decode)
 std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
                                 bool both = false);

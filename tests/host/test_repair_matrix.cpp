@@ -37,7 +37,7 @@ int main(int argc, char** argv)
             std::printf(" %u", M[static_cast<size_t>(j) * k + i]);
         std::printf("\n");
     }
-    // the packing of a repair context: KP as matrix_kp(k) (kernels.hip)
+    // the packing of a repair context: KP as matrix_kp(k) (matrix_route.h)
     int kp = 2;
     while (2 * kp < k)
         kp *= 2;

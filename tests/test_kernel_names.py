@@ -25,6 +25,23 @@ def _names(kernels):
             yield role, n.replace(" (tail)", "").strip()
 
 
+@pytest.mark.parametrize("k,m,sys_,R,P", [
+    (16, 48, False, 1, 1024), (16, 48, True, 17, 2088), (64, 960, False, 17, 1024),
+    (128, 128, True, 16, 200), (256, 768, False, 64, 2088),
+])
+def test_reported_repair_kernels_exist(k, m, sys_, R, P):
+    import quadiron_amd as qa
+    plan = qa.Plan(k, m, sys_)
+    syms = _kernel_symbols(qa.LIB_PATH)
+    kernels = plan.repair_kernels(R, P)
+    names = list(_names(kernels))
+    assert len(names) >= 2 and all(role == "repair" for role, _ in names), kernels
+    assert names[0][1].startswith("repair_ctx_kernel<"), kernels
+    for _, name in names:
+        pre = "qi::" + name + ("(" if name.endswith(">") else "")
+        assert any(pre in s for s in syms), (name, kernels)
+
+
 @pytest.mark.parametrize("cfg,sys_", [
     ("cfg2", False), ("cfg2", True), ("cfg3", False), ("cfg1", False),
     ("k32", False), ("k128", False), ("k200", False), ("k256", False),
