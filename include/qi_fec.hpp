@@ -95,6 +95,13 @@ class DecodeContext {
     size_t size_;
 };
 
+// What RsFnt::verify_blocks_vertical reports per fragment: the columns whose
+// stored word / OOR mark differ from the recomputed symbol and the smallest
+// such column (0xFFFFFFFF: none); all -1 for a fragment that was not checked
+struct VerifyResult {
+    long long value_mismatch, mark_mismatch, first;
+};
+
 class RsFnt {
   public:
     // throws std::invalid_argument (bad parameters / word_size != 2) or
@@ -150,6 +157,25 @@ class RsFnt {
     // fits the single-chunk device staging with every fragment row of the
     // code in its own slot (at most 256 MiB of rows)
     bool repair_supported(size_t n_targets, size_t block_size_bytes) const;
+
+    // Fused verify (scrubbing): check the present fragments against each
+    // other on the device without rebuilding a row (qi_gpu_verify).  The
+    // basis is the first n_data present fragments, chosen as
+    // decode_blocks_vertical chooses them; every other present fragment is
+    // recomputed from the basis and compared with its buffer and its marks
+    // (more than 64 of them: in groups of at most 64 over the same staged
+    // rows).  result gets one entry per fragment id (code_len): {-1, -1, -1}
+    // for a missing or a basis fragment, otherwise the number of columns
+    // whose stored word differs, the number whose OOR mark differs, and the
+    // smallest such column (0xFFFFFFFF: none).  A corrupt basis fragment
+    // shows in every checked fragment at its column.  Returns false with
+    // fewer than n_data + 1 fragments present.  Throws std::invalid_argument
+    // where repair_supported(1, block_size_bytes) is false.
+    bool verify_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                std::vector<uint8_t*>& parities_bufs,
+                                std::vector<Properties>& parities_props,
+                                std::vector<int>& missing_idxs,
+                                std::vector<VerifyResult>& result, size_t block_size_bytes);
 
     void encode_streams_vertical(
         const std::vector<std::istream*>& input_data_bufs,

@@ -230,6 +230,62 @@ int qi_gpu_repair(qi_plan* plan, const void* d_ctx, int n_targets,
  * unsupported.  Per calling thread, valid until its next call. */
 const char* qi_gpu_repair_kernels(const qi_plan* plan, int n_targets, long long words);
 
+/* ---- Fused fragment verify (scrubbing): check stored fragments against
+ * each other on the device, in one pass and without writing a row.  Take k
+ * *basis* fragments and n_checks *check* fragments of a stripe, all present
+ * and distinct.  Each check fragment j is recomputed from the basis rows
+ * (their OOR marks restored) exactly as qi_gpu_repair would rebuild it, and
+ * compared with the stored row j and that row's OOR bucket where it is
+ * computed: a repair into scratch rows followed by a compare writes n_checks
+ * rows and reads 2 n_checks rows that this call never touches.
+ *
+ * The context IS a repair context with targets = the check ids: build it
+ * with qi_gpu_repair_ctx(plan, d_basis_ids, d_checks, n_checks, ...), sized
+ * by qi_gpu_repair_ctx_bytes, with the same limits (k <= 256, 1 <= n_checks
+ * <= min(64, m), ids below k + m; a check id that is also a basis id raises
+ * bit 2 of qi_gpu_take_error).  d_checks is the [S][n_checks] u16 array given
+ * to that call.  Basis rows AND check rows are addressed by fragment id as
+ * qi_gpu_decode addresses received rows (d_data / d_coded), their buckets by
+ * the same slot.
+ *
+ * At column c the canonical recomputed value is v in [0, 65536]:
+ *   value mismatch: (v & 0xffff) != stored[c]
+ *   mark mismatch:  (v == 65536) != (c is in the stored row's bucket); a
+ *                   systematic data row has no bucket, so any v == 65536
+ *                   there is one (as is every one when d_oor_counts is NULL).
+ * Per (stripe s, check j), at index s * n_checks + j, the call writes
+ *   d_value_mismatch: the number of value mismatches,
+ *   d_mark_mismatch:  the number of mark mismatches,
+ *   d_first:          the smallest column with either kind, or 0xFFFFFFFF.
+ * It initialises all three itself.  A corrupt *basis* fragment shows up as a
+ * mismatch in every check row at that column (each recomputed symbol depends
+ * on every basis symbol of its column); telling which fragment of a stripe
+ * is the corrupt one is the caller's business (e.g. by checking again with
+ * another basis).
+ *
+ * d_work: qi_gpu_verify_work_bytes bytes of scratch for the recomputed rows'
+ * 65536 positions, work_cap per (stripe, check) -- about words / 65537 are
+ * expected; it holds no rows (its size does not depend on the width).  More
+ * recomputed 65536 values than work_cap, or a stored bucket over oor_cap,
+ * raise bit 1 of qi_gpu_take_error (the mark counts are then lower bounds).
+ * Returns QI_ERR_UNSUPPORTED for k > 256 (qi_gpu_verify_work_bytes: 0), -1
+ * for n_checks out of range (nothing is launched). */
+size_t qi_gpu_verify_work_bytes(const qi_plan* plan, int n_checks, int n_stripes,
+                                int work_cap);
+int qi_gpu_verify(qi_plan* plan, const void* d_ctx, int n_checks,
+                  const uint16_t* d_checks /*[S][R], as given to repair_ctx*/,
+                  const uint16_t* d_data, long long dss, long long drs,
+                  const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_oor_counts, const uint32_t* d_oor_entries,
+                  int oor_cap, void* d_work, int work_cap,
+                  uint32_t* d_value_mismatch, uint32_t* d_mark_mismatch,
+                  uint32_t* d_first, long long words, int n_stripes, void* stream);
+/* Names of the kernels such a check launches (rows at 8-byte aligned
+ * offsets), as "verify=<kernels>": the repair's, in their _verify forms, and
+ * the bucket comparison; "" when unsupported.  Per calling thread, valid
+ * until its next call. */
+const char* qi_gpu_verify_kernels(const qi_plan* plan, int n_checks, long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -267,6 +323,20 @@ int qi_fec_repair_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
                          uint32_t oor_cap, const int* missing, const int* targets,
                          int n_targets, uint8_t** out, uint32_t* out_oor,
                          uint32_t* out_count, uint32_t out_cap, size_t block_bytes);
+
+/* Fused verify of the present fragments (RsFnt::verify_blocks_vertical,
+ * include/qi_fec.hpp): the first k present fragments are the basis, every
+ * other present one is recomputed from them and compared with its buffer and
+ * its marks.  result: 3 * (k + m) values, per fragment id {value mismatches,
+ * mark mismatches, first mismatching column or 0xFFFFFFFF}, or {-1, -1, -1}
+ * for a missing or a basis fragment.  `data` may be NULL for non-systematic
+ * codes, oor_count NULL when no row has marks.  Returns 1 verified, 0 fewer
+ * than k + 1 fragments present, -1 error, -2 shape not supported (k > 256 or
+ * a block wider than the single-chunk staging). */
+int qi_fec_verify_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
+                         const uint32_t* oor, const uint32_t* oor_count,
+                         uint32_t oor_cap, const int* missing, long long* result,
+                         size_t block_bytes);
 
 /* Stream API (encode_streams_vertical / decode_streams_vertical,
  * src/fec_base.h:463-542, 898-1048) over caller memory: each fragment is a

@@ -60,6 +60,10 @@ def _declare(lib):
         "qi_gpu_repair": (I, [V, V, I, V, LL, LL, V, LL, LL, V, V, I, V, LL,
                               LL, V, V, I, LL, I, V]),
         "qi_gpu_repair_kernels": (C.c_char_p, [V, I, LL]),
+        "qi_gpu_verify_work_bytes": (SZ, [V, I, I, I]),
+        "qi_gpu_verify": (I, [V, V, I, V, V, LL, LL, V, LL, LL, V, V, I, V, I,
+                              V, V, V, LL, I, V]),
+        "qi_gpu_verify_kernels": (C.c_char_p, [V, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -70,6 +74,7 @@ def _declare(lib):
         "qi_fec_decode_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
         "qi_fec_repair_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, c_u8pp, V,
                                      V, U32, SZ]),
+        "qi_fec_verify_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
                                       c_u8pp]),
@@ -380,6 +385,65 @@ class Plan:
             raise RuntimeError(f"qi_gpu_repair failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    def verify_kernels(self, n_checks, words):
+        """'verify=<kernels>' a check of n_checks fragments launches over
+        `words` columns (qi_gpu_verify_kernels); '' when unsupported."""
+        return lib().qi_gpu_verify_kernels(self.h, n_checks, words).decode()
+
+    def verify_work_bytes(self, n_checks, n_stripes, work_cap):
+        """Scratch for the recomputed rows' 65536 positions (no rows: no
+        width); 0 when the plan (k > 256) or n_checks is not supported."""
+        return lib().qi_gpu_verify_work_bytes(self.h, n_checks, n_stripes,
+                                              work_cap)
+
+    def verify(self, ctx, checks, coded, work, work_cap, value_mismatch,
+               mark_mismatch, first, data=None, counts=None, entries=None,
+               cap=0, stream=None, check=True):
+        """Fused check (qi_gpu_verify).  ctx: a repair context built by
+        repair_ctx(basis ids, checks, ...); checks: int16 tensor [S, R], the
+        same as given there; coded: [S, n_out, P] (fragment slot rows, with
+        their OOR buckets counts / entries), data: [S, k, P] for systematic
+        codes; work: uint8 scratch of verify_work_bytes(R, S, work_cap).
+        value_mismatch, mark_mismatch, first: int32 tensors of S * R
+        elements, written (and initialised) by the call.  Returns the sticky
+        error flags when check."""
+        import torch
+        if checks.dim() != 2:
+            raise ValueError("checks: expected [S, R]")
+        S, R = checks.shape
+        _rows(coded, "coded", self.n_outputs, S)
+        P = coded.shape[2]
+        if data is not None:
+            _rows(data, "data", self.k, S)
+            if data.shape[2] != P:
+                raise ValueError("data and coded differ in width")
+        need = self.repair_ctx_bytes(R, S, P)
+        if need == 0 and S > 0:
+            raise ValueError(f"check of {R} fragments is not supported on "
+                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        _flat(checks, "checks", S * R, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _flat(work, "work", self.verify_work_bytes(R, S, work_cap), (torch.uint8,))
+        for t, name in ((value_mismatch, "value_mismatch"),
+                        (mark_mismatch, "mark_mismatch"), (first, "first")):
+            if t is None:
+                raise ValueError(f"{name} is required")
+            _flat(t, name, S * R, (torch.int32, torch.uint32))
+        _oor(counts, entries, cap, S, self.n_outputs)
+        d = data if data is not None else coded
+        rc = lib().qi_gpu_verify(
+            self.h, ctx.data_ptr(), R, checks.data_ptr(), d.data_ptr(),
+            d.stride(0), d.stride(1), coded.data_ptr(), coded.stride(0),
+            coded.stride(1),
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            work.data_ptr(), int(work_cap), value_mismatch.data_ptr(),
+            mark_mismatch.data_ptr(), first.data_ptr(), P, S,
+            self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_verify failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -429,6 +493,34 @@ class Fec:
         if rc < 0:
             raise RuntimeError(f"qi_fec_repair_blocks failed: {rc}")
         return (outs, o_oor, o_cnt) if rc == 1 else None
+
+    def verify_blocks(self, data, parities, oor, counts, missing):
+        """Check the present fragments against each other in one pass on the
+        device (qi_fec_verify_blocks): the first k present ones are the
+        basis, every other present one is recomputed and compared with its
+        row and its marks.  Arguments as repair_blocks.  Returns an int64
+        array (k + m, 3): per fragment id [value mismatches, mark
+        mismatches, first mismatching column or 0xFFFFFFFF], or [-1, -1, -1]
+        for a missing or a basis fragment; None when fewer than k + 1
+        fragments are present.  Raises ValueError for an unsupported shape
+        (k > 256, a block wider than one staging chunk)."""
+        import numpy as np
+        rows = [r for r in list(data or []) + list(parities) if r is not None]
+        B = len(rows[0])
+        miss = np.ascontiguousarray(missing, np.int32)
+        oor = np.ascontiguousarray(oor, np.uint32)
+        counts = np.ascontiguousarray(counts, np.uint32)
+        res = np.full((self.k + self.m, 3), -1, np.int64)
+        rc = lib().qi_fec_verify_blocks(
+            self.h, ptr_array(list(data)) if data is not None else None,
+            ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p), oor.shape[1],
+            miss.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p), B)
+        if rc == -2:
+            raise ValueError("verify_blocks: shape not supported")
+        if rc < 0:
+            raise RuntimeError(f"qi_fec_verify_blocks failed: {rc}")
+        return res if rc == 1 else None
 
     def close(self):
         if self.h:

@@ -571,6 +571,139 @@ bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     return true;
 }
 
+// ---- fused verify (single chunk; qi_gpu_repair_ctx / qi_gpu_verify) ----
+bool RsFnt::verify_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                   std::vector<uint8_t*>& parities_bufs,
+                                   std::vector<Properties>& parities_props,
+                                   std::vector<int>& missing_idxs,
+                                   std::vector<VerifyResult>& result, size_t block_size_bytes)
+{
+    const bool sys = type == FecType::SYSTEMATIC;
+    // (the staging of a repair; the group size is checked per group)
+    if (!repair_supported(1, block_size_bytes))
+        throw std::invalid_argument("RsFnt::verify_blocks_vertical: unsupported shape");
+    std::vector<int> present(code_len);
+    for (unsigned i = 0; i < code_len; i++)
+        present[i] = missing_idxs[i] ? 0 : 1;
+    result.assign(code_len, VerifyResult{-1, -1, -1});
+    std::vector<int> ids;
+    if (!select_fragments(present, ids))
+        return false;
+    const int k = static_cast<int>(n_data);
+    std::vector<char> basis(code_len, 0);
+    for (int id : ids)
+        basis[id] = 1;
+    std::vector<int> checks;
+    for (unsigned f = 0; f < code_len; f++)
+        if (present[f] && !basis[f])
+            checks.push_back(static_cast<int>(f));
+    if (checks.empty())
+        return false;  // fewer than n_data + 1 fragments: nothing to check against
+    for (auto& p : parities_props)
+        p.sort();
+    const size_t words = block_size_bytes / word_size;
+    const size_t P = pad_words(words);
+    const size_t no = n_outputs;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // every present fragment in its own slot (data rows first when
+    // systematic), the coded rows' OOR buckets by slot
+    const size_t data_rows = sys ? n_data : 0;
+    std::vector<std::vector<uint32_t>> marks(no);
+    size_t cap = 1;
+    for (unsigned f = 0; f < code_len; f++) {
+        if (!present[f] || (sys && f < n_data))
+            continue;
+        const size_t slot = sys ? f - n_data : f;
+        for (auto const& it : parities_props[slot].get_map())
+            if (it.first < words)
+                marks[slot].push_back(static_cast<uint32_t>(it.first));
+        cap = std::max(cap, marks[slot].size());
+    }
+    std::vector<uint32_t> hcnt(no, 0), hent(no * cap, 0);
+    for (size_t i = 0; i < no; i++) {
+        hcnt[i] = static_cast<uint32_t>(marks[i].size());
+        std::copy(marks[i].begin(), marks[i].end(), hent.begin() + i * cap);
+    }
+    const size_t Rmax = std::min<size_t>({size_t{64}, checks.size(), code_len - n_data});
+    const size_t ctx_bytes = qi_gpu_repair_ctx_bytes(pl, static_cast<int>(Rmax), 1,
+                                                     static_cast<long long>(words));
+    if (ctx_bytes == 0)
+        throw std::invalid_argument("RsFnt::verify_blocks_vertical: unsupported shape");
+    size_t wcap = 64 + words / 512;
+    // counts buffer: input counts, input entries, the three results
+    const size_t ent_off = 64 * ((no * 4 + 63) / 64);
+    const size_t res_off = ent_off + 64 * ((hent.size() * 4 + 63) / 64);
+    if (!h.in.reserve((data_rows + no) * P * 2) || !h.counts.reserve(res_off + 3 * Rmax * 4) ||
+        !h.ids.reserve((k + Rmax) * 2) || !h.ctx.reserve(ctx_bytes))
+        throw std::runtime_error("RsFnt: device allocation failed");
+    uint16_t* din = static_cast<uint16_t*>(h.in.p);
+    uint16_t* dcoded = din + data_rows * P;
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + ent_off);
+    uint32_t* dres = reinterpret_cast<uint32_t*>(dcb + res_off);
+    for (unsigned f = 0; f < code_len; f++) {
+        if (!present[f])
+            continue;
+        const bool d = sys && f < n_data;
+        const uint8_t* src = d ? data_bufs[f] : parities_bufs[sys ? f - n_data : f];
+        uint16_t* dst = d ? din + f * P : dcoded + (sys ? f - n_data : f) * P;
+        check(hipMemcpyAsync(dst, src, words * 2, hipMemcpyHostToDevice, s), "H2D");
+    }
+    check(hipMemcpyAsync(dcnt, hcnt.data(), no * 4, hipMemcpyHostToDevice, s), "H2D");
+    check(hipMemcpyAsync(dent, hent.data(), hent.size() * 4, hipMemcpyHostToDevice, s), "H2D");
+    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
+    std::vector<uint16_t> hids(k + Rmax);
+    for (int i = 0; i < k; i++)
+        hids[i] = static_cast<uint16_t>(ids[i]);
+    std::vector<uint32_t> res(3 * Rmax);
+    // groups of at most 64 checks over the same staged rows
+    for (size_t g0 = 0; g0 < checks.size(); g0 += Rmax) {
+        const size_t R = std::min(Rmax, checks.size() - g0);
+        for (size_t j = 0; j < R; j++)
+            hids[k + j] = static_cast<uint16_t>(checks[g0 + j]);
+        // (the previous group's kernels read the ids: ordered on the stream,
+        // and the host copy is synchronous with respect to hids below)
+        check(hipMemcpyAsync(h.ids.p, hids.data(), (k + R) * 2, hipMemcpyHostToDevice, s), "H2D");
+        check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, dcnt, dent,
+                                   static_cast<int>(cap), static_cast<long long>(words), h.ctx.p,
+                                   s),
+                 "verify context");
+        for (int attempt = 0; attempt < 2; attempt++) {
+            const size_t wb = qi_gpu_verify_work_bytes(pl, static_cast<int>(R), 1,
+                                                       static_cast<int>(wcap));
+            if (!wb || !h.entries.reserve(wb))
+                throw std::runtime_error("RsFnt: device allocation failed");
+            check_rc(qi_gpu_verify(pl, h.ctx.p, static_cast<int>(R), dids + k, din, 0,
+                                   static_cast<long long>(P), dcoded, 0,
+                                   static_cast<long long>(P), dcnt, dent, static_cast<int>(cap),
+                                   h.entries.p, static_cast<int>(wcap), dres, dres + R,
+                                   dres + 2 * R, static_cast<long long>(words), 1, s),
+                     "verify");
+            check(hipMemcpyAsync(res.data(), dres, 3 * R * 4, hipMemcpyDeviceToHost, s), "D2H");
+            std::vector<uint32_t> wc(R);
+            check(hipMemcpyAsync(wc.data(), h.entries.p, R * 4, hipMemcpyDeviceToHost, s), "D2H");
+            check(hipStreamSynchronize(s), "sync");
+            const uint32_t mx = *std::max_element(wc.begin(), wc.end());
+            if (mx <= wcap)
+                break;
+            // adversarial data: more recomputed 65536 values than the work
+            // buckets hold; run again with the exact capacity
+            (void)qi_gpu_take_error(pl);
+            wcap = mx;
+        }
+        if (qi_gpu_take_error(pl))
+            throw std::runtime_error("RsFnt: verify failed (bad ids or OOR bucket capacity)");
+        for (size_t j = 0; j < R; j++)
+            result[checks[g0 + j]] = VerifyResult{static_cast<long long>(res[j]),
+                                                  static_cast<long long>(res[R + j]),
+                                                  static_cast<long long>(res[2 * R + j])};
+    }
+    return true;
+}
+
 namespace {
 
 // One stage of the pipelined stream API: pinned host staging, device
@@ -1471,6 +1604,40 @@ int qi_fec_repair_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const ui
             out_count[j] = c;
         }
         return 1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_verify_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const uint32_t* oor,
+                         const uint32_t* oor_count, uint32_t cap, const int* missing,
+                         long long* result, size_t block_bytes)
+{
+    try {
+        if (!h || !parities || !missing || !result)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.repair_supported(1, block_bytes))
+            return -2;
+        std::vector<uint8_t*> dv(f.n_data, nullptr);
+        if (data)
+            dv.assign(data, data + f.n_data);
+        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
+        std::vector<qi::Properties> props(f.n_outputs);
+        for (unsigned i = 0; i < f.n_outputs; i++) {
+            const uint32_t c = !oor_count ? 0 : oor_count[i] < cap ? oor_count[i] : cap;
+            for (uint32_t e = 0; e < c; e++)
+                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
+        }
+        std::vector<int> miss(missing, missing + f.code_len);
+        std::vector<qi::fec::VerifyResult> res;
+        const bool ok = f.verify_blocks_vertical(dv, pv, props, miss, res, block_bytes);
+        for (unsigned i = 0; i < f.code_len; i++) {
+            result[3 * i] = res[i].value_mismatch;
+            result[3 * i + 1] = res[i].mark_mismatch;
+            result[3 * i + 2] = res[i].first;
+        }
+        return ok ? 1 : 0;
     } catch (...) {
         return -1;
     }

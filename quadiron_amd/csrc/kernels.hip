@@ -540,6 +540,35 @@ struct MatArgs {
     uint32_t* err;
 };
 
+// The forms a matrix kernel's body file is compiled in (MODE, a constexpr
+// set by the including kernel): plain; input and output marks in one launch
+// (a repair); and the verify form of a fused check, which is the repair with
+// the row store replaced by a load of the stored row and a compare.
+enum class MatMode { kPlain, kBoth, kVerify };
+
+// What the verify forms add to a launch (the other forms get an empty one):
+// chk[s * R + t] is the fragment id of matrix row t, whose stored row lies in
+// the launch's source regions; value mismatches are counted in vmis[s * R +
+// t] and the smallest mismatching column goes to first[s * R + t].  The
+// recomputed rows' 65536 positions go to the launch's output buckets.
+struct VerArgs {
+    const uint16_t* chk = nullptr;
+    uint32_t* vmis = nullptr;
+    uint32_t* first = nullptr;
+};
+
+// One row's mismatches of a wave into its counters, by one lane: `mis` is
+// this lane's column (lane order = column order), col its column
+__device__ __forceinline__ void verify_report_lanes(const VerArgs& v, long long idx, bool mis,
+                                                    uint32_t col)
+{
+    const uint64_t m = __builtin_amdgcn_ballot_w64(mis);
+    if (mis && static_cast<int>(threadIdx.x & 63) == __builtin_ctzll(m)) {
+        atomicAdd(v.vmis + idx, static_cast<uint32_t>(__builtin_popcountll(m)));
+        atomicMin(v.first + idx, col);
+    }
+}
+
 // Where the OOR marks of the received rows (decode_prepare's restore of
 // 65536, src/fec_base.h:1361-1404) come from in a matrix launch.  A tile
 // normally takes them from the context's route table or from one scan of
@@ -602,11 +631,14 @@ constexpr int kRedoCols = 64;
 // recomputed: a block of matrix_os_kernel redoes just the rows it stored
 // itself (G row-block groups share a column range), so no two blocks write
 // the same outputs; other callers pass gq = 0, G = 1 (every row).
-template <int NT, bool BOTH = false>
+// The verify form compares instead of storing: the stored row of matrix row
+// t is fragment v.chk[s * R + t], in the source regions.
+template <int NT, MatMode MODE = MatMode::kPlain>
 __device__ void redo_columns(const MatArgs& a, int s, long long t0c, long long t1c,
                              uint16_t* xs, uint32_t* mk, uint32_t* colmk, int gq = 0,
-                             int G = 1)
+                             int G = 1, const VerArgs& v = VerArgs{})
 {
+    constexpr bool BOTH = MODE != MatMode::kPlain, VERIFY = MODE == MatMode::kVerify;
     const MatLayout L = a.L;
     const int kin = L.kin;
     const RowSrc& src = a.src;
@@ -671,8 +703,19 @@ __device__ void redo_columns(const MatArgs& a, int s, long long t0c, long long t
                     y = static_cast<uint32_t>(static_cast<uint64_t>(y) *
                                               static_cast<uint32_t>(rs < 0 ? rs + kQ : rs) %
                                               65537u);
-                dst.base[s * dst.ss + a.rowmap[t] * dst.rs + c0 + c] =
-                    static_cast<uint16_t>(y == 65536u ? 0u : y);
+                if constexpr (VERIFY) {
+                    const int id = min(static_cast<int>(v.chk[static_cast<long long>(s) * L.R + t]),
+                                       src.rows0 + src.rows1 - 1);
+                    const uint16_t* row =
+                        id < src.split ? src.base0 + s * src.ss0 + id * src.rs0
+                                       : src.base1 + s * src.ss1 + (id - src.split) * src.rs1;
+                    verify_report_lanes(v, static_cast<long long>(s) * L.R + t,
+                                        (y == 65536u ? 0u : y) != row[c0 + c],
+                                        static_cast<uint32_t>(c0 + c));
+                } else {
+                    dst.base[s * dst.ss + a.rowmap[t] * dst.rs + c0 + c] =
+                        static_cast<uint16_t>(y == 65536u ? 0u : y);
+                }
                 if constexpr (BOTH)
                     if (y == 65536u)
                         record_oor(a.out_oor, s, a.rowmap[t], c0 + c);
@@ -701,13 +744,22 @@ constexpr int kRedoSpan = 64;
 
 __global__ __launch_bounds__(kBlock) void matrix_redo_kernel(MatArgs a, int n_stripes)
 {
-    constexpr bool BOTH = false;
+    constexpr MatMode MODE = MatMode::kPlain;
+    constexpr VerArgs v{};
 #include "matrix_redo_body.h"
 }
 // input and output marks in one launch (a repair)
 __global__ __launch_bounds__(kBlock) void matrix_redo_kernel_both(MatArgs a, int n_stripes)
 {
-    constexpr bool BOTH = true;
+    constexpr MatMode MODE = MatMode::kBoth;
+    constexpr VerArgs v{};
+#include "matrix_redo_body.h"
+}
+// a fused check: the slow tiles compared with the stored rows, counted once
+__global__ __launch_bounds__(kBlock) void matrix_redo_kernel_verify(MatArgs a, int n_stripes,
+                                                                    VerArgs v)
+{
+    constexpr MatMode MODE = MatMode::kVerify;
 #include "matrix_redo_body.h"
 }
 
@@ -938,6 +990,135 @@ __device__ __forceinline__ void matrix_compute(
 }
 
 
+// The stored rows a verify form compares with: the launch's source regions
+// and its VerArgs; skip: a slow tile (counted once, by its redo)
+template <bool BUF>
+struct VerRows {
+    const VerArgs& v;
+    const RowSrc& src;
+    const Region<BUF>& g0;
+    const Region<BUF>& g1;
+    bool skip;
+};
+
+// matrix_compute in its verify form: the same product, marks and row scale,
+// with the row store replaced by a load of the stored row and a compare (a
+// copy, not a flag of matrix_compute: the existing forms keep their text and
+// their registers)
+template <int KP, int COLS, bool FULL, bool BUF>
+__device__ __forceinline__ void matrix_compute_verify(
+    const MatLayout& L, const int32_t* __restrict__ M,
+    const int32_t (&xp)[COLS][KP], const Region<BUF>& go, uint32_t ors,
+    uint32_t voff, long long col, long long col0, long long avail, int s,
+    int n_lm, const int* s_i, const uint32_t* s_col, const Oor& out_oor,
+    const int32_t* __restrict__ rowmap, const VerRows<BUF>* vr)
+{
+    // M: the per-stripe matrix block (wave-uniform: scalar loads)
+    const int kin = L.kin;
+    const int32_t* kcorr = M + L.kcorr();
+    const int32_t* rscale = M + L.rscale();
+    const int32_t* plain = M + L.plain();
+    const bool rec = out_oor.counts != nullptr;
+    for (int t = 0; t < L.R; t++) {
+        const int32_t* mrow = M + t * KP;
+        // the stored row of check t (wave-uniform id), loaded ahead of
+        // the products
+        int32_t sv[COLS];
+        {
+            const int id = min(static_cast<int>(vr->v.chk[static_cast<long long>(s) * L.R + t]),
+                               vr->src.rows0 + vr->src.rows1 - 1);
+            const bool lo = id < vr->src.split;
+            Region<BUF> g = vr->g0;
+            if constexpr (BUF)
+                g.r = lo ? vr->g0.r : vr->g1.r;
+            g.p = lo ? vr->g0.p : vr->g1.p;
+            const uint32_t off = static_cast<uint32_t>(
+                lo ? id * vr->src.rs0 * 2 : (id - vr->src.split) * vr->src.rs1 * 2);
+            ld<COLS, FULL, BUF, kAuxLd>(g, off, voff, avail, sv);
+        }
+        int32_t acc[COLS];
+#pragma unroll
+        for (int c = 0; c < COLS; c++)
+            acc[c] = kcorr[t];
+#pragma unroll
+        for (int j = 0; j < KP; j++) {
+            const qi_short2 m2 = __builtin_bit_cast(qi_short2, mrow[j]);
+#pragma unroll
+            for (int c = 0; c < COLS; c++)
+                acc[c] = fold(__builtin_amdgcn_sdot2(
+                    __builtin_bit_cast(qi_short2, xp[c][j]), m2, acc[c], false));
+        }
+        int32_t y[COLS];
+#pragma unroll
+        for (int c = 0; c < COLS; c++)
+            y[c] = fold(acc[c]);  // T-range
+        // restored OOR symbols: 65536 == -1 where the stored word is 0
+        for (int e = 0; e < n_lm; e++) {
+            const int pos = s_i[e];
+            const long long w = s_col[e];
+            // branch-free per lane, unconditional load consumed at once (see
+            // the matrix-core epilogue: a load under a divergent branch made
+            // the compiler drain vmcnt(0) after every row)
+            const long long d = w - col;
+            const int32_t corr = plain[t * kin + pos];
+#pragma unroll
+            for (int c = 0; c < COLS; c++) {
+                const int32_t yc = fold(fold(y[c] - corr));
+                y[c] = d == c ? yc : y[c];
+            }
+        }
+        const int32_t rs = rscale[t];
+        if (rs != 1) {
+#pragma unroll
+            for (int c = 0; c < COLS; c++)
+                y[c] = fold(fold(mul_rs(y[c], rs)));
+        }
+        uint32_t o[COLS];
+        uint32_t bad = 0;
+#pragma unroll
+        for (int c = 0; c < COLS; c++) {
+            o[c] = static_cast<uint32_t>(y[c]);
+            bad |= o[c];
+        }
+        if (__builtin_expect((bad >> 16) != 0, 0)) {
+#pragma unroll
+            for (int c = 0; c < COLS; c++) {
+                if (static_cast<uint32_t>(y[c]) > 65535u && rec &&
+                    (FULL || c < avail))
+                    record_oor(out_oor, s, rowmap[t], col + c);
+                o[c] = fix16(y[c]);
+            }
+        }
+        {
+            // (a mismatch is rare: one ballot per row, the atomics by one lane)
+            uint32_t mm = 0;
+#pragma unroll
+            for (int c = 0; c < COLS; c++)
+                mm |= ((FULL || c < avail) && (o[c] & 0xffffu) != static_cast<uint32_t>(sv[c])
+                           ? 1u
+                           : 0u)
+                      << c;
+            mm = vr->skip ? 0u : mm;
+            const uint64_t any = __builtin_amdgcn_ballot_w64(mm != 0);
+            if (__builtin_expect(any != 0, 0)) {
+                uint32_t tot = 0;
+#pragma unroll
+                for (int c = 0; c < COLS; c++)
+                    tot += static_cast<uint32_t>(
+                        __builtin_popcountll(__builtin_amdgcn_ballot_w64((mm >> c) & 1u)));
+                // lane order is column order: the first lane holds the minimum
+                if (mm && static_cast<int>(threadIdx.x & 63) == __builtin_ctzll(any)) {
+                    const long long idx = static_cast<long long>(s) * L.R + t;
+                    atomicAdd(vr->v.vmis + idx, tot);
+                    atomicMin(vr->v.first + idx,
+                              static_cast<uint32_t>(col) + __builtin_ctz(mm));
+                }
+            }
+        }
+    }
+}
+
+
 template <int KP, int COLS, bool BUF>
 __global__ __launch_bounds__(kBlock) void matrix_kernel(MatArgs a)
 {
@@ -945,14 +1126,23 @@ __global__ __launch_bounds__(kBlock) void matrix_kernel(MatArgs a)
     // __forceinline__ body changed the register allocation of the plain
     // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
     // form keeps its text and its resource report; do not fold the two.)
-    constexpr bool BOTH = false;
+    constexpr MatMode MODE = MatMode::kPlain;
+    constexpr VerArgs v{};
 #include "matrix_kernel_body.h"
 }
 // input and output marks in one launch (a repair): see push_slow_tile
 template <int KP, int COLS, bool BUF>
 __global__ __launch_bounds__(kBlock) void matrix_kernel_both(MatArgs a)
 {
-    constexpr bool BOTH = true;
+    constexpr MatMode MODE = MatMode::kBoth;
+    constexpr VerArgs v{};
+#include "matrix_kernel_body.h"
+}
+// a fused check: the repair's product compared with the stored rows
+template <int KP, int COLS, bool BUF>
+__global__ __launch_bounds__(kBlock) void matrix_kernel_verify(MatArgs a, VerArgs v)
+{
+    constexpr MatMode MODE = MatMode::kVerify;
 #include "matrix_kernel_body.h"
 }
 
@@ -995,6 +1185,89 @@ typedef int qi_v4i __attribute__((ext_vector_type(4)));
 typedef int qi_v2i __attribute__((ext_vector_type(2)));
 typedef unsigned int qi_v4u __attribute__((ext_vector_type(4)));
 
+// ---- the verify forms' epilogue on the matrix cores: lane (g, t) holds 16
+// adjacent columns of output row t, so it loads the same 32 bytes of the
+// stored row (the four lanes of a row read one whole 128-byte line) and
+// compares in place; nothing goes through the LDS transpose of the stores.
+
+// This lane's stored row: fragment chk[t] of the stripe in the source
+// regions, as a byte offset inside its region and the region (lo: region 0);
+// rows past R get an offset past any extent (their loads return 0)
+struct VerRow {
+    uint32_t off;
+    bool lo;
+};
+__device__ __forceinline__ VerRow verify_row(const VerArgs& v, const RowSrc& src, int s, int R,
+                                             int t)
+{
+    // (an id the context builder refused still addresses a row of the stripe)
+    const int id = min(static_cast<int>(v.chk[static_cast<long long>(s) * R + (t < R ? t : R - 1)]),
+                       src.rows0 + src.rows1 - 1);
+    const bool lo = id < src.split;
+    const uint32_t off =
+        static_cast<uint32_t>(lo ? id * src.rs0 * 2 : (id - src.split) * src.rs1 * 2);
+    return {t < R ? off : 0x80000000u, lo};
+}
+
+// 16 columns (32 bytes) of that row from byte cb2 on.  TWO: the rows of a
+// wave lie in either region, so each lane loads through both descriptors,
+// past the extent in the other one (no memory access, zeros)
+template <bool TWO>
+__device__ __forceinline__ void verify_load16(const Region<true>& g0, const Region<true>& g1,
+                                              const VerRow& vr, uint32_t cb2, qi_v4u (&sv)[2])
+{
+    constexpr uint32_t kOob = 0x80000000u;
+    const bool in = vr.off != kOob;
+    const uint32_t o0 = in && (!TWO || vr.lo) ? vr.off + cb2 : kOob;
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+        sv[h] = __builtin_amdgcn_raw_buffer_load_b128(g0.r, static_cast<int>(o0 + 16 * h), 0,
+                                                      kAuxLd);
+    if constexpr (TWO) {
+        const uint32_t o1 = in && !vr.lo ? vr.off + cb2 : kOob;
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+            sv[h] |= __builtin_amdgcn_raw_buffer_load_b128(g1.r, static_cast<int>(o1 + 16 * h), 0,
+                                                           kAuxLd);
+    }
+}
+
+// Compare this lane's 16 stored-form values y (row idx - s R of the stripe,
+// columns cb ..) with the loaded words; a row's mismatches are summed over
+// its four lanes (g) and reported by the first: one atomic add and one
+// atomic min per (wave, row) that saw one.  Every lane of the wave calls it;
+// skip (wave-uniform): a slow tile, counted by its redo.
+__device__ __forceinline__ void verify_tile16(const VerArgs& v, long long idx, bool trow,
+                                              const int32_t (&y)[16], const qi_v4u (&sv)[2],
+                                              long long cb, bool skip)
+{
+    uint32_t mm = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const uint32_t w = sv[h][d];
+            mm |= (static_cast<uint32_t>(y[8 * h + 2 * d]) != (w & 0xffffu) ? 1u : 0u)
+                  << (8 * h + 2 * d);
+            mm |= (static_cast<uint32_t>(y[8 * h + 2 * d + 1]) != (w >> 16) ? 1u : 0u)
+                  << (8 * h + 2 * d + 1);
+        }
+    mm = trow && !skip ? mm : 0u;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(mm != 0) != 0, 0)) {
+        uint32_t nm = static_cast<uint32_t>(__builtin_popcount(mm));
+        uint32_t fm = mm ? static_cast<uint32_t>(cb) + __builtin_ctz(mm) : 0xffffffffu;
+#pragma unroll
+        for (int o = 16; o < 64; o *= 2) {
+            nm += __shfl_xor(nm, o);
+            fm = min(fm, static_cast<uint32_t>(__shfl_xor(fm, o)));
+        }
+        if ((threadIdx.x & 63) < 16 && nm) {
+            atomicAdd(v.vmis + idx, nm);
+            atomicMin(v.first + idx, fm);
+        }
+    }
+}
+
 // Geometry of a matrix-core block: NST super tiles of 64 columns (the
 // block's columns, staged once as the A image), NW waves.  RSPLIT: the waves
 // split the row blocks (wave wv takes wv, wv + NW, ...) and each walks every
@@ -1032,14 +1305,23 @@ __global__ __launch_bounds__(64 * NW) void matrix_mfma_kernel(MatArgs a)
     // __forceinline__ body changed the register allocation of the plain
     // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
     // form keeps its text and its resource report; do not fold the two.)
-    constexpr bool BOTH = false;
+    constexpr MatMode MODE = MatMode::kPlain;
+    constexpr VerArgs v{};
 #include "matrix_mfma_body.h"
 }
 // input and output marks in one launch (a repair): see push_slow_tile
 template <int KS, int NST, int NW, bool RSPLIT>
 __global__ __launch_bounds__(64 * NW) void matrix_mfma_kernel_both(MatArgs a)
 {
-    constexpr bool BOTH = true;
+    constexpr MatMode MODE = MatMode::kBoth;
+    constexpr VerArgs v{};
+#include "matrix_mfma_body.h"
+}
+// a fused check: the repair's product compared with the stored rows
+template <int KS, int NST, int NW, bool RSPLIT>
+__global__ __launch_bounds__(64 * NW) void matrix_mfma_kernel_verify(MatArgs a, VerArgs v)
+{
+    constexpr MatMode MODE = MatMode::kVerify;
 #include "matrix_mfma_body.h"
 }
 
@@ -1366,21 +1648,137 @@ __global__ __launch_bounds__(512) void matrix_os_kernel(MatArgs a, int G, int C,
     // __forceinline__ body changed the register allocation of the plain
     // form -- SGPR spills, VGPRs, once the occupancy.  This way the plain
     // form keeps its text and its resource report; do not fold the two.)
-    constexpr bool BOTH = false;
+    constexpr MatMode MODE = MatMode::kPlain;
+    constexpr VerArgs v{};
 #include "matrix_os_body.h"
 }
 // input and output marks in one launch (a repair): see push_slow_tile
 template <int KS, int WR, int RPW, bool TWO>
 __global__ __launch_bounds__(512) void matrix_os_kernel_both(MatArgs a, int G, int C, int TS)
 {
-    constexpr bool BOTH = true;
+    constexpr MatMode MODE = MatMode::kBoth;
+    constexpr VerArgs v{};
+#include "matrix_os_body.h"
+}
+// a fused check: the repair's product compared with the stored rows
+template <int KS, int WR, int RPW, bool TWO>
+__global__ __launch_bounds__(512) void matrix_os_kernel_verify(MatArgs a, int G, int C, int TS,
+                                                               VerArgs v)
+{
+    constexpr MatMode MODE = MatMode::kVerify;
 #include "matrix_os_body.h"
 }
 
 
 // ---------------------------------------------------------------------------
+// Fused check, the marks: the _verify forms left every recomputed 65536 of
+// check row t in work bucket t; the stored row's own bucket must hold exactly
+// those columns.  One block per (stripe, check row) takes the two buckets as
+// sets and counts their symmetric difference by comparing all pairs (a bucket
+// holds about words / 65537 entries; the cost is quadratic, but no entry is
+// ever dropped): entry i counts when the other bucket lacks its column and no
+// earlier entry of its own bucket repeats it.  Stored entries that are no
+// column of the row (>= words) are ignored.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void verify_marks_kernel(
+    const uint16_t* __restrict__ checks, int R, Oor stored, int slot_base, Oor work,
+    long long words, uint32_t* __restrict__ mark_mismatch, uint32_t* __restrict__ first,
+    uint32_t* err)
+{
+    __shared__ uint32_t s_n, s_min;
+    const int s = blockIdx.x / R, t = blockIdx.x - s * R;
+    const long long idx = static_cast<long long>(s) * R + t;
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        s_min = 0xffffffffu;
+    }
+    __syncthreads();
+    const int slot = static_cast<int>(checks[idx]) - slot_base;
+    const bool has = stored.counts != nullptr && slot >= 0 && slot < stored.slots;
+    const long long ab = static_cast<long long>(s) * stored.slots + slot;
+    uint32_t na = has ? stored.counts[ab] : 0u, nb = work.counts[idx];
+    if (na > static_cast<uint32_t>(stored.cap) || nb > static_cast<uint32_t>(work.cap)) {
+        if (threadIdx.x == 0)
+            atomicOr(err, kErrOorTruncated);
+        na = min(na, static_cast<uint32_t>(stored.cap));
+        nb = min(nb, static_cast<uint32_t>(work.cap));
+    }
+    const uint32_t* A = has ? stored.entries + ab * stored.cap : nullptr;
+    const uint32_t* B = work.entries + idx * work.cap;
+    uint32_t n = 0, mn = 0xffffffffu;
+    for (uint32_t i = threadIdx.x; i < na + nb; i += kBlock) {
+        const bool in_a = i < na;
+        const uint32_t* own = in_a ? A : B;
+        const uint32_t* other = in_a ? B : A;
+        const uint32_t io = in_a ? i : i - na, n_other = in_a ? nb : na;
+        const uint32_t c = own[io];
+        bool count = !in_a || c < words;
+        for (uint32_t j = 0; count && j < io; j++)
+            count = own[j] != c;
+        for (uint32_t j = 0; count && j < n_other; j++)
+            count = other[j] != c;
+        if (count) {
+            n++;
+            mn = min(mn, c);
+        }
+    }
+    if (n) {
+        atomicAdd(&s_n, n);
+        atomicMin(&s_min, mn);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n) {
+        atomicAdd(mark_mismatch + idx, s_n);
+        atomicMin(first + idx, s_min);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void verify_init_kernel(uint32_t* value_mismatch,
+                                                             uint32_t* mark_mismatch,
+                                                             uint32_t* first,
+                                                             uint32_t* work_counts, long long n)
+{
+    const long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i < n) {
+        value_mismatch[i] = 0u;
+        mark_mismatch[i] = 0u;
+        first[i] = 0xffffffffu;
+        work_counts[i] = 0u;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+int launch_verify_init(uint32_t* value_mismatch, uint32_t* mark_mismatch, uint32_t* first,
+                       uint32_t* work_counts, long long n, hipStream_t st)
+{
+    if (n <= 0)
+        return 0;
+    const long long grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7fffffffLL)
+        return -1;
+    hipLaunchKernelGGL(verify_init_kernel, dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, st,
+                       value_mismatch, mark_mismatch, first, work_counts, n);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_verify_marks(const uint16_t* checks, int R, int S, const Oor* stored, int slot_base,
+                        const Oor& work, long long words, uint32_t* mark_mismatch,
+                        uint32_t* first, uint32_t* err, hipStream_t st)
+{
+    const long long grid = static_cast<long long>(S) * R;
+    if (grid <= 0)
+        return 0;
+    if (grid > 0x7fffffffLL)
+        return -1;
+    const Oor none{nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL(verify_marks_kernel, dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, st,
+                       checks, R, stored ? *stored : none, slot_base, work, words, mark_mismatch,
+                       first, err);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 static int grid_for(long long words, int cols, int n_stripes, int* tiles)
 {
     const long long per = static_cast<long long>(kBlock) * cols;
@@ -1492,17 +1890,22 @@ static bool lds_opt_in(const void* fn, size_t bytes)
 }
 
 template <int KP, int COLS, bool BUF>
-static int mat_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
+static int mat_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st, const VerArgs& v)
 {
     if (grid_for(a.words - a.ext.c0, COLS, S, &a.tiles))
         return -1;
+    if (r.verify) {
+        hipLaunchKernelGGL((matrix_kernel_verify<KP, COLS, BUF>), dim3(a.tiles * S), dim3(kBlock),
+                           0, st, a, v);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const auto fn = r.both ? &matrix_kernel_both<KP, COLS, BUF> : &matrix_kernel<KP, COLS, BUF>;
     hipLaunchKernelGGL(fn, dim3(a.tiles * S), dim3(kBlock), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 template <int KS, int NST, int NW, bool RSPLIT>
-static int mfma_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
+static int mfma_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st, const VerArgs& v)
 {
     using G = MfmaTile<KS, NST, NW>;
     using Fn = void (*)(MatArgs);
@@ -1524,6 +1927,16 @@ static int mfma_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
                    (!both || lds_opt_in(reinterpret_cast<const void*>(both), G::kLdsStaged));
         }) < 0)
         return -2;
+    if (r.verify) {
+        // (the shapes of the _both form; at most 4 row blocks: under 64 KiB)
+        if constexpr (mfma_has_both(KS)) {
+            static_assert(G::kLdsStaged <= 65536, "verify form without the LDS opt-in");
+            hipLaunchKernelGGL((matrix_mfma_kernel_verify<KS, NST, NW, RSPLIT>), dim3(t * S),
+                               dim3(G::kThreads), lds, st, a, v);
+            return hipGetLastError() == hipSuccess ? 0 : -2;
+        }
+        return -1;
+    }
     hipLaunchKernelGGL(run, dim3(t * S), dim3(G::kThreads), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1548,7 +1961,7 @@ static int gen_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 }
 
 template <int KS, int WR, int RPW>
-static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
+static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st, const VerArgs& v)
 {
     using O = OsTile<OsK<KS>::KC, WR>;
     // the forms the library has (matrix_route.h), indexed by two + 2 * both
@@ -1558,6 +1971,12 @@ static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
     if constexpr (os_has_both(KS, WR, RPW)) {
         fns[2] = &matrix_os_kernel_both<KS, WR, RPW, false>;
         fns[3] = &matrix_os_kernel_both<KS, WR, RPW, true>;
+    }
+    // the verify forms, indexed by two (the shapes of the _both forms)
+    void (*vfns[2])(MatArgs, int, int, int, VerArgs) = {nullptr, nullptr};
+    if constexpr (os_has_both(KS, WR, RPW)) {
+        vfns[0] = &matrix_os_kernel_verify<KS, WR, RPW, false>;
+        vfns[1] = &matrix_os_kernel_verify<KS, WR, RPW, true>;
     }
     const long long TS = r.wfull / O::kCols;
     if (TS <= 0 || TS > 0x7fffffffLL)
@@ -1571,6 +1990,9 @@ static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
     static std::atomic<int> slots_of[kOnceDevices];
     const int dev = once_per_device(attr_done, [&](int d) {
         for (const auto fn : fns)
+            if (fn && lds > 65536 && !lds_opt_in(reinterpret_cast<const void*>(fn), lds))
+                return false;
+        for (const auto fn : vfns)
             if (fn && lds > 65536 && !lds_opt_in(reinterpret_cast<const void*>(fn), lds))
                 return false;
         int per_cu = 0, cus = 0;
@@ -1621,6 +2043,14 @@ static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
     if (blocks > 0x7fffffffLL)
         return -1;
     a.tiles = static_cast<int>(TS);
+    if (r.verify) {
+        const auto vfn = vfns[r.two ? 1 : 0];
+        if (!vfn)
+            return -1;
+        hipLaunchKernelGGL(vfn, dim3(static_cast<unsigned>(blocks)), dim3(O::kThreads), lds, st,
+                           a, G, static_cast<int>(C), static_cast<int>(TS), v);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const auto fn = fns[(r.two ? 1 : 0) + (r.both ? 2 : 0)];
     if (!fn)
         return -1;  // (matrix_route reports these as errors)
@@ -1632,16 +2062,17 @@ static int os_launch(MatArgs a, const MatRoute& r, int S, hipStream_t st)
 // The one map from a route to its instantiation: every matrix kernel of the
 // library appears here, and nothing else launches one (the redo launch,
 // which has no parameters, is launch_matrix's).
-static int launch_route(const MatRoute& r, MatArgs a, int S, hipStream_t st)
+static int launch_route(const MatRoute& r, MatArgs a, int S, hipStream_t st,
+                        const VerArgs& v = VerArgs{})
 {
     if (r.err == -1)
         return -1;
 #define QI_OS(KS_, WR_, RPW_)                                  \
     if (r.KS == KS_ && r.WR == WR_ && r.RPW == RPW_)           \
-        rc = os_launch<KS_, WR_, RPW_>(a, r, S, st);
+        rc = os_launch<KS_, WR_, RPW_>(a, r, S, st, v);
 #define QI_MFMA(KS_, NST_, NW_, RS_)                                          \
     if (r.KS == KS_ && r.NST == NST_ && r.NW == NW_ && r.RSPLIT == RS_)       \
-        rc = mfma_launch<KS_, NST_, NW_, RS_>(a, r, S, st);
+        rc = mfma_launch<KS_, NST_, NW_, RS_>(a, r, S, st, v);
     if (r.core != MatCore::kNone) {
         int rc = -1;
         if (r.core == MatCore::kGen) {
@@ -1663,7 +2094,7 @@ static int launch_route(const MatRoute& r, MatArgs a, int S, hipStream_t st)
 #undef QI_MFMA
 #define QI_TAIL(KP_, COLS_, BUF_)                                \
     if (r.KP == KP_ && r.COLS == COLS_ && r.BUF == BUF_)         \
-        return mat_launch<KP_, COLS_, BUF_>(a, r, S, st);
+        return mat_launch<KP_, COLS_, BUF_>(a, r, S, st, v);
     QI_TAIL(2, 1, false) QI_TAIL(2, 1, true) QI_TAIL(2, 2, true) QI_TAIL(2, 4, true)
     QI_TAIL(4, 1, false) QI_TAIL(4, 1, true) QI_TAIL(4, 2, true) QI_TAIL(4, 4, true)
     QI_TAIL(8, 1, false) QI_TAIL(8, 1, true) QI_TAIL(8, 2, true) QI_TAIL(8, 4, true)
@@ -1690,13 +2121,13 @@ static MatExt mat_ext(const RowSrc& src, int R, const RowDst& dst, long long wor
 }
 
 // what matrix_route reads of a launch
-static MatRouteIn route_in(const MatArgs& a)
+static MatRouteIn route_in(const MatArgs& a, bool verify = false)
 {
     const bool buf = a.ext.e0 && a.ext.eo && (!a.src.base1 || a.ext.e1);
     const int align = !rows_aligned(2, a.src, a.dst) ? 1 : rows_aligned(4, a.src, a.dst) ? 4 : 2;
     return MatRouteIn{a.L, a.words, buf, align, a.in_oor.counts != nullptr,
                       a.out_oor.counts != nullptr, a.ids != nullptr, a.route != nullptr,
-                      a.src.base1 != nullptr};
+                      a.src.base1 != nullptr, verify};
 }
 
 bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long words)
@@ -1712,9 +2143,10 @@ bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long wo
 // for aligned rows in buffer range; a decode's ids and route table come with
 // its input marks.  both: input and output marks in one launch (a repair)
 std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
-                                bool both)
+                                bool both, bool verify)
 {
-    return to_string(matrix_route(MatRouteIn{L, words, true, 4, in_oor, both, in_oor, in_oor, two}));
+    return to_string(
+        matrix_route(MatRouteIn{L, words, true, 4, in_oor, both, in_oor, in_oor, two, verify}));
 }
 
 std::string encode_fnt_kernel_name(int k)
@@ -1728,7 +2160,8 @@ int launch_matrix(const MatLayout& L, const int32_t* mat, long long ms,
                   const int32_t* ids, long long is, RowSrc src, RowDst dst,
                   long long words, int S, const Oor* in_oor, int slot_base,
                   const Oor* out_oor, const int32_t* rowmap, const uint32_t* route,
-                  long long rstride, SlowList slow, uint32_t* err, hipStream_t st)
+                  long long rstride, SlowList slow, uint32_t* err, hipStream_t st,
+                  const MatVerify* ver)
 {
     if (!rowmap)
         return -1;
@@ -1739,13 +2172,23 @@ int launch_matrix(const MatLayout& L, const int32_t* mat, long long ms,
     const Oor none{nullptr, nullptr, 0, 0};
     MatArgs a{L, mat, ms, ids, is, src, dst, mat_ext(src, L.R, dst, words), words, 0, in_oor ? *in_oor : none, slot_base, out_oor ? *out_oor : none,
               rowmap, route, rstride, in_oor ? slow : SlowList{nullptr, 0}, err};
-    const MatRoute r = matrix_route(route_in(a));
-    const int rc = launch_route(r, a, S, st);
+    // a fused check (ver): the stored rows are the source regions', nothing
+    // is written through dst, and the output buckets take the recomputed
+    // rows' 65536 positions
+    const VerArgs v = ver ? VerArgs{ver->checks, ver->value_mismatch, ver->first} : VerArgs{};
+    if (ver && (!ver->checks || !ver->value_mismatch || !ver->first || !out_oor))
+        return -1;
+    const MatRoute r = matrix_route(route_in(a, ver != nullptr));
+    const int rc = launch_route(r, a, S, st, v);
     if (rc || !r.redo)
         return rc;
     // the dot2 kernel's tiles with more marks than its LDS list (the matrix
     // cores redo theirs themselves): see push_slow_tile
     const int grid = (S + kRedoSpan - 1) / kRedoSpan;
+    if (r.verify) {
+        hipLaunchKernelGGL(matrix_redo_kernel_verify, dim3(grid), dim3(kBlock), 0, st, a, S, v);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const auto redo = r.both ? &matrix_redo_kernel_both : &matrix_redo_kernel;
     hipLaunchKernelGGL(redo, dim3(grid), dim3(kBlock), 0, st, a, S);
     return hipGetLastError() == hipSuccess ? 0 : -2;

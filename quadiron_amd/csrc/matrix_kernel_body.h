@@ -1,7 +1,11 @@
-// Body of a kernel of kernels.hip, included once per form: BOTH (a
-// constexpr bool set by the including kernel) selects the form for input
-// and output marks in one launch (a repair); with BOTH false the text is
-// the kernel as it was before that form existed.  Not a stand-alone header.
+// Body of a kernel of kernels.hip, included once per form: MODE (a
+// constexpr MatMode set by the including kernel, next to its VerArgs v)
+// selects the plain form, the form for input and output marks in one launch
+// (BOTH: a repair) or the verify form (VERIFY: a repair that compares with
+// the stored row instead of storing); in the plain form the text is the
+// kernel as it was before the others existed.  Not a stand-alone header.
+    [[maybe_unused]] constexpr bool BOTH = MODE != MatMode::kPlain,
+                                    VERIFY = MODE == MatMode::kVerify;
     const MatLayout L = a.L;
     const int32_t* __restrict__ mat = a.mat;
     const long long mat_stride = a.ms;
@@ -65,11 +69,14 @@
     // KP >= 64 (the column tails of k > 64): 128-256 ids do not fit the
     // SGPRs (they spilled to VGPR lanes and scratch), so lane c of
     // idl[i / 64] holds id i and the row loads read it with v_readlane.
-    constexpr int NIL = KP >= 64 ? 2 * KP / 64 : 1;
-    constexpr int NIV = KP >= 64 ? 1 : 2 * KP;
+    // (VERIFY: from KP = 32 on -- its row addressing needs the SGPRs the 64
+    // ids took, and the flat form spilled to scratch)
+    constexpr int kIdLanes = VERIFY ? 32 : 64;
+    constexpr int NIL = KP >= kIdLanes ? (2 * KP + 63) / 64 : 1;
+    constexpr int NIV = KP >= kIdLanes ? 1 : 2 * KP;
     int idl[NIL];
     int idv[NIV];
-    if constexpr (KP >= 64) {
+    if constexpr (KP >= kIdLanes) {
         const int ln = static_cast<int>(threadIdx.x & 63);
 #pragma unroll
         for (int c = 0; c < NIL; c++) {
@@ -96,7 +103,7 @@
         }
     }
     auto id_of = [&](int i) {
-        if constexpr (KP >= 64)
+        if constexpr (KP >= kIdLanes)
             return __builtin_amdgcn_readlane(idl[i / 64], i % 64);
         else
             return idv[i];
@@ -124,7 +131,20 @@
         // a slow tile records no output marks here, matrix_redo_kernel_both
         // does, from fully restored inputs (block-uniform)
         const Oor out_rec = sc.slow ? Oor{nullptr, nullptr, 0, 0} : out_oor;
-        if (full) {
+        if constexpr (VERIFY) {
+            // the same, comparing with the stored rows (a slow tile is
+            // counted by the redo alone)
+            const VerRows<BUF> vrows{v, src, g0, g1, sc.slow};
+            if (full) {
+                matrix_compute_verify<KP, COLS, true, BUF>(L, M, xp, go, ors, voff, col, col0,
+                                                           COLS, s, n_lm, s_i, s_col, out_rec,
+                                                           a.rowmap, &vrows);
+            } else if (col < words) {
+                matrix_compute_verify<KP, COLS, false, BUF>(L, M, xp, go, ors, voff, col, col0,
+                                                            words - col, s, n_lm, s_i, s_col,
+                                                            out_rec, a.rowmap, &vrows);
+            }
+        } else if (full) {
             matrix_compute<KP, COLS, true, BUF>(L, M, xp, go, ors, voff, col, col0, COLS, s,
                                                 n_lm, s_i, s_col, out_rec, a.rowmap);
         } else if (col < words) {

@@ -1,7 +1,11 @@
-// Body of a kernel of kernels.hip, included once per form: BOTH (a
-// constexpr bool set by the including kernel) selects the form for input
-// and output marks in one launch (a repair); with BOTH false the text is
-// the kernel as it was before that form existed.  Not a stand-alone header.
+// Body of a kernel of kernels.hip, included once per form: MODE (a
+// constexpr MatMode set by the including kernel, next to its VerArgs v)
+// selects the plain form, the form for input and output marks in one launch
+// (BOTH: a repair) or the verify form (VERIFY: a repair that compares with
+// the stored row instead of storing); in the plain form the text is the
+// kernel as it was before the others existed.  Not a stand-alone header.
+    [[maybe_unused]] constexpr bool BOTH = MODE != MatMode::kPlain,
+                                    VERIFY = MODE == MatMode::kVerify;
     const MatLayout L = a.L;
     const int32_t* __restrict__ mat = a.mat;
     const long long mat_stride = a.ms;
@@ -228,6 +232,12 @@
                        const int32_t rs, const int32_t (&pr)[3]) {
         const int t = 16 * rb + tl;
         const bool trow = t < L.R;
+        // VERIFY: this lane's stored row, and its 16 columns of the super
+        // tile (loaded ahead of the tile's MFMAs)
+        [[maybe_unused]] VerRow vrow{};
+        [[maybe_unused]] qi_v4u sv[2];
+        if constexpr (VERIFY)
+            vrow = verify_row(v, src, s, L.R, t);
         // MFMAs of super tile ST into acc
         auto tile_mfma = [&](const int ST, qi_v4i (&acc)[4][3]) {
 #pragma unroll
@@ -350,6 +360,11 @@
                     }
                 }
             }
+            if constexpr (VERIFY) {
+                // compared where it lies: no transpose, no store
+                verify_tile16(v, static_cast<long long>(s) * L.R + t, trow, y, sv, cb, sc.slow);
+                return;
+            }
             qi_v4u o0, o1;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
@@ -408,6 +423,13 @@
         for (int st = 0; st < nst; st++) {
             qi_v4i acc[4][3];
             int32_t y[16];
+            if constexpr (VERIFY) {
+                const uint32_t cb2 = static_cast<uint32_t>((col0 + 64 * st_of(st) + 16 * g) * 2);
+                if (src.base1)  // (block-uniform)
+                    verify_load16<true>(g0, g1, vrow, cb2, sv);
+                else
+                    verify_load16<false>(g0, g1, vrow, cb2, sv);
+            }
             tile_mfma(st_of(st), acc);
             tile_y(acc, y);
             tile_fin(st_of(st), y);
@@ -439,7 +461,8 @@
         // block redoes its columns once its stores are done, with the image
         // as scratch (kin x 136 bytes <= the image)
         drain_block_stores();
-        redo_columns<64 * NW, BOTH>(a, s, col0, col1, reinterpret_cast<uint16_t*>(qi_lds),
+        redo_columns<64 * NW, MODE>(a, s, col0, col1, reinterpret_cast<uint16_t*>(qi_lds),
                               reinterpret_cast<uint32_t*>(qi_lds + kin * 2 * kRedoCols),
-                              reinterpret_cast<uint32_t*>(qi_lds + kin * (2 * kRedoCols + 8)));
+                              reinterpret_cast<uint32_t*>(qi_lds + kin * (2 * kRedoCols + 8)), 0, 1,
+                              v);
     }

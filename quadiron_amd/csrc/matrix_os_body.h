@@ -1,7 +1,11 @@
-// Body of a kernel of kernels.hip, included once per form: BOTH (a
-// constexpr bool set by the including kernel) selects the form for input
-// and output marks in one launch (a repair); with BOTH false the text is
-// the kernel as it was before that form existed.  Not a stand-alone header.
+// Body of a kernel of kernels.hip, included once per form: MODE (a
+// constexpr MatMode set by the including kernel, next to its VerArgs v)
+// selects the plain form, the form for input and output marks in one launch
+// (BOTH: a repair) or the verify form (VERIFY: a repair that compares with
+// the stored row instead of storing); in the plain form the text is the
+// kernel as it was before the others existed.  Not a stand-alone header.
+    [[maybe_unused]] constexpr bool BOTH = MODE != MatMode::kPlain,
+                                    VERIFY = MODE == MatMode::kVerify;
     constexpr int NCH = OsK<KS>::NCH, KC = OsK<KS>::KC;
     using O = OsTile<KC, WR>;  // one chunk's image (the whole K when NCH = 1)
     constexpr int KH = O::kRows, RSB = O::kPitch, RPT = O::kRpt, NCOL = O::kCols;
@@ -75,6 +79,10 @@
     bool act[RPW];
     qi_v4i b0[RPW][KS / 4], b1[RPW][KS / 4];
     int32_t kt[RPW], rs[RPW], pr[RPW][3];
+    // VERIFY: this lane's stored row per row block, and its 16 columns of
+    // the tile in hand (loaded ahead of the tile's MFMAs)
+    [[maybe_unused]] VerRow vrow[RPW];
+    [[maybe_unused]] qi_v4u sv[2];
 #pragma unroll
     for (int j = 0; j < RPW; j++) {
         // row blocks dealt round-robin over the G groups (their counts
@@ -106,6 +114,8 @@
             const int ot = 16 * rbc + 8 * h + (l >> 3);
             pr[j][1 + h] = rowmap[ot < L.R ? ot : L.R - 1];
         }
+        if constexpr (VERIFY)
+            vrow[j] = verify_row(v, src, s, L.R, act[j] ? t : L.R);
     }
 
     // staging: lane (rowgrp, cl) loads 4 columns (b64) of rows kRpp r +
@@ -294,10 +304,10 @@
                 const long long c0 = static_cast<long long>(tile) * NCOL;
                 // this group's row blocks only: the G blocks of a column
                 // range each redo (and earlier stored) disjoint rows
-                redo_columns<512, BOTH>(a, s, c0, c0 + NCOL, reinterpret_cast<uint16_t*>(qi_lds),
+                redo_columns<512, MODE>(a, s, c0, c0 + NCOL, reinterpret_cast<uint16_t*>(qi_lds),
                                   reinterpret_cast<uint32_t*>(qi_lds + kin * 2 * kRedoCols),
                                   reinterpret_cast<uint32_t*>(qi_lds + kin * (2 * kRedoCols + 8)),
-                                  gq, G);
+                                  gq, G, v);
             }
         }
     };
@@ -421,6 +431,16 @@
                 }
             }
         }
+        if constexpr (VERIFY) {
+            // compared where it lies (no transpose, no store); a slow tile is
+            // counted by its redo
+            const int tb = static_cast<int>(col0 / NCOL) - t0;
+            verify_tile16(v, static_cast<long long>(s) * L.R + t, trow, y, sv, cb,
+                          (slow_bits[tb >> 5] >> (tb & 31)) & 1u);
+            if constexpr (j == RPW - 1)
+                before_stores();
+            return;
+        }
         qi_v4u o0, o1;
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -460,12 +480,17 @@
     auto compute = [&](const uint8_t* img, long long col0, int n_lm, const int* mi,
                        const uint32_t* mc, auto jc, auto&& before_stores) {
         qi_v4i acc[4][3];
+        if constexpr (VERIFY)
+            verify_load16<TWO>(g0, g1, vrow[decltype(jc)::value],
+                               static_cast<uint32_t>((col0 + 16 * g) * 2), sv);
         init_acc(acc, jc);
         mma(img, acc, jc, C0{});
         epilogue(acc, col0, n_lm, mi, mc, jc, before_stores);
     };
 
     auto idle_stores = [&]() {
+        if constexpr (VERIFY)
+            return;  // (the verify forms store nothing)
 #pragma unroll
         for (int h = 0; h < 2; h++)
             __builtin_amdgcn_raw_buffer_store_b128(qi_v4u{0u, 0u, 0u, 0u}, go.r,

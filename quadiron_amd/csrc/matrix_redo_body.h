@@ -1,7 +1,11 @@
-// Body of a kernel of kernels.hip, included once per form: BOTH (a
-// constexpr bool set by the including kernel) selects the form for input
-// and output marks in one launch (a repair); with BOTH false the text is
-// the kernel as it was before that form existed.  Not a stand-alone header.
+// Body of a kernel of kernels.hip, included once per form: MODE (a
+// constexpr MatMode set by the including kernel, next to its VerArgs v)
+// selects the plain form, the form for input and output marks in one launch
+// (BOTH: a repair) or the verify form (VERIFY: a repair that compares with
+// the stored row instead of storing); in the plain form the text is the
+// kernel as it was before the others existed.  Not a stand-alone header.
+    [[maybe_unused]] constexpr bool BOTH = MODE != MatMode::kPlain,
+                                    VERIFY = MODE == MatMode::kVerify;
     // (the dot2 tails' slow tiles: k <= 256; the operand-stationary kernel
     // redoes its own in its dynamic LDS)
     __shared__ uint16_t xs[kMatGenMaxKin * kRedoCols];  // [input i][column]
@@ -34,7 +38,7 @@
             const long long t0 = static_cast<long long>(code >> 3) * kSlowGrain;
             const long long t1 = min(t0 + (static_cast<long long>(kSlowGrain) << (code & 7)),
                                      a.words);
-            redo_columns<kBlock, BOTH>(a, s, t0, t1, xs, mk, colmk);
+            redo_columns<kBlock, MODE>(a, s, t0, t1, xs, mk, colmk, 0, 1, v);
         }
         __syncthreads();
         if (tid == 0)

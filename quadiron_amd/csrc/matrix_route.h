@@ -85,7 +85,8 @@ constexpr bool os_has_two(int KS, int RPW)
     return !(KS >= 24 && RPW == 2);
 }
 // input and output marks in one launch: what a repair reaches (at most 4 row
-// blocks, k <= 256)
+// blocks, k <= 256); the verify forms (the stored rows compared, not
+// written) exist for the same shapes
 constexpr bool os_has_both(int KS, int WR, int RPW)
 {
     return (KS == 4 && WR == 4) || KS == 8 || (KS == 16 && RPW == 1);
@@ -104,6 +105,7 @@ struct MatRouteIn {
     bool in_marks, out_marks;  // OOR marks to restore / to record
     bool ids, route;           // per-stripe fragment ids / route tables
     bool two;                  // rows from two source regions
+    bool verify = false;       // compare with the stored rows, store nothing
 };
 
 enum class MatCore { kNone, kOs, kGen, kMfma };
@@ -124,6 +126,9 @@ struct MatRoute {
     int KP = 0, COLS = 0;
     bool BUF = false;
     bool redo = false;
+    // the _verify forms, of every kernel of the route (a fused check: the
+    // shapes of `both`)
+    bool verify = false;
     // -1: the library has no such matrix-core kernel (nothing is launched);
     // -3: none for the tail (the matrix cores, if any, still run first)
     int err = 0;
@@ -133,7 +138,9 @@ inline MatRoute matrix_route(const MatRouteIn& in)
 {
     MatRoute r;
     const int KS = in.L.KS(), RB = in.L.RB();
-    r.both = in.in_marks && in.out_marks;
+    r.verify = in.verify;
+    r.both = !in.verify && in.in_marks && in.out_marks;
+    const bool marks2 = r.both || r.verify;  // the forms of os_has_both
     r.wfull = in.words / kRouteTile * kRouteTile;
     if (KS > 0 && in.buf && in.align == 4 && r.wfull > 0) {
         r.KS = KS;
@@ -143,9 +150,10 @@ inline MatRoute matrix_route(const MatRouteIn& in)
             r.WR = og.wr;
             r.RPW = og.rpw;
             r.two = in.two;
-            if ((r.both && !os_has_both(KS, og.wr, og.rpw)) || (in.two && !os_has_two(KS, og.rpw)))
+            if ((marks2 && !os_has_both(KS, og.wr, og.rpw)) || (in.two && !os_has_two(KS, og.rpw)))
                 r.err = -1;
-        } else if (KS == 4 && RB >= 4 && !in.in_marks && !in.route && !in.ids && !in.two) {
+        } else if (KS == 4 && RB >= 4 && !in.in_marks && !in.route && !in.ids && !in.two &&
+                   !in.verify) {
             // a tall generator over one source region (every encode): the
             // lean generator kernel
             r.core = MatCore::kGen;
@@ -162,7 +170,7 @@ inline MatRoute matrix_route(const MatRouteIn& in)
             r.NW = 4;
             r.RSPLIT = KS == 8 || KS == 16 || RB >= 4;
             // only the operand-stationary kernel takes kin > 256
-            if (KS > 16 || (r.both && !mfma_has_both(KS)))
+            if (KS > 16 || (marks2 && !mfma_has_both(KS)))
                 r.err = -1;
         }
     } else {
@@ -187,7 +195,7 @@ inline MatRoute matrix_route(const MatRouteIn& in)
 // spelled as the demangler (and rocprofv3) spells the instantiations
 inline std::string to_string(const MatRoute& r)
 {
-    const std::string sfx = r.both ? "_both" : "";
+    const std::string sfx = r.verify ? "_verify" : r.both ? "_both" : "";
     auto tf = [](bool b) { return std::string(b ? "true" : "false"); };
     auto n = [](int v) { return std::to_string(v); };
     std::string s;

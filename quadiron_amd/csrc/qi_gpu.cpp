@@ -64,12 +64,12 @@ RowSrc plan_src(const qi_plan* p, const uint16_t* d_data, long long dss, long lo
 // apply the matrices of the contexts `v` (decode or repair) to the rows
 int apply_ctx(const qi_plan* p, const MatLayout& L, const MatCtxView& v, const RowSrc& src,
               const RowDst& out, long long words, int S, const Oor* in, int slot_base,
-              const Oor* out_marks, hipStream_t s)
+              const Oor* out_marks, hipStream_t s, const MatVerify* ver = nullptr)
 {
     // output row t = matrix row t (d_rowid: the identity, at least
     // QI_REPAIR_MAX_TARGETS entries)
     return launch_matrix(L, v.ctx, v.stride, v.ids(), v.stride, src, out, words, S, in, slot_base,
-                         out_marks, p->d_rowid, v.route(), v.stride, v.slow(), p->d_err, s);
+                         out_marks, p->d_rowid, v.route(), v.stride, v.slow(), p->d_err, s, ver);
 }
 
 // The decode of qi_gpu_decode and qi_gpu_decode_packed, which differ in the
@@ -334,6 +334,66 @@ const char* qi_gpu_repair_kernels(const qi_plan* p, int R, long long words)
         return "";
     names = "repair=" + repair_ctx_kernel_name(p->k, R) + " + " +
             matrix_kernel_names(repair_layout(p, R), words, true, p->sys != 0, true);
+    return names.c_str();
+}
+
+// ---- fused verify (k <= 256): the repair's launch in its _verify forms --
+// the check rows recomputed from the basis rows and compared with the stored
+// ones in the epilogue, their 65536 positions recorded in the work buckets --
+// then verify_marks_kernel over the stored and the work buckets ----
+size_t qi_gpu_verify_work_bytes(const qi_plan* p, int n_checks, int n_stripes, int work_cap)
+{
+    if (!p || p->ntt || n_stripes < 0 || work_cap < 0 || !repair_ok(p, n_checks))
+        return 0;
+    // per (stripe, check row): a count and work_cap entries
+    return static_cast<size_t>(n_stripes) * n_checks * (1 + static_cast<size_t>(work_cap)) *
+           sizeof(uint32_t);
+}
+
+int qi_gpu_verify(qi_plan* p, const void* d_ctx, int R, const uint16_t* d_checks,
+                  const uint16_t* d_data, long long dss, long long drs, const uint16_t* d_coded,
+                  long long css, long long crs, const uint32_t* d_counts,
+                  const uint32_t* d_entries, int cap, void* d_work, int work_cap,
+                  uint32_t* d_value_mismatch, uint32_t* d_mark_mismatch, uint32_t* d_first,
+                  long long words, int n_stripes, void* stream)
+{
+    if (!p || !d_ctx || !d_coded || !d_checks || !d_work || !d_value_mismatch ||
+        !d_mark_mismatch || !d_first || n_stripes < 0 || words < 0 || work_cap < 0)
+        return -1;
+    if (p->ntt)
+        return QI_ERR_UNSUPPORTED;
+    if (!repair_ok(p, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    const long long n = static_cast<long long>(n_stripes) * R;
+    uint32_t* wc = static_cast<uint32_t*>(d_work);
+    if (int rc = launch_verify_init(d_value_mismatch, d_mark_mismatch, d_first, wc, n, st(stream)))
+        return rc;
+    if (words == 0)
+        return 0;
+    const MatLayout L = repair_layout(p, R);
+    Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs, cap};
+    Oor work{wc, wc + n, R, work_cap};  // work slot j = check row j
+    const MatVerify ver{d_checks, d_value_mismatch, d_first};
+    const int slot_base = p->sys ? p->k : 0;
+    if (int rc = apply_ctx(p, L, MatCtxView(L, d_ctx, mat_ctx_words(L, words), words),
+                           plan_src(p, d_data, dss, drs, d_coded, css, crs),
+                           RowDst{nullptr, 0, 0}, words, n_stripes, d_counts ? &in : nullptr,
+                           slot_base, &work, st(stream), &ver))
+        return rc;
+    return launch_verify_marks(d_checks, R, n_stripes, d_counts ? &in : nullptr, slot_base, work,
+                               words, d_mark_mismatch, d_first, p->d_err, st(stream));
+}
+
+const char* qi_gpu_verify_kernels(const qi_plan* p, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || p->ntt || words <= 0 || !repair_ok(p, R))
+        return "";
+    names = "verify=" + repair_ctx_kernel_name(p->k, R) + " + " +
+            matrix_kernel_names(repair_layout(p, R), words, true, p->sys != 0, false, true) +
+            " + " + verify_marks_kernel_name();
     return names.c_str();
 }
 

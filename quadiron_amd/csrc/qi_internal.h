@@ -171,6 +171,12 @@ inline std::string repair_ctx_kernel_name(int k, int R)
     return "repair_ctx_kernel<" + std::to_string(repair_ctx_threads(k, R)) + ">";
 }
 
+// the bucket comparison a fused check ends with (launch_verify_marks)
+inline std::string verify_marks_kernel_name()
+{
+    return "verify_marks_kernel";
+}
+
 // ---- launchers (kernels.hip) ----
 // non-systematic encode by twisted register-resident sub-NTTs
 int launch_encode_fnt(int k, int n, int n_out, const int32_t* d_twist,
@@ -189,13 +195,41 @@ int launch_encode_fnt(int k, int n, int n_out, const int32_t* d_twist,
 //   identity for decode matrices)
 //   route: per-stripe OOR routing tables (route_stride u32 apart), or null
 //   slow: per-stripe slow-tile lists (required when in_oor is given)
+//   ver: a fused check instead of a product (see MatVerify); requires out_oor
+struct MatVerify;
 int launch_matrix(const MatLayout& L, const int32_t* mat, long long mat_stride,
                   const int32_t* ids, long long ids_stride, RowSrc src,
                   RowDst dst, long long words,
                   int n_stripes, const Oor* in_oor, int slot_base,
                   const Oor* out_oor, const int32_t* rowmap, const uint32_t* route,
                   long long route_stride, SlowList slow, uint32_t* d_err,
-                  hipStream_t stream);
+                  hipStream_t stream, const MatVerify* ver = nullptr);
+
+// A fused check (the _verify kernel forms): matrix row t of stripe s is
+// recomputed as in a repair and compared with the stored row of fragment
+// checks[s * R + t], addressed in the source regions like the inputs; no row
+// is written (dst is not used).  value_mismatch[s * R + t] counts the columns
+// whose low 16 bits differ and first[s * R + t] takes the smallest such
+// column by an atomic min (both initialised by the caller); the recomputed
+// 65536 positions go to out_oor (slot t), for launch_verify_marks.
+struct MatVerify {
+    const uint16_t* checks;
+    uint32_t* value_mismatch;
+    uint32_t* first;
+};
+// counters of S x R checks to 0 / 0 / 0xFFFFFFFF and the work buckets' counts
+// to 0
+int launch_verify_init(uint32_t* value_mismatch, uint32_t* mark_mismatch, uint32_t* first,
+                       uint32_t* work_counts, long long n, hipStream_t stream);
+// per (stripe, check row): the stored bucket of fragment checks[s * R + t]
+// (slot id - slot_base of `stored`; none for id < slot_base or stored null)
+// and the work bucket t as sets; the size of their symmetric difference is
+// added to mark_mismatch and its columns go to first by atomic min.  A bucket
+// over its capacity raises kErrOorTruncated; stored entries >= words are no
+// columns and are ignored
+int launch_verify_marks(const uint16_t* checks, int R, int n_stripes, const Oor* stored,
+                        int slot_base, const Oor& work, long long words, uint32_t* mark_mismatch,
+                        uint32_t* first, uint32_t* d_err, hipStream_t stream);
 
 // per-stripe decode matrices from fragment ids (S x k).
 //   mode 0: coefficient extraction (non-systematic: data = poly coefs)
@@ -240,7 +274,7 @@ bool matrix_cores_take(const RowSrc& src, const RowDst& dst, int R, long long wo
 // buffer range; diagnostics: qi_gpu_kernels); two: rows from two source
 // regions (the systematic decode)
 std::string matrix_kernel_names(const MatLayout& L, long long words, bool in_oor, bool two,
-                                bool both = false);
+                                bool both = false, bool verify = false);
 // the register-codelet encode kernel launch_encode_fnt runs (aligned rows)
 std::string encode_fnt_kernel_name(int k);
 
