@@ -20,6 +20,20 @@
  * u16 elements).  One call processes n_stripes stripes; every column of every
  * stripe is an independent codeword.
  *
+ * Supported layouts: a unit stride between the words of a row, and any
+ * positive row and stripe strides for which no two rows overlap; every tensor
+ * of a call has its own.  Fragment-major is one example (each fragment holds
+ * all its stripes back to back: stripe_stride = words, row_stride = n_stripes
+ * * words), stripe-major [stripe][row][word] the other.  While every stripe's
+ * row region, (rows - 1) * row_stride + words elements, stays inside a 31-bit
+ * byte range (below 2^31 - 1 bytes), the kernels named under qi_plan_create
+ * run.  Once one region of a call is larger -- rows GiB apart, as in a large
+ * fragment-major batch -- the whole call runs the flat-addressing forms of
+ * the dot2 and register-codelet kernels (k <= 256, 64-bit row offsets) or the
+ * NTT engine (k > 256) instead of the matrix cores.  That path is tested bit
+ * for bit against the reference, regions past 4 GiB included, but nobody has
+ * timed it: expect it to be slower, by an unmeasured amount.
+ *
  * OOR marks are kept in *buckets*: counts[s*slots + slot] (u32) and
  * entries[(s*slots + slot)*cap + e] (u32 word offset within the row).  Encode
  * zeroes nothing: callers clear counts (qi_gpu_oor_clear) before encoding.

@@ -93,6 +93,22 @@ struct Region {
     }
 };
 
+// Byte offset of a row inside its stripe region (wave-uniform): 32 bits as
+// a buffer op's soffset, 64 bits on the flat path, whose regions are the ones
+// that do not fit a 31-bit range (rows of a fragment-major layout lie GiB
+// apart)
+template <bool BUF>
+using roff_t = std::conditional_t<BUF, uint32_t, uint64_t>;
+// a row stride in bytes from its halves (the buffer forms take the low one)
+template <bool BUF>
+__device__ __forceinline__ roff_t<BUF> row_stride(uint32_t lo, uint32_t hi)
+{
+    if constexpr (BUF)
+        return lo;
+    else
+        return static_cast<uint64_t>(hi) << 32 | lo;
+}
+
 // Cache policy of the streamed rows (buffer-op aux bits on gfx950: 1 = sc0,
 // 2 = nt, 16 = sc1).  Measured with tools/membw2.hip / membw3.hip on the
 // kernels' own shapes (profiles/r1_membw.txt): nt|sc1 stores (device scope,
@@ -134,7 +150,7 @@ __device__ __forceinline__ void block_map(int b, int tiles, int& s, int& tile)
 
 // NDW (1 or 2) dwords per lane of the row at byte offset `row`
 template <int NDW, bool BUF, int AUX = 0>
-__device__ __forceinline__ void ld_dw(const Region<BUF>& g, uint32_t row,
+__device__ __forceinline__ void ld_dw(const Region<BUF>& g, roff_t<BUF> row,
                                       uint32_t voff, uint32_t (&w)[NDW])
 {
     static_assert(NDW == 1 || NDW == 2, "dword count");
@@ -159,7 +175,7 @@ __device__ __forceinline__ void ld_dw(const Region<BUF>& g, uint32_t row,
 }
 
 template <int NDW, bool BUF, int AUX = 0>
-__device__ __forceinline__ void st_dw(const Region<BUF>& g, uint32_t row,
+__device__ __forceinline__ void st_dw(const Region<BUF>& g, roff_t<BUF> row,
                                       uint32_t voff, const uint32_t (&w)[NDW])
 {
     static_assert(NDW == 1 || NDW == 2, "dword count");
@@ -187,7 +203,7 @@ __device__ __forceinline__ void st_dw(const Region<BUF>& g, uint32_t row,
 // FULL: COLS/2 dwords per lane (COLS 2 or 4); otherwise one u16 per column
 // and columns past `avail` are 0.
 template <int COLS, bool FULL, bool BUF, int AUX = 0>
-__device__ __forceinline__ void ld(const Region<BUF>& g, uint32_t row,
+__device__ __forceinline__ void ld(const Region<BUF>& g, roff_t<BUF> row,
                                    uint32_t voff, long long avail, int32_t* v)
 {
     if constexpr (FULL && COLS % 2 == 0) {
@@ -217,7 +233,7 @@ __device__ __forceinline__ void ld(const Region<BUF>& g, uint32_t row,
 }
 
 template <int COLS, bool FULL, bool BUF, int AUX = 0>
-__device__ __forceinline__ void st(const Region<BUF>& g, uint32_t row,
+__device__ __forceinline__ void st(const Region<BUF>& g, roff_t<BUF> row,
                                    uint32_t voff, long long avail,
                                    const uint32_t* v)
 {
@@ -263,7 +279,7 @@ static constexpr bool kEncPair = true;
 template <int K, int COLS, bool FULL, bool KEQ, bool BUF>
 __device__ __forceinline__ void encode_body(
     int k, int n, int n_out, const int32_t* __restrict__ twist,
-    const Region<BUF>& gi, uint32_t irs, const Region<BUF>& go, uint32_t ors,
+    const Region<BUF>& gi, roff_t<BUF> irs, const Region<BUF>& go, roff_t<BUF> ors,
     uint32_t voff, long long col, long long avail, int s, const Oor& oor)
 {
     // RELOAD (K = 32): re-read the K input rows every pass (L2 hits after
@@ -283,7 +299,7 @@ __device__ __forceinline__ void encode_body(
         for (int t = 0; t < K; t++) {
             const int row = KEQ ? t : (t < k ? t : k - 1);  // clamp, then mask
             int32_t v[COLS];
-            ld<COLS, FULL, BUF>(gi, static_cast<uint32_t>(row) * irs, vo, avail, v);
+            ld<COLS, FULL, BUF>(gi, static_cast<roff_t<BUF>>(row) * irs, vo, avail, v);
 #pragma unroll
             for (int c = 0; c < COLS; c++)
                 x[c][t] = (KEQ || t < k) ? v[c] : 0;
@@ -373,7 +389,7 @@ __device__ __forceinline__ void encode_body(
                 for (int c = 0; c < COLS; c++)
                     o[c] = static_cast<uint32_t>(y[c][u]);
                 if (!decltype(chk)::value || row < n_out)
-                    st<COLS, FULL, BUF, kAuxSt>(go, static_cast<uint32_t>(row) * ors,
+                    st<COLS, FULL, BUF, kAuxSt>(go, static_cast<roff_t<BUF>>(row) * ors,
                                                 voff, avail, o);
             }
         }
@@ -393,7 +409,7 @@ __device__ __forceinline__ void encode_body(
         for (int t = 0; t < K; t++) {
             const int row = KEQ ? t : (t < k ? t : k - 1);
             uint32_t w[1];
-            ld_dw<1, BUF>(gi, static_cast<uint32_t>(row) * irs, voff, w);
+            ld_dw<1, BUF>(gi, static_cast<roff_t<BUF>>(row) * irs, voff, w);
             xw[t] = (KEQ || t < k) ? w[0] : 0u;
         }
         auto compute_p = [&](int v, int32_t (&y)[COLS][K]) {
@@ -430,7 +446,7 @@ __device__ __forceinline__ void encode_body(
         auto store = [&](int row, uint32_t o) {
             if (!decltype(chk)::value || row < n_out) {
                 const uint32_t w[1] = {o};
-                st_dw<1, BUF, kAuxSt>(go, static_cast<uint32_t>(row) * ors, voff, w);
+                st_dw<1, BUF, kAuxSt>(go, static_cast<roff_t<BUF>>(row) * ors, voff, w);
             }
         };
         int v = 0;
@@ -484,15 +500,19 @@ encode_fnt_kernel(
     const long long col = col0 + static_cast<long long>(threadIdx.x) * COLS;
     const Region<BUF> gi(data + s * dss, iext);
     const Region<BUF> go(out + s * oss, oext);
+    // the flat form has no extents: iext / oext carry the upper halves of its
+    // row strides (enc_launch), and the signature stays that of the buffer
+    // forms
+    const roff_t<BUF> irs_ = row_stride<BUF>(irs, iext), ors_ = row_stride<BUF>(ors, oext);
     const uint32_t voff = static_cast<uint32_t>(col * 2);
     if (col0 + kBlock * COLS <= words) {  // block-uniform
-        encode_body<K, COLS, true, KEQ, BUF>(k, n, n_out, twist, gi, irs, go,
-                                             ors, voff, col, COLS, s, oor);
+        encode_body<K, COLS, true, KEQ, BUF>(k, n, n_out, twist, gi, irs_, go,
+                                             ors_, voff, col, COLS, s, oor);
     } else {
         if (col >= words)
             return;
-        encode_body<K, COLS, false, KEQ, BUF>(k, n, n_out, twist, gi, irs, go,
-                                              ors, voff, col, words - col, s,
+        encode_body<K, COLS, false, KEQ, BUF>(k, n, n_out, twist, gi, irs_, go,
+                                              ors_, voff, col, words - col, s,
                                               oor);
     }
 }
@@ -877,7 +897,7 @@ __device__ __forceinline__ void matrix_load(const IdOf& id_of,
 #pragma unroll
     for (int j = 0; j < KP; j++) {
         Region<BUF> g[2] = {g0, g0};
-        uint32_t off[2];
+        roff_t<BUF> off[2];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int id = id_of(2 * j + h);
@@ -887,7 +907,7 @@ __device__ __forceinline__ void matrix_load(const IdOf& id_of,
             if constexpr (BUF)
                 g[h].r = lo ? g0.r : g1.r;
             g[h].p = lo ? g0.p : g1.p;
-            off[h] = static_cast<uint32_t>(lo ? id * src.rs0 * 2
+            off[h] = static_cast<roff_t<BUF>>(lo ? id * src.rs0 * 2
                                               : (id - src.split) * src.rs1 * 2);
         }
         if constexpr (FULL && COLS % 2 == 0) {
@@ -918,7 +938,7 @@ __device__ __forceinline__ void matrix_load(const IdOf& id_of,
 template <int KP, int COLS, bool FULL, bool BUF>
 __device__ __forceinline__ void matrix_compute(
     const MatLayout& L, const int32_t* __restrict__ M,
-    const int32_t (&xp)[COLS][KP], const Region<BUF>& go, uint32_t ors,
+    const int32_t (&xp)[COLS][KP], const Region<BUF>& go, roff_t<BUF> ors,
     uint32_t voff, long long col, long long col0, long long avail, int s,
     int n_lm, const int* s_i, const uint32_t* s_col, const Oor& out_oor,
     const int32_t* __restrict__ rowmap)
@@ -984,7 +1004,7 @@ __device__ __forceinline__ void matrix_compute(
                 o[c] = fix16(y[c]);
             }
         }
-        st<COLS, FULL, BUF, kAuxSt>(go, static_cast<uint32_t>(rowmap[t]) * ors, voff, avail,
+        st<COLS, FULL, BUF, kAuxSt>(go, static_cast<roff_t<BUF>>(rowmap[t]) * ors, voff, avail,
                                     o);
     }
 }
@@ -1008,7 +1028,7 @@ struct VerRows {
 template <int KP, int COLS, bool FULL, bool BUF>
 __device__ __forceinline__ void matrix_compute_verify(
     const MatLayout& L, const int32_t* __restrict__ M,
-    const int32_t (&xp)[COLS][KP], const Region<BUF>& go, uint32_t ors,
+    const int32_t (&xp)[COLS][KP], const Region<BUF>& go, roff_t<BUF> ors,
     uint32_t voff, long long col, long long col0, long long avail, int s,
     int n_lm, const int* s_i, const uint32_t* s_col, const Oor& out_oor,
     const int32_t* __restrict__ rowmap, const VerRows<BUF>* vr)
@@ -1032,7 +1052,7 @@ __device__ __forceinline__ void matrix_compute_verify(
             if constexpr (BUF)
                 g.r = lo ? vr->g0.r : vr->g1.r;
             g.p = lo ? vr->g0.p : vr->g1.p;
-            const uint32_t off = static_cast<uint32_t>(
+            const roff_t<BUF> off = static_cast<roff_t<BUF>>(
                 lo ? id * vr->src.rs0 * 2 : (id - vr->src.split) * vr->src.rs1 * 2);
             ld<COLS, FULL, BUF, kAuxLd>(g, off, voff, avail, sv);
         }
@@ -1789,16 +1809,6 @@ static int grid_for(long long words, int cols, int n_stripes, int* tiles)
     return 0;
 }
 
-// byte extent of `rows` rows of `words` u16 at row stride rs (elements);
-// 0 when it does not fit a 32-bit buffer range
-static uint32_t extent(long long rows, long long rs, long long words)
-{
-    if (rows <= 0)
-        return 0;
-    const long long e = ((rows - 1) * rs + words) * 2;
-    return e > 0 && e < 0x7fffffffLL ? static_cast<uint32_t>(e) : 0;
-}
-
 template <int K, int COLS, bool KEQ, bool BUF>
 static int enc_launch(int k, int n, int n_out, const int32_t* tw,
                       const uint16_t* data, long long dss, long long drs,
@@ -1808,10 +1818,17 @@ static int enc_launch(int k, int n, int n_out, const int32_t* tw,
     int tiles;
     if (grid_for(words, COLS, S, &tiles))
         return -1;
+    // (flat: the row strides' upper halves in the extents' place)
+    const unsigned long long ib = static_cast<unsigned long long>(drs) * 2,
+                             ob = static_cast<unsigned long long>(out.rs) * 2;
+    if constexpr (!BUF) {
+        iext = static_cast<uint32_t>(ib >> 32);
+        oext = static_cast<uint32_t>(ob >> 32);
+    }
     hipLaunchKernelGGL((encode_fnt_kernel<K, COLS, KEQ, BUF>), dim3(tiles * S),
                        dim3(kBlock), 0, st, k, n, n_out, tw, data, dss,
-                       static_cast<uint32_t>(drs * 2), iext, out.base, out.ss,
-                       static_cast<uint32_t>(out.rs * 2), oext, words, tiles,
+                       static_cast<uint32_t>(ib), iext, out.base, out.ss,
+                       static_cast<uint32_t>(ob), oext, words, tiles,
                        oor);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1832,7 +1849,7 @@ int launch_encode_fnt(int k, int n, int n_out, const int32_t* d_twist,
     const int K = static_cast<int>(ceil2(static_cast<uint32_t>(k)));
     const bool a2 = aligned_for(2, data, dss, drs, out.ss, out.rs) &&
                     (reinterpret_cast<uintptr_t>(out.base) % 4) == 0;
-    const uint32_t ie = extent(k, drs, words), oe = extent(n_out, out.rs, words);
+    const uint32_t ie = row_extent(k, drs, words), oe = row_extent(n_out, out.rs, words);
     if (!ie || !oe) {
         // stripes wider than a 31-bit buffer range: flat addressing
         switch (K) {
@@ -2116,8 +2133,8 @@ static bool rows_aligned(int cols, const RowSrc& src, const RowDst& dst)
 
 static MatExt mat_ext(const RowSrc& src, int R, const RowDst& dst, long long words)
 {
-    return MatExt{extent(src.rows0, src.rs0, words), extent(src.rows1, src.rs1, words),
-                  extent(R, dst.rs, words), 0};
+    return MatExt{row_extent(src.rows0, src.rs0, words), row_extent(src.rows1, src.rs1, words),
+                  row_extent(R, dst.rs, words), 0};
 }
 
 // what matrix_route reads of a launch

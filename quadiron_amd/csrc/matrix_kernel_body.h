@@ -126,7 +126,7 @@
         __syncthreads();
         n_lm = n_rm;
     }
-    const uint32_t ors = static_cast<uint32_t>(dst.rs * 2);
+    const roff_t<BUF> ors = static_cast<roff_t<BUF>>(dst.rs * 2);
     if constexpr (BOTH) {
         // a slow tile records no output marks here, matrix_redo_kernel_both
         // does, from fully restored inputs (block-uniform)

@@ -4,6 +4,8 @@
 // so the names a plan reports are the kernels that run.
 #pragma once
 
+#include <stdint.h>
+
 #include <string>
 
 #include "matrix_pack.h"  // MatLayout
@@ -13,6 +15,18 @@ namespace qi {
 // columns per OOR route tile: a multiple of every block width (256*COLS);
 // the matrix cores take whole tiles, the dot2 kernel the tail
 constexpr int kRouteTile = 1024;
+
+// Byte extent of a stripe's row region: `rows` rows of `words` u16 at row
+// stride rs (elements), as a buffer resource takes it; 0 when the region does
+// not fit a 31-bit range (or has no rows), which sends the launch to the flat
+// kernels.  In 128 bits: a product past 2^63 must not wrap into the range
+inline uint32_t row_extent(long long rows, long long rs, long long words)
+{
+    if (rows <= 0)
+        return 0;
+    const __int128 e = (static_cast<__int128>(rows - 1) * rs + words) * 2;
+    return e > 0 && e < 0x7fffffffLL ? static_cast<uint32_t>(e) : 0;
+}
 
 // pair columns (KP) of the dot2 kernel's packed rows for kin inputs
 inline int matrix_kp(int kin)

@@ -514,3 +514,84 @@ def craft_received(k, m, sys_, ids, cols, rng, n_spread=8):
     if nrep:
         d[:, ~kept] = rng.integers(0, 65536, (k, nrep))
     return d.astype(np.uint16), r, kept, M, meta
+
+
+# ------------------------------------------------------------------------
+# Wide row layouts.  A [S, rows, P] tensor of the device C-ABI may have any
+# positive strides; in a fragment-major layout (every fragment holds all its
+# stripes back to back: stripe stride P, row stride >= S * P) a stripe's row
+# region can span GiB, and the library then leaves the buffer-resource
+# kernels for the flat ones.
+
+FILL = 0x5A5A   # the word of a backing wherever no row lives
+
+
+def row_extent(rows, rs, words):
+    """The library's rule (row_extent, quadiron_amd/csrc/matrix_route.h;
+    tests/golden/row_extent.txt pins both): the byte extent of `rows` rows of
+    `words` u16 at row stride rs, 0 when it does not fit a 31-bit buffer
+    range -- then every kernel of the launch is a flat one."""
+    if rows <= 0:
+        return 0
+    e = ((rows - 1) * rs + words) * 2
+    return e if 0 < e < 0x7fffffff else 0
+
+
+def strided_rows(S, rows, P, rs, ss):
+    """(backing, view): a 1-D int16 device tensor of (rows - 1) * rs +
+    (S - 1) * ss + P words filled with FILL, and its [S, rows, P] view with
+    strides (ss, rs, 1).  The backing covers the region from word 0 on, so
+    an offset that lost its upper bits still lands inside the allocation."""
+    import torch
+    n = (rows - 1) * rs + (S - 1) * ss + P
+    backing = torch.full((n,), FILL, dtype=torch.int16, device="cuda")
+    return backing, torch.as_strided(backing, (S, rows, P), (ss, rs, 1))
+
+
+def backing_is_fill(backing, chunk=1 << 27):
+    """Whether every word of the backing is FILL, compared on the device in
+    chunks (temporaries of 128 MiB)."""
+    import torch
+    bad = torch.zeros((), dtype=torch.bool, device=backing.device)
+    for lo in range(0, backing.numel(), chunk):
+        bad |= (backing[lo:lo + chunk] != FILL).any()
+    return not bool(bad.item())
+
+
+def wide_rs(cls, rows, P):
+    """The smallest row stride (u16 words, a multiple of 4) that puts `rows`
+    rows of P words into a region class:
+      N   narrow: two stripes side by side, rs = 2 P
+      B   the top of the buffer range: extent within 4096 bytes below 2^31 - 1
+          (or within one stride step, 8 (rows - 1) bytes, where that is more)
+      F2  extent in [2^31, 2^31 + 2^20): flat kernels, row offsets below 4 GiB
+      F4  (rows - 1) * rs * 2 >= 2^32 + 2^28: flat, the upper rows past 4 GiB
+          (rows = 2: the row stride itself past 2^32 bytes)
+    and the extent the library must see for it (asserted)."""
+    assert rows >= 2 or cls == "N", "one row cannot be wide"
+    up4 = lambda v: -(-v // 4) * 4
+    if cls == "N":
+        rs = up4(2 * P)
+        assert row_extent(rows, rs, P) != 0
+        return rs
+    if cls == "B":
+        rs = up4(-(-((1 << 31) - 1 - 4096 - 2 * P) // (2 * (rows - 1))))
+        if ((rows - 1) * rs + P) * 2 >= (1 << 31) - 1:
+            # a step of 4 words moves the extent by 8 (rows - 1) bytes: past
+            # 513 rows a stride can jump the 4096-byte window; then the
+            # largest stride below the limit, as close as the layout gets
+            rs -= 4
+        e = ((rows - 1) * rs + P) * 2
+        assert (1 << 31) - 1 - max(4096, 8 * (rows - 1)) <= e < (1 << 31) - 1, (rows, P, e)
+        assert row_extent(rows, rs, P) == e
+    elif cls == "F2":
+        rs = up4(-(-((1 << 31) - 2 * P) // (2 * (rows - 1))))
+        e = ((rows - 1) * rs + P) * 2
+        assert (1 << 31) <= e < (1 << 31) + (1 << 20), (rows, P, e)
+        assert row_extent(rows, rs, P) == 0
+    else:
+        assert cls == "F4"
+        rs = up4(-(-((1 << 32) + (1 << 28)) // (2 * (rows - 1))))
+        assert (rows - 1) * rs * 2 >= (1 << 32) + (1 << 28)
+        assert row_extent(rows, rs, P) == 0
+    return rs

@@ -46,6 +46,58 @@ def test_pinned_routes(exe):
         assert (err, got) == (0, want), inp
 
 
+def test_flat_routes_pinned():
+    """buf = 0 routes are pinned at every KP of the dot2 kernel, as an encode,
+    a decode with marks and a repair."""
+    flat = {}
+    with open(os.path.join(HERE, "golden", "matrix_routes.txt")) as f:
+        for ln in f:
+            if not ln.startswith("#") and ln.split()[3] == "0":
+                flat.setdefault(ln.split(" | ")[1].strip(), []).append(ln)
+    for kp in (2, 4, 8, 16, 32, 64, 128):
+        assert f"matrix_kernel<{kp}, 1, false> (tail)" in flat, kp
+        assert f"matrix_kernel<{kp}, 1, false> (tail) + matrix_redo_kernel" in flat, kp
+        assert (f"matrix_kernel_both<{kp}, 1, false> (tail) + matrix_redo_kernel_both"
+                in flat), kp
+
+
+def _extent_table():
+    rows = []
+    with open(os.path.join(HERE, "golden", "row_extent.txt")) as f:
+        for ln in f:
+            if not ln.startswith("#"):
+                inp, want = ln.split(" | ")
+                rows.append((tuple(int(v) for v in inp.split()), int(want)))
+    return rows
+
+
+def test_row_extent_boundaries(tmp_path):
+    """row_extent, which decides between the buffer and the flat kernels:
+    2^31 - 2 bytes is an extent, 2^31 is not, no rows give 0, and a product
+    past 2^62 does not wrap into a positive value."""
+    table = _extent_table()
+    args = {a for a, _ in table}
+    assert {(1, 0, (1 << 30) - 1), (1, 0, 1 << 30), (0, 1024, 1024), (-1, 1024, 1024),
+            (5, 1 << 62, 100)} <= args
+    assert dict(table)[(1, 0, (1 << 30) - 1)] == (1 << 31) - 2
+    out = str(tmp_path / "test_row_extent")
+    subprocess.check_call(["g++", "-std=c++20", "-O1", "-Wall", "-Werror",
+                           os.path.join(HERE, "host", "test_row_extent.cpp"), "-o", out])
+    res = subprocess.run([out], input="".join("%d %d %d\n" % a for a, _ in table),
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    got = [int(v) for v in res.stdout.split()]
+    assert got == [w for _, w in table], list(zip(table, got))
+
+
+def test_row_extent_python_rule():
+    """qi_testlib.row_extent, the rule the wide-row GPU tests state their
+    preconditions with, gives the same table."""
+    from qi_testlib import row_extent
+    for a, want in _extent_table():
+        assert row_extent(*a) == want, a
+
+
 def _kernel_symbols(path):
     # (as tests/test_kernel_names.py)
     out = subprocess.run(["nm", "-DC", path], check=True, capture_output=True,
