@@ -234,8 +234,6 @@ class RsFnt {
                         const std::vector<const uint8_t*>& rows,
                         const std::vector<const Properties*>& props,
                         uint8_t* const* outputs, size_t words, size_t offset);
-    bool select_fragments(const std::vector<int>& present,
-                          std::vector<int>& ids) const;
     // the two-slot pinned pipeline behind the stream API and the blocks
     // wider than one chunk: read(h, pitch, cont) fills the next chunk's
     // input rows (pitch bytes apart) and returns the bytes per row (0: no

@@ -18,6 +18,7 @@
 
 #include "../../include/qi_fec.hpp"
 #include "../../include/qi_gpu.h"
+#include "fec_stage.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
 
@@ -114,6 +115,41 @@ void check_rc(int rc, const char* what)
                                  std::to_string(rc));
 }
 
+void reserve(DevBuf& b, size_t bytes)
+{
+    if (!b.reserve(bytes))
+        throw std::runtime_error("RsFnt: device allocation failed");
+}
+
+void h2d(void* dst, const void* src, size_t bytes, hipStream_t s)
+{
+    check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), "H2D");
+}
+
+void d2h(void* dst, const void* src, size_t bytes, hipStream_t s)
+{
+    check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s), "D2H");
+}
+
+// the bucket counts back from the device (synchronises s): the largest
+size_t read_max(std::vector<uint32_t>& cnt, const void* dcnt, hipStream_t s)
+{
+    d2h(cnt.data(), dcnt, cnt.size() * 4, s);
+    check(hipStreamSynchronize(s), "sync");
+    return *std::max_element(cnt.begin(), cnt.end());
+}
+
+void upload_marks(const stage::PackedMarks& pm, uint32_t* dcnt, uint32_t* dent, hipStream_t s)
+{
+    h2d(dcnt, pm.counts.data(), pm.counts.size() * 4, s);
+    h2d(dent, pm.entries.data(), pm.entries.size() * 4, s);
+}
+
+stage::FragMap frag_map(const RsFnt& f)
+{
+    return stage::FragMap(f.type, f.n_data, f.n_outputs);
+}
+
 struct Timer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     uint64_t usec() const
@@ -193,53 +229,35 @@ void RsFnt::encode_columns(qi_plan* pl, const uint8_t* const* data, uint8_t* con
     hipStream_t s = h.stream;
     const size_t P = pad_words(words);
     const size_t no = static_cast<size_t>(pl->n_outputs);
-    size_t cap = 64 + words / 512;
-    check(h.in.reserve(static_cast<size_t>(pl->k) * P * 2) ? hipSuccess : hipErrorOutOfMemory,
-          "alloc");
-    check(h.out.reserve(no * P * 2) ? hipSuccess : hipErrorOutOfMemory, "alloc");
-    check(h.counts.reserve(no * 4) ? hipSuccess : hipErrorOutOfMemory, "alloc");
+    reserve(h.in, static_cast<size_t>(pl->k) * P * 2);
+    reserve(h.out, no * P * 2);
+    reserve(h.counts, no * 4);
     uint16_t* din = static_cast<uint16_t*>(h.in.p);
     uint16_t* dout = static_cast<uint16_t*>(h.out.p);
     uint32_t* dcnt = static_cast<uint32_t*>(h.counts.p);
     for (int t = 0; t < pl->k; t++)
-        check(hipMemcpyAsync(din + t * P, data[t], words * 2,
-                             hipMemcpyHostToDevice, s),
-              "H2D");
+        h2d(din + t * P, data[t], words * 2, s);
     std::vector<uint32_t> cnt(no);
-    for (int attempt = 0; attempt < 2; attempt++) {
-        check(h.entries.reserve(no * cap * 4) ? hipSuccess : hipErrorOutOfMemory,
-              "alloc");
-        check_rc(qi_gpu_oor_clear(dcnt, no, s), "oor_clear");
-        check_rc(qi_gpu_encode(pl, din, 0, static_cast<long long>(P), dout, 0,
-                               static_cast<long long>(P),
-                               static_cast<long long>(words), 1, dcnt,
-                               static_cast<uint32_t*>(h.entries.p),
-                               static_cast<int>(cap), s),
-                 "qi_gpu_encode");
-        check(hipMemcpyAsync(cnt.data(), dcnt, no * 4, hipMemcpyDeviceToHost, s),
-              "D2H");
-        check(hipStreamSynchronize(s), "sync");
-        const uint32_t mx = *std::max_element(cnt.begin(), cnt.end());
-        if (mx <= cap)
-            break;
-        cap = mx;  // adversarial data: re-run with exact capacity
-    }
+    const size_t cap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, no * c * 4);
+            check_rc(qi_gpu_oor_clear(dcnt, no, s), "oor_clear");
+            check_rc(qi_gpu_encode(pl, din, 0, static_cast<long long>(P), dout, 0,
+                                   static_cast<long long>(P), static_cast<long long>(words), 1,
+                                   dcnt, static_cast<uint32_t*>(h.entries.p),
+                                   static_cast<int>(c), s),
+                     "qi_gpu_encode");
+        },
+        [&] { return read_max(cnt, dcnt, s); }, [] {});
     std::vector<uint32_t> ent(no * cap);
-    check(hipMemcpyAsync(ent.data(), h.entries.p, no * cap * 4,
-                         hipMemcpyDeviceToHost, s),
-          "D2H");
+    d2h(ent.data(), h.entries.p, no * cap * 4, s);
     for (size_t i = 0; i < no; i++)
         if (outputs[i])
-            check(hipMemcpyAsync(outputs[i], dout + i * P, words * 2,
-                                 hipMemcpyDeviceToHost, s),
-                  "D2H");
+            d2h(outputs[i], dout + i * P, words * 2, s);
     check(hipStreamSynchronize(s), "sync");
-    for (size_t i = 0; i < no; i++) {
-        uint32_t* b = ent.data() + i * cap;
-        std::sort(b, b + cnt[i]);
-        for (uint32_t e = 0; e < cnt[i]; e++)
-            props[i].add(offset + b[e], OOR_MARK);
-    }
+    for (size_t i = 0; i < no; i++)
+        stage::add_sorted(props[i], ent.data() + i * cap, cnt[i], offset);
 }
 
 void RsFnt::decode_columns(qi_plan* pl, const std::vector<int>& ids,
@@ -255,50 +273,27 @@ void RsFnt::decode_columns(qi_plan* pl, const std::vector<int>& ids,
     const size_t P = pad_words(words);
     const int k = pl->k;
     // OOR marks of the received coded rows inside [offset, offset+words)
-    std::vector<std::vector<uint32_t>> marks(k);
-    size_t cap = 1;
-    for (int i = 0; i < k; i++) {
-        if (!props[i])
-            continue;
-        for (auto const& it : props[i]->get_map())
-            if (it.first >= offset && it.first < offset + words)
-                marks[i].push_back(static_cast<uint32_t>(it.first - offset));
-        cap = std::max(cap, marks[i].size());
-    }
-    std::vector<uint32_t> hcnt(k), hent(static_cast<size_t>(k) * cap, 0);
-    for (int i = 0; i < k; i++) {
-        hcnt[i] = static_cast<uint32_t>(marks[i].size());
-        std::copy(marks[i].begin(), marks[i].end(), hent.begin() + i * cap);
-    }
-    std::vector<uint16_t> hids(k);
-    for (int i = 0; i < k; i++)
-        hids[i] = static_cast<uint16_t>(ids[i]);
+    const stage::PackedMarks pm = stage::pack_marks(props, offset, words);
+    const size_t cap = pm.cap;
+    std::vector<uint16_t> hids(ids.begin(), ids.end());
     const size_t ctx_bytes =
         qi_gpu_decode_ctx_bytes(pl, 1, static_cast<long long>(words));
-    const size_t cnt_off = 0, ent_off = 64 * ((k * 4 + 63) / 64);
-    if (!h.in.reserve(static_cast<size_t>(k) * P * 2) ||
-        !h.out.reserve(static_cast<size_t>(k) * P * 2) ||
-        !h.counts.reserve(ent_off + hent.size() * 4) ||
-        !h.ids.reserve(k * 2) || !h.ctx.reserve(ctx_bytes))
-        throw std::runtime_error("RsFnt: device allocation failed");
+    // counts buffer: counts, entries
+    const auto off = stage::layout({size_t(k) * 4, pm.entries.size() * 4});
+    reserve(h.in, static_cast<size_t>(k) * P * 2);
+    reserve(h.out, static_cast<size_t>(k) * P * 2);
+    reserve(h.counts, off[2]);
+    reserve(h.ids, k * 2);
+    reserve(h.ctx, ctx_bytes);
     uint16_t* din = static_cast<uint16_t*>(h.in.p);
     uint16_t* dout = static_cast<uint16_t*>(h.out.p);
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    for (int i = 0; i < k; i++)
-        check(hipMemcpyAsync(din + i * P, rows[i], words * 2,
-                             hipMemcpyHostToDevice, s),
-              "H2D");
-    check(hipMemcpyAsync(dcb + cnt_off, hcnt.data(), k * 4, hipMemcpyHostToDevice,
-                         s),
-          "H2D");
-    check(hipMemcpyAsync(dcb + ent_off, hent.data(), hent.size() * 4,
-                         hipMemcpyHostToDevice, s),
-          "H2D");
-    check(hipMemcpyAsync(h.ids.p, hids.data(), k * 2, hipMemcpyHostToDevice, s),
-          "H2D");
     // received rows staged by position; OOR buckets by position
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + cnt_off);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + ent_off);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h.counts.p) + off[0]);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h.counts.p) + off[1]);
+    for (int i = 0; i < k; i++)
+        h2d(din + i * P, rows[i], words * 2, s);
+    upload_marks(pm, dcnt, dent, s);
+    h2d(h.ids.p, hids.data(), k * 2, s);
     check_rc(qi_gpu_decode_ctx_packed(pl, static_cast<uint16_t*>(h.ids.p), hids.data(), 1,
                                       dcnt, dent, static_cast<int>(cap),
                                       static_cast<long long>(words), h.ctx.p, s),
@@ -310,9 +305,7 @@ void RsFnt::decode_columns(qi_plan* pl, const std::vector<int>& ids,
              "decode");
     for (int t = 0; t < k; t++)
         if (outputs[t])
-            check(hipMemcpyAsync(outputs[t], dout + t * P, words * 2,
-                                 hipMemcpyDeviceToHost, s),
-                  "D2H");
+            d2h(outputs[t], dout + t * P, words * 2, s);
     check(hipStreamSynchronize(s), "sync");
     if (qi_gpu_take_error(pl))
         throw std::runtime_error("RsFnt: OOR marks lost (bucket capacity)");
@@ -341,23 +334,24 @@ void RsFnt::encode_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     total_enc_usec += tm.usec();
 }
 
-bool RsFnt::select_fragments(const std::vector<int>& present,
-                             std::vector<int>& ids) const
+namespace {
+
+// the k selected fragments by position: where each one comes from (`data`
+// or `coded`, by slot) and, for a coded one, its marks
+template <typename T, typename R>
+void selected_rows(const stage::FragMap& map, const std::vector<int>& ids,
+                   const std::vector<T>& data, const std::vector<T>& coded,
+                   std::vector<Properties>& coded_props, std::vector<R>& rows,
+                   std::vector<const Properties*>& props)
 {
-    // first k present, data before parities: src/fec_base.h:1199-1236
-    ids.clear();
-    const bool sys = type == FecType::SYSTEMATIC;
-    if (sys)
-        for (unsigned i = 0; i < n_data; i++)
-            if (present[i])
-                ids.push_back(static_cast<int>(i));
-    for (unsigned i = 0; i < n_outputs && ids.size() < n_data; i++) {
-        const unsigned j = sys ? n_data + i : i;
-        if (present[j])
-            ids.push_back(static_cast<int>(j));
+    for (size_t i = 0; i < ids.size(); i++) {
+        const auto fs = map.slot(ids[i]);
+        rows[i] = map.pick(ids[i], data, coded);
+        props[i] = fs.is_data ? nullptr : &coded_props[fs.slot];
     }
-    return ids.size() == n_data;
 }
+
+}  // namespace
 
 bool RsFnt::decode_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                    std::vector<uint8_t*>& parities_bufs,
@@ -367,19 +361,12 @@ bool RsFnt::decode_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                    size_t block_size_bytes)
 {
     // src/fec_base.h:1177-1321
-    const bool sys = type == FecType::SYSTEMATIC;
-    std::vector<int> present(code_len);
-    for (unsigned i = 0; i < code_len; i++)
-        present[i] = missing_idxs[i] ? 0 : 1;
-    if (sys) {
-        unsigned nd = 0;
-        for (unsigned i = 0; i < n_data; i++)
-            nd += present[i];
-        if (nd == n_data)
-            return true;  // data in clear (src/fec_base.h:1208-1211)
-    }
+    const stage::FragMap map = frag_map(*this);
+    const std::vector<int> present = map.present(missing_idxs);
+    if (map.data_in_clear(present))
+        return true;
     std::vector<int> ids;
-    if (!select_fragments(present, ids))
+    if (!map.select(present, ids))
         return false;
     // DecodeContext sorts every input property list (src/fec_context.h:93-97)
     for (auto& p : parities_props)
@@ -387,16 +374,7 @@ bool RsFnt::decode_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     reset_stats_dec();
     std::vector<const uint8_t*> rows(n_data);
     std::vector<const Properties*> props(n_data, nullptr);
-    for (unsigned i = 0; i < n_data; i++) {
-        const int id = ids[i];
-        if (sys && id < static_cast<int>(n_data)) {
-            rows[i] = data_bufs[id];
-        } else {
-            const int slot = sys ? id - static_cast<int>(n_data) : id;
-            rows[i] = parities_bufs[slot];
-            props[i] = &parities_props[slot];
-        }
-    }
+    selected_rows(map, ids, data_bufs, parities_bufs, parities_props, rows, props);
     std::vector<uint8_t*> outs(n_data, nullptr);
     for (unsigned t = 0; t < n_data; t++)
         if (wanted_idxs[t])
@@ -428,7 +406,8 @@ size_t read_full(std::istream* is, uint8_t* p, size_t len)
 
 }  // namespace
 
-// ---- fused repair (single chunk; qi_gpu_repair_ctx / qi_gpu_repair) ----
+// ---- fused repair and verify (single chunk; qi_gpu_repair_ctx, then
+// qi_gpu_repair / qi_gpu_verify) ----
 bool RsFnt::repair_supported(size_t n_targets, size_t block_size_bytes) const
 {
     const size_t words = block_size_bytes / word_size;
@@ -441,6 +420,56 @@ bool RsFnt::repair_supported(size_t n_targets, size_t block_size_bytes) const
     return static_cast<size_t>(code_len) * pad_words(words) * 2 <= (size_t{256} << 20);
 }
 
+namespace {
+
+// What a repair and a verify stage alike: the fragments `upload` in their own
+// row slots of h.in (row = fragment id: the data rows first when systematic,
+// then the coded rows), the coded ones' OOR buckets by slot at the head of
+// h.counts, followed by `tail_bytes` for the caller's own results; h.ids and
+// h.ctx reserved.
+struct Staged {
+    size_t P;
+    uint16_t *din, *dcoded;
+    uint32_t *dcnt, *dent, *dtail;
+    stage::PackedMarks pm;  // host side of the buckets: alive until the sync
+};
+
+Staged stage_fragments(qi_plan* pl, const stage::FragMap& map, const std::vector<int>& upload,
+                       const std::vector<uint8_t*>& data_bufs,
+                       const std::vector<uint8_t*>& parities_bufs,
+                       const std::vector<Properties>& parities_props, size_t words,
+                       size_t tail_bytes, size_t n_ids, size_t ctx_bytes)
+{
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    Staged st;
+    const size_t P = st.P = pad_words(words), no = map.n_outputs;
+    std::vector<const Properties*> marked(no, nullptr);
+    for (int id : upload) {
+        const auto fs = map.slot(id);
+        if (!fs.is_data)
+            marked[fs.slot] = &parities_props[fs.slot];
+    }
+    st.pm = stage::pack_marks(marked, 0, words);
+    const auto off = stage::layout({no * 4, st.pm.entries.size() * 4, tail_bytes});
+    reserve(h.in, (map.data_rows() + no) * P * 2);
+    reserve(h.counts, off[3]);
+    reserve(h.ids, n_ids * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    st.din = static_cast<uint16_t*>(h.in.p);
+    st.dcoded = st.din + map.data_rows() * P;
+    st.dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
+    st.dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
+    st.dtail = reinterpret_cast<uint32_t*>(dcb + off[2]);
+    for (int id : upload)
+        h2d(st.din + id * P, map.pick(id, data_bufs, parities_bufs), words * 2, s);
+    upload_marks(st.pm, st.dcnt, st.dent, s);
+    return st;
+}
+
+}  // namespace
+
 bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                    std::vector<uint8_t*>& parities_bufs,
                                    std::vector<Properties>& parities_props,
@@ -450,252 +479,163 @@ bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                    std::vector<Properties>& out_props,
                                    size_t block_size_bytes)
 {
-    const bool sys = type == FecType::SYSTEMATIC;
+    // validate
+    const stage::FragMap map = frag_map(*this);
     const size_t R = targets.size();
     if (!repair_supported(R, block_size_bytes))
         throw std::invalid_argument("RsFnt::repair_blocks_vertical: unsupported shape");
     if (out_bufs.size() < R)
         throw std::invalid_argument("RsFnt::repair_blocks_vertical: out_bufs");
-    std::vector<int> present(code_len);
-    for (unsigned i = 0; i < code_len; i++)
-        present[i] = missing_idxs[i] ? 0 : 1;
+    const std::vector<int> present = map.present(missing_idxs);
     for (int t : targets)
         if (t < 0 || t >= static_cast<int>(code_len) || present[t])
             throw std::invalid_argument("RsFnt::repair_blocks_vertical: target not missing");
     std::vector<int> ids;
-    if (!select_fragments(present, ids))
+    if (!map.select(present, ids))
         return false;
     for (auto& p : parities_props)
         p.sort();
     out_props.assign(R, Properties());
     const size_t words = block_size_bytes / word_size;
-    const size_t P = pad_words(words);
     const int k = static_cast<int>(n_data);
-    const size_t no = n_outputs;
     qi_plan* pl = plan_;
     HostState& h = pl->host;
     hipStream_t s = h.stream;
-    // the received rows in their own slots: data rows (systematic) first,
-    // then the coded rows; OOR buckets of the coded rows by slot
-    const size_t data_rows = sys ? n_data : 0;
-    std::vector<std::vector<uint32_t>> marks(no);
-    size_t cap = 1;
-    for (int i = 0; i < k; i++) {
-        const int id = ids[i];
-        if (sys && id < k)
-            continue;
-        const size_t slot = sys ? id - k : id;
-        for (auto const& it : parities_props[slot].get_map())
-            if (it.first < words)
-                marks[slot].push_back(static_cast<uint32_t>(it.first));
-        cap = std::max(cap, marks[slot].size());
-    }
-    std::vector<uint32_t> hcnt(no, 0), hent(no * cap, 0);
-    for (size_t i = 0; i < no; i++) {
-        hcnt[i] = static_cast<uint32_t>(marks[i].size());
-        std::copy(marks[i].begin(), marks[i].end(), hent.begin() + i * cap);
-    }
-    std::vector<uint16_t> hids(k + R);
-    for (int i = 0; i < k; i++)
-        hids[i] = static_cast<uint16_t>(ids[i]);
-    for (size_t j = 0; j < R; j++)
-        hids[k + j] = static_cast<uint16_t>(targets[j]);
     const size_t ctx_bytes = qi_gpu_repair_ctx_bytes(pl, static_cast<int>(R), 1,
                                                      static_cast<long long>(words));
     if (ctx_bytes == 0)
         throw std::invalid_argument("RsFnt::repair_blocks_vertical: unsupported shape");
-    size_t ocap = 64 + words / 512;
-    // counts buffer: input counts, input entries, output counts
-    const size_t ent_off = 64 * ((no * 4 + 63) / 64);
-    const size_t oc_off = ent_off + 64 * ((hent.size() * 4 + 63) / 64);
-    if (!h.in.reserve((data_rows + no) * P * 2) || !h.out.reserve(R * P * 2) ||
-        !h.counts.reserve(oc_off + R * 4) || !h.ids.reserve((k + R) * 2) ||
-        !h.ctx.reserve(ctx_bytes))
-        throw std::runtime_error("RsFnt: device allocation failed");
-    uint16_t* din = static_cast<uint16_t*>(h.in.p);
-    uint16_t* dcoded = din + data_rows * P;
+    // stage: the k selected rows, their buckets, then the output counts
+    reserve(h.out, R * pad_words(words) * 2);
+    const Staged st = stage_fragments(pl, map, ids, data_bufs, parities_bufs, parities_props,
+                                      words, R * 4, k + R, ctx_bytes);
+    const long long P = static_cast<long long>(st.P);
+    const int cap = static_cast<int>(st.pm.cap);
     uint16_t* dout = static_cast<uint16_t*>(h.out.p);
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + ent_off);
-    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + oc_off);
-    for (int i = 0; i < k; i++) {
-        const int id = ids[i];
-        const bool d = sys && id < k;
-        const uint8_t* src = d ? data_bufs[id] : parities_bufs[sys ? id - k : id];
-        uint16_t* dst = d ? din + id * P : dcoded + (sys ? id - k : id) * P;
-        check(hipMemcpyAsync(dst, src, words * 2, hipMemcpyHostToDevice, s), "H2D");
-    }
-    check(hipMemcpyAsync(dcnt, hcnt.data(), no * 4, hipMemcpyHostToDevice, s), "H2D");
-    check(hipMemcpyAsync(dent, hent.data(), hent.size() * 4, hipMemcpyHostToDevice, s), "H2D");
-    check(hipMemcpyAsync(h.ids.p, hids.data(), (k + R) * 2, hipMemcpyHostToDevice, s), "H2D");
+    uint32_t* docnt = st.dtail;
+    std::vector<uint16_t> hids(ids.begin(), ids.end());
+    hids.insert(hids.end(), targets.begin(), targets.end());
+    h2d(h.ids.p, hids.data(), (k + R) * 2, s);
     const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
-    check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, dcnt, dent,
-                               static_cast<int>(cap), static_cast<long long>(words), h.ctx.p, s),
+    check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, st.dcnt, st.dent, cap,
+                               static_cast<long long>(words), h.ctx.p, s),
              "repair context");
+    // launch (no error drain between the attempts: the sticky error is read
+    // once, after the rows are back)
     std::vector<uint32_t> ocnt(R);
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if (!h.entries.reserve(R * ocap * 4))
-            throw std::runtime_error("RsFnt: device allocation failed");
-        check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
-        check_rc(qi_gpu_repair(pl, h.ctx.p, static_cast<int>(R), din, 0,
-                               static_cast<long long>(P), dcoded, 0, static_cast<long long>(P),
-                               dcnt, dent, static_cast<int>(cap), dout, 0,
-                               static_cast<long long>(P), docnt,
-                               static_cast<uint32_t*>(h.entries.p), static_cast<int>(ocap),
-                               static_cast<long long>(words), 1, s),
-                 "repair");
-        check(hipMemcpyAsync(ocnt.data(), docnt, R * 4, hipMemcpyDeviceToHost, s), "D2H");
-        check(hipStreamSynchronize(s), "sync");
-        const uint32_t mx = *std::max_element(ocnt.begin(), ocnt.end());
-        if (mx <= ocap)
-            break;
-        ocap = mx;  // adversarial data: re-run with exact capacity
-    }
+    const size_t ocap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, R * c * 4);
+            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+            check_rc(qi_gpu_repair(pl, h.ctx.p, static_cast<int>(R), st.din, 0, P, st.dcoded, 0,
+                                   P, st.dcnt, st.dent, cap, dout, 0, P, docnt,
+                                   static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                   static_cast<long long>(words), 1, s),
+                     "repair");
+        },
+        [&] { return read_max(ocnt, docnt, s); }, [] {});
+    // collect
     std::vector<uint32_t> ent(R * ocap);
-    check(hipMemcpyAsync(ent.data(), h.entries.p, R * ocap * 4, hipMemcpyDeviceToHost, s),
-          "D2H");
+    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
     for (size_t j = 0; j < R; j++)
         if (out_bufs[j])
-            check(hipMemcpyAsync(out_bufs[j], dout + j * P, words * 2, hipMemcpyDeviceToHost, s),
-                  "D2H");
+            d2h(out_bufs[j], dout + j * st.P, words * 2, s);
     check(hipStreamSynchronize(s), "sync");
     if (qi_gpu_take_error(pl))
         throw std::runtime_error("RsFnt: repair failed (bad ids or OOR bucket capacity)");
-    for (size_t j = 0; j < R; j++) {
-        uint32_t* b = ent.data() + j * ocap;
-        std::sort(b, b + ocnt[j]);
-        for (uint32_t e = 0; e < ocnt[j]; e++)
-            out_props[j].add(b[e], OOR_MARK);
-    }
+    for (size_t j = 0; j < R; j++)
+        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
     return true;
 }
 
-// ---- fused verify (single chunk; qi_gpu_repair_ctx / qi_gpu_verify) ----
 bool RsFnt::verify_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                    std::vector<uint8_t*>& parities_bufs,
                                    std::vector<Properties>& parities_props,
                                    std::vector<int>& missing_idxs,
                                    std::vector<VerifyResult>& result, size_t block_size_bytes)
 {
-    const bool sys = type == FecType::SYSTEMATIC;
-    // (the staging of a repair; the group size is checked per group)
+    // validate (the staging of a repair; the group size is checked per group)
+    const stage::FragMap map = frag_map(*this);
     if (!repair_supported(1, block_size_bytes))
         throw std::invalid_argument("RsFnt::verify_blocks_vertical: unsupported shape");
-    std::vector<int> present(code_len);
-    for (unsigned i = 0; i < code_len; i++)
-        present[i] = missing_idxs[i] ? 0 : 1;
+    const std::vector<int> present = map.present(missing_idxs);
     result.assign(code_len, VerifyResult{-1, -1, -1});
     std::vector<int> ids;
-    if (!select_fragments(present, ids))
+    if (!map.select(present, ids))
         return false;
     const int k = static_cast<int>(n_data);
     std::vector<char> basis(code_len, 0);
     for (int id : ids)
         basis[id] = 1;
-    std::vector<int> checks;
-    for (unsigned f = 0; f < code_len; f++)
+    std::vector<int> held, checks;
+    for (unsigned f = 0; f < code_len; f++) {
+        if (present[f])
+            held.push_back(static_cast<int>(f));
         if (present[f] && !basis[f])
             checks.push_back(static_cast<int>(f));
+    }
     if (checks.empty())
         return false;  // fewer than n_data + 1 fragments: nothing to check against
     for (auto& p : parities_props)
         p.sort();
     const size_t words = block_size_bytes / word_size;
-    const size_t P = pad_words(words);
-    const size_t no = n_outputs;
     qi_plan* pl = plan_;
     HostState& h = pl->host;
     hipStream_t s = h.stream;
-    // every present fragment in its own slot (data rows first when
-    // systematic), the coded rows' OOR buckets by slot
-    const size_t data_rows = sys ? n_data : 0;
-    std::vector<std::vector<uint32_t>> marks(no);
-    size_t cap = 1;
-    for (unsigned f = 0; f < code_len; f++) {
-        if (!present[f] || (sys && f < n_data))
-            continue;
-        const size_t slot = sys ? f - n_data : f;
-        for (auto const& it : parities_props[slot].get_map())
-            if (it.first < words)
-                marks[slot].push_back(static_cast<uint32_t>(it.first));
-        cap = std::max(cap, marks[slot].size());
-    }
-    std::vector<uint32_t> hcnt(no, 0), hent(no * cap, 0);
-    for (size_t i = 0; i < no; i++) {
-        hcnt[i] = static_cast<uint32_t>(marks[i].size());
-        std::copy(marks[i].begin(), marks[i].end(), hent.begin() + i * cap);
-    }
     const size_t Rmax = std::min<size_t>({size_t{64}, checks.size(), code_len - n_data});
     const size_t ctx_bytes = qi_gpu_repair_ctx_bytes(pl, static_cast<int>(Rmax), 1,
                                                      static_cast<long long>(words));
     if (ctx_bytes == 0)
         throw std::invalid_argument("RsFnt::verify_blocks_vertical: unsupported shape");
-    size_t wcap = 64 + words / 512;
-    // counts buffer: input counts, input entries, the three results
-    const size_t ent_off = 64 * ((no * 4 + 63) / 64);
-    const size_t res_off = ent_off + 64 * ((hent.size() * 4 + 63) / 64);
-    if (!h.in.reserve((data_rows + no) * P * 2) || !h.counts.reserve(res_off + 3 * Rmax * 4) ||
-        !h.ids.reserve((k + Rmax) * 2) || !h.ctx.reserve(ctx_bytes))
-        throw std::runtime_error("RsFnt: device allocation failed");
-    uint16_t* din = static_cast<uint16_t*>(h.in.p);
-    uint16_t* dcoded = din + data_rows * P;
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + ent_off);
-    uint32_t* dres = reinterpret_cast<uint32_t*>(dcb + res_off);
-    for (unsigned f = 0; f < code_len; f++) {
-        if (!present[f])
-            continue;
-        const bool d = sys && f < n_data;
-        const uint8_t* src = d ? data_bufs[f] : parities_bufs[sys ? f - n_data : f];
-        uint16_t* dst = d ? din + f * P : dcoded + (sys ? f - n_data : f) * P;
-        check(hipMemcpyAsync(dst, src, words * 2, hipMemcpyHostToDevice, s), "H2D");
-    }
-    check(hipMemcpyAsync(dcnt, hcnt.data(), no * 4, hipMemcpyHostToDevice, s), "H2D");
-    check(hipMemcpyAsync(dent, hent.data(), hent.size() * 4, hipMemcpyHostToDevice, s), "H2D");
+    // stage: every present fragment, the buckets, then the three results
+    const Staged st = stage_fragments(pl, map, held, data_bufs, parities_bufs, parities_props,
+                                      words, 3 * Rmax * 4, k + Rmax, ctx_bytes);
+    const long long P = static_cast<long long>(st.P);
+    const int cap = static_cast<int>(st.pm.cap);
+    uint32_t* dres = st.dtail;
     const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
-    std::vector<uint16_t> hids(k + Rmax);
-    for (int i = 0; i < k; i++)
-        hids[i] = static_cast<uint16_t>(ids[i]);
+    std::vector<uint16_t> hids(ids.begin(), ids.end());
+    hids.resize(k + Rmax);
     std::vector<uint32_t> res(3 * Rmax);
-    // groups of at most 64 checks over the same staged rows
+    size_t wcap = 64 + words / 512;
+    // launch: groups of at most 64 checks over the same staged rows
     for (size_t g0 = 0; g0 < checks.size(); g0 += Rmax) {
         const size_t R = std::min(Rmax, checks.size() - g0);
         for (size_t j = 0; j < R; j++)
             hids[k + j] = static_cast<uint16_t>(checks[g0 + j]);
         // (the previous group's kernels read the ids: ordered on the stream,
         // and the host copy is synchronous with respect to hids below)
-        check(hipMemcpyAsync(h.ids.p, hids.data(), (k + R) * 2, hipMemcpyHostToDevice, s), "H2D");
-        check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, dcnt, dent,
-                                   static_cast<int>(cap), static_cast<long long>(words), h.ctx.p,
-                                   s),
+        h2d(h.ids.p, hids.data(), (k + R) * 2, s);
+        check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, st.dcnt, st.dent,
+                                   cap, static_cast<long long>(words), h.ctx.p, s),
                  "verify context");
-        for (int attempt = 0; attempt < 2; attempt++) {
-            const size_t wb = qi_gpu_verify_work_bytes(pl, static_cast<int>(R), 1,
-                                                       static_cast<int>(wcap));
-            if (!wb || !h.entries.reserve(wb))
-                throw std::runtime_error("RsFnt: device allocation failed");
-            check_rc(qi_gpu_verify(pl, h.ctx.p, static_cast<int>(R), dids + k, din, 0,
-                                   static_cast<long long>(P), dcoded, 0,
-                                   static_cast<long long>(P), dcnt, dent, static_cast<int>(cap),
-                                   h.entries.p, static_cast<int>(wcap), dres, dres + R,
-                                   dres + 2 * R, static_cast<long long>(words), 1, s),
-                     "verify");
-            check(hipMemcpyAsync(res.data(), dres, 3 * R * 4, hipMemcpyDeviceToHost, s), "D2H");
-            std::vector<uint32_t> wc(R);
-            check(hipMemcpyAsync(wc.data(), h.entries.p, R * 4, hipMemcpyDeviceToHost, s), "D2H");
-            check(hipStreamSynchronize(s), "sync");
-            const uint32_t mx = *std::max_element(wc.begin(), wc.end());
-            if (mx <= wcap)
-                break;
-            // adversarial data: more recomputed 65536 values than the work
-            // buckets hold; run again with the exact capacity
-            (void)qi_gpu_take_error(pl);
-            wcap = mx;
-        }
+        std::vector<uint32_t> wc(R);
+        // adversarial data: more recomputed 65536 values than the work
+        // buckets hold; the error that attempt raised is drained before the
+        // next one, and a capacity that grew is kept for the later groups
+        wcap = stage::run_with_retry(
+            wcap,
+            [&](size_t c) {
+                const size_t wb = qi_gpu_verify_work_bytes(pl, static_cast<int>(R), 1,
+                                                           static_cast<int>(c));
+                if (!wb)
+                    throw std::runtime_error("RsFnt: device allocation failed");
+                reserve(h.entries, wb);
+                check_rc(qi_gpu_verify(pl, h.ctx.p, static_cast<int>(R), dids + k, st.din, 0, P,
+                                       st.dcoded, 0, P, st.dcnt, st.dent, cap, h.entries.p,
+                                       static_cast<int>(c), dres, dres + R, dres + 2 * R,
+                                       static_cast<long long>(words), 1, s),
+                         "verify");
+            },
+            [&] {
+                d2h(res.data(), dres, 3 * R * 4, s);
+                return read_max(wc, h.entries.p, s);
+            },
+            [&] { (void)qi_gpu_take_error(pl); });
         if (qi_gpu_take_error(pl))
             throw std::runtime_error("RsFnt: verify failed (bad ids or OOR bucket capacity)");
+        // collect
         for (size_t j = 0; j < R; j++)
             result[checks[g0 + j]] = VerifyResult{static_cast<long long>(res[j]),
                                                   static_cast<long long>(res[R + j]),
@@ -716,7 +656,6 @@ struct StreamSlot {
     size_t host_bytes = 0;
     DevBuf in, out, small, ctx;
     size_t got = 0, offset = 0;
-    uint32_t cap = 0;
     bool busy = false;
     StreamSlot()
     {
@@ -749,17 +688,7 @@ struct StreamSlot {
         }
         return host;
     }
-    void dev(DevBuf& b, size_t n)
-    {
-        if (!b.reserve(n))
-            throw std::runtime_error("RsFnt: device allocation failed");
-    }
 };
-
-size_t round64(size_t n)
-{
-    return (n + 63) / 64 * 64;
-}
 
 // fn(i) for i < n on up to 16 threads: the fragments are independent
 // streams (shard files, sockets), so they are read and written in parallel
@@ -803,6 +732,89 @@ size_t read_rows(const std::vector<std::istream*>& src, uint8_t* rows,
     return got;
 }
 
+// write `got` bytes of each of the n rows at hout to its stream (null: not
+// wanted)
+template <typename S>
+void write_rows(const std::vector<S*>& dst, size_t n, const uint8_t* hout, size_t pitch,
+                size_t got)
+{
+    parallel_for(n, [&](size_t i) {
+        if (dst[i])
+            dst[i]->write(reinterpret_cast<const char*>(hout + i * pitch),
+                          static_cast<std::streamsize>(got));
+    });
+}
+
+// the reader and writer of a block in caller memory, chunk by chunk: n rows
+// of `total` bytes in, n rows out at the chunk's byte offset (null: not
+// wanted)
+auto mem_reader(const uint8_t* const* rows, size_t n, size_t total)
+{
+    return [=, pos = size_t{0}](uint8_t* h, size_t pitch, bool& cont) mutable {
+        const size_t got = std::min(pitch, total - pos);
+        parallel_for(n, [&](size_t i) {
+            std::memcpy(h + i * pitch, rows[i] + pos, got);
+            std::memset(h + i * pitch + got, 0, pitch - got);
+        });
+        pos += got;
+        cont = pos < total;
+        return got;
+    };
+}
+
+auto mem_writer(uint8_t* const* outs, size_t n)
+{
+    return [=](const uint8_t* hout, size_t pitch, size_t got, size_t off) {
+        parallel_for(n, [&](size_t i) {
+            if (outs[i])
+                std::memcpy(outs[i] + off, hout + i * pitch, got);
+        });
+    };
+}
+
+// The two-slot loop under both pipes: chunks of whole packets (CH bytes per
+// row) alternate between two slots (pinned staging, device buffers, a HIP
+// stream each): while one chunk is in H2D -> kernels -> D2H, the host fills
+// the other slot with the next chunk and finishes the previous one.
+//   pinned_bytes(offset)                  the chunk's pinned staging size
+//   submit(slot, host, got, words, offset)  enqueue the filled chunk on slot.st
+//   finish(slot)                          the chunk has left the device
+// offset counts words; `ops` counts the chunks; chunks finish in order.
+template <typename Reader, typename Bytes, typename Submit, typename Finish>
+void two_slot_pipe(StreamSlot* slot, size_t CH, const Reader& read, uint64_t& ops,
+                   Bytes pinned_bytes, Submit submit, Finish finish)
+{
+    auto done = [&](StreamSlot& sl) {
+        check(hipStreamSynchronize(sl.st), "sync");
+        sl.busy = false;
+        finish(sl);
+    };
+    size_t offset = 0;
+    unsigned it = 0;
+    bool cont = true;
+    while (cont) {
+        StreamSlot& sl = slot[it & 1];
+        if (sl.busy)
+            done(sl);
+        uint8_t* h = sl.pinned(pinned_bytes(offset));
+        const size_t got = read(h, CH, cont);
+        if (got == 0)
+            break;
+        submit(sl, h, got, (got + 1) / 2, offset);
+        sl.got = got;
+        sl.offset = offset;
+        sl.busy = true;
+        offset += got / 2;
+        ops++;
+        it++;
+    }
+    // drain in chunk order: the older pending chunk sits in slot it % 2
+    if (slot[it & 1].busy)
+        done(slot[it & 1]);
+    if (slot[(it + 1) & 1].busy)
+        done(slot[(it + 1) & 1]);
+}
+
 }  // namespace
 
 struct RsFnt::StreamPipe {
@@ -824,10 +836,7 @@ void RsFnt::encode_streams_vertical(
             return read_rows(input_data_bufs, h, pitch, cont);
         },
         [&](const uint8_t* hout, size_t pitch, size_t got, size_t) {
-            parallel_for(n_outputs, [&](size_t i) {
-                output_parities_bufs[i]->write(reinterpret_cast<const char*>(hout + i * pitch),
-                                               static_cast<std::streamsize>(got));
-            });
+            write_rows(output_parities_bufs, n_outputs, hout, pitch, got);
         },
         output_parities_props);
     total_enc_usec += tm.usec();
@@ -836,91 +845,58 @@ void RsFnt::encode_streams_vertical(
 void RsFnt::encode_pipe(const RowReader& read, const RowWriter& write,
                         std::vector<Properties>& output_parities_props)
 {
-    // chunks of whole packets alternate between two slots (pinned staging,
-    // device buffers, a HIP stream each): while one chunk is in H2D ->
-    // kernels -> D2H, the host fills the other slot with the next chunk and
-    // writes out the previous one
     for (auto& p : output_parities_props)
         p.clear();
     const size_t CH = chunk_bytes(buf_size);  // a multiple of 128 bytes
     const size_t P = CH / 2, k = n_data, no = n_outputs;
     const uint32_t cap = static_cast<uint32_t>(64 + P / 512);
-    // pinned: k input rows, no output rows, OOR counts, OOR entries
-    const size_t in_b = k * CH, out_b = no * CH, cnt_b = round64(no * 4);
-    const size_t ent_b = no * cap * 4;
+    // pinned: k input rows, no output rows, then (as on the device) OOR
+    // counts, OOR entries
+    const size_t in_b = k * CH, out_b = no * CH;
+    const auto small = stage::layout({no * 4, no * cap * 4});
     if (!pipe_)
         pipe_.reset(new StreamPipe);
-    StreamSlot* slot = pipe_->slot;
-    auto finish = [&](StreamSlot& sl) {
-        check(hipStreamSynchronize(sl.st), "sync");
-        sl.busy = false;
-        uint8_t* hout = sl.host + in_b;
-        const uint32_t* cnt = reinterpret_cast<const uint32_t*>(hout + out_b);
-        const uint32_t* ent = reinterpret_cast<const uint32_t*>(hout + out_b + cnt_b);
-        const size_t words = (sl.got + 1) / 2;
-        const uint32_t mx = *std::max_element(cnt, cnt + no);
-        if (mx > cap) {
-            // adversarial data: redo this chunk synchronously, exact capacity
-            std::vector<const uint8_t*> dp(k);
-            std::vector<uint8_t*> op(no);
-            for (size_t i = 0; i < k; i++)
-                dp[i] = sl.host + i * CH;
-            for (size_t i = 0; i < no; i++)
-                op[i] = hout + i * CH;
-            encode_columns(plan_, dp.data(), op.data(), words, output_parities_props,
-                           sl.offset);
-        } else {
-            for (size_t i = 0; i < no; i++) {
-                std::vector<uint32_t> b(ent + i * cap, ent + i * cap + cnt[i]);
-                std::sort(b.begin(), b.end());
-                for (uint32_t e : b)
-                    output_parities_props[i].add(sl.offset + e, OOR_MARK);
+    two_slot_pipe(
+        pipe_->slot, CH, read, n_encode_ops,
+        [&](size_t) { return in_b + out_b + small[2]; },
+        [&](StreamSlot& sl, uint8_t* h, size_t, size_t words, size_t) {
+            reserve(sl.in, in_b);
+            reserve(sl.out, out_b);
+            reserve(sl.small, small[2]);
+            uint8_t* ds = static_cast<uint8_t*>(sl.small.p);
+            uint32_t* dcnt = reinterpret_cast<uint32_t*>(ds + small[0]);
+            uint32_t* dent = reinterpret_cast<uint32_t*>(ds + small[1]);
+            h2d(sl.in.p, h, k * CH, sl.st);
+            check_rc(qi_gpu_oor_clear(dcnt, no, sl.st), "oor_clear");
+            check_rc(qi_gpu_encode(plan_, static_cast<uint16_t*>(sl.in.p), 0,
+                                   static_cast<long long>(P), static_cast<uint16_t*>(sl.out.p),
+                                   0, static_cast<long long>(P), static_cast<long long>(words),
+                                   1, dcnt, dent, static_cast<int>(cap), sl.st),
+                     "qi_gpu_encode");
+            d2h(h + in_b, sl.out.p, out_b, sl.st);
+            d2h(h + in_b + out_b, sl.small.p, small[2], sl.st);
+        },
+        [&](StreamSlot& sl) {
+            uint8_t* hout = sl.host + in_b;
+            const uint32_t* cnt = reinterpret_cast<const uint32_t*>(hout + out_b + small[0]);
+            uint32_t* ent = reinterpret_cast<uint32_t*>(hout + out_b + small[1]);
+            if (*std::max_element(cnt, cnt + no) > cap) {
+                // adversarial data: redo this chunk synchronously, exact capacity
+                std::vector<const uint8_t*> dp(k);
+                std::vector<uint8_t*> op(no);
+                for (size_t i = 0; i < k; i++)
+                    dp[i] = sl.host + i * CH;
+                for (size_t i = 0; i < no; i++)
+                    op[i] = hout + i * CH;
+                encode_columns(plan_, dp.data(), op.data(), (sl.got + 1) / 2,
+                               output_parities_props, sl.offset);
+            } else {
+                for (size_t i = 0; i < no; i++)
+                    stage::add_sorted(output_parities_props[i], ent + i * cap, cnt[i],
+                                      sl.offset);
             }
-        }
-        write(hout, CH, sl.got, 2 * sl.offset);
-    };
-    size_t offset = 0;
-    unsigned it = 0;
-    bool cont = true;
-    while (cont) {
-        StreamSlot& sl = slot[it & 1];
-        if (sl.busy)
-            finish(sl);
-        uint8_t* h = sl.pinned(in_b + out_b + cnt_b + ent_b);
-        const size_t got = read(h, CH, cont);
-        if (got == 0)
-            break;
-        const size_t words = (got + 1) / 2;
-        sl.dev(sl.in, in_b);
-        sl.dev(sl.out, out_b);
-        sl.dev(sl.small, cnt_b + ent_b);
-        uint32_t* dcnt = static_cast<uint32_t*>(sl.small.p);
-        uint32_t* dent = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(sl.small.p) + cnt_b);
-        check(hipMemcpyAsync(sl.in.p, h, k * CH, hipMemcpyHostToDevice, sl.st), "H2D");
-        check_rc(qi_gpu_oor_clear(dcnt, no, sl.st), "oor_clear");
-        check_rc(qi_gpu_encode(plan_, static_cast<uint16_t*>(sl.in.p), 0,
-                               static_cast<long long>(P),
-                               static_cast<uint16_t*>(sl.out.p), 0,
-                               static_cast<long long>(P), static_cast<long long>(words),
-                               1, dcnt, dent, static_cast<int>(cap), sl.st),
-                 "qi_gpu_encode");
-        check(hipMemcpyAsync(h + in_b, sl.out.p, out_b, hipMemcpyDeviceToHost, sl.st),
-              "D2H");
-        check(hipMemcpyAsync(h + in_b + out_b, sl.small.p, cnt_b + ent_b,
-                             hipMemcpyDeviceToHost, sl.st),
-              "D2H");
-        sl.got = got;
-        sl.offset = offset;
-        sl.busy = true;
-        offset += got / 2;
-        n_encode_ops++;
-        it++;
-    }
-    // drain in chunk order: the older pending chunk sits in slot it % 2
-    if (slot[it & 1].busy)
-        finish(slot[it & 1]);
-    if (slot[(it + 1) & 1].busy)
-        finish(slot[(it + 1) & 1]);
+            write(hout, CH, sl.got, 2 * sl.offset);
+        });
 }
 
 bool RsFnt::decode_streams_vertical(
@@ -931,22 +907,14 @@ bool RsFnt::decode_streams_vertical(
 {
     // src/fec_base.h:898-1048, through the two-slot pipeline: the k received
     // rows of a chunk are staged back to back (packed decode)
-    const bool sys = type == FecType::SYSTEMATIC;
-    std::vector<int> present(code_len, 0);
-    if (sys)
-        for (unsigned i = 0; i < n_data; i++)
-            present[i] = input_data_bufs[i] != nullptr;
-    for (unsigned i = 0; i < n_outputs; i++)
-        present[sys ? n_data + i : i] = input_parities_bufs[i] != nullptr;
-    if (sys) {
-        unsigned nd = 0;
-        for (unsigned i = 0; i < n_data; i++)
-            nd += present[i];
-        if (nd == n_data)
-            return true;
-    }
+    const stage::FragMap map = frag_map(*this);
+    const std::vector<int> present =
+        map.present([&](unsigned i) { return input_data_bufs[i] != nullptr; },
+                    [&](unsigned i) { return input_parities_bufs[i] != nullptr; });
+    if (map.data_in_clear(present))
+        return true;
     std::vector<int> ids;
-    if (!select_fragments(present, ids))
+    if (!map.select(present, ids))
         return false;
     for (auto& p : input_parities_props)
         p.sort();
@@ -954,26 +922,14 @@ bool RsFnt::decode_streams_vertical(
     const size_t k = n_data;
     std::vector<std::istream*> src(k);
     std::vector<const Properties*> props(k, nullptr);
-    for (size_t i = 0; i < k; i++) {
-        const int id = ids[i];
-        if (sys && id < static_cast<int>(n_data)) {
-            src[i] = input_data_bufs[id];
-        } else {
-            const int s_ = sys ? id - static_cast<int>(n_data) : id;
-            src[i] = input_parities_bufs[s_];
-            props[i] = &input_parities_props[s_];
-        }
-    }
+    selected_rows(map, ids, input_data_bufs, input_parities_bufs, input_parities_props, src,
+                  props);
     Timer tm;
     decode_pipe(
         ids, props,
         [&](uint8_t* h, size_t pitch, bool& cont) { return read_rows(src, h, pitch, cont); },
         [&](const uint8_t* hout, size_t pitch, size_t got, size_t) {
-            parallel_for(k, [&](size_t i) {
-                if (output_data_bufs[i])
-                    output_data_bufs[i]->write(reinterpret_cast<const char*>(hout + i * pitch),
-                                               static_cast<std::streamsize>(got));
-            });
+            write_rows(output_data_bufs, k, hout, pitch, got);
         });
     total_dec_usec += tm.usec();
     return true;
@@ -983,100 +939,63 @@ void RsFnt::decode_pipe(const std::vector<int>& ids, const std::vector<const Pro
                         const RowReader& read, const RowWriter& write)
 {
     const size_t k = n_data;
-    // OOR marks of each received row (ascending), consumed chunk by chunk
-    std::vector<std::vector<size_t>> marks(k);
-    for (size_t i = 0; i < k; i++)
-        if (props[i])
-            for (auto const& it : props[i]->get_map())
-                marks[i].push_back(it.first);
-    std::vector<size_t> mpos(k, 0);
     const size_t CH = chunk_bytes(buf_size);
     const size_t P = CH / 2;
-    const size_t io_b = k * CH, ids_b = round64(k * 2), cnt_b = round64(k * 4);
+    const size_t io_b = k * CH;
+    // OOR marks of each received row (ascending), consumed chunk by chunk;
+    // pinned behind the rows, as on the device: ids, counts, entries
+    std::vector<size_t> cursor(k, 0);
+    stage::PackedMarks pm;
+    std::array<size_t, 4> small{};
     if (!pipe_)
         pipe_.reset(new StreamPipe);
-    StreamSlot* slot = pipe_->slot;
-    auto finish = [&](StreamSlot& sl) {
-        check(hipStreamSynchronize(sl.st), "sync");
-        sl.busy = false;
-        if (qi_gpu_take_error(plan_))
-            throw std::runtime_error("RsFnt: OOR marks lost (bucket capacity)");
-        write(sl.host + io_b, CH, sl.got, 2 * sl.offset);
-    };
-    size_t offset = 0;
-    unsigned it = 0;
-    bool cont = true;
-    while (cont) {
-        StreamSlot& sl = slot[it & 1];
-        if (sl.busy)
-            finish(sl);
-        // the chunk's marks per received row (positions relative to it)
-        const size_t words_max = P;
-        std::vector<std::vector<uint32_t>> cm(k);
-        uint32_t cap = 1;
-        for (size_t i = 0; i < k; i++) {
-            while (mpos[i] < marks[i].size() && marks[i][mpos[i]] < offset)
-                mpos[i]++;
-            size_t e = mpos[i];
-            while (e < marks[i].size() && marks[i][e] < offset + words_max)
-                cm[i].push_back(static_cast<uint32_t>(marks[i][e++] - offset));
-            cap = std::max<uint32_t>(cap, static_cast<uint32_t>(cm[i].size()));
-        }
-        const size_t ent_b = round64(static_cast<size_t>(k) * cap * 4);
-        const size_t small_b = ids_b + cnt_b + ent_b;
-        uint8_t* h = sl.pinned(2 * io_b + small_b);
-        const size_t got = read(h, CH, cont);
-        if (got == 0)
-            break;
-        const size_t words = (got + 1) / 2;
-        uint8_t* hs = h + 2 * io_b;
-        uint16_t* hids = reinterpret_cast<uint16_t*>(hs);
-        uint32_t* hcnt = reinterpret_cast<uint32_t*>(hs + ids_b);
-        uint32_t* hent = reinterpret_cast<uint32_t*>(hs + ids_b + cnt_b);
-        for (size_t i = 0; i < k; i++) {
-            hids[i] = static_cast<uint16_t>(ids[i]);
-            hcnt[i] = static_cast<uint32_t>(cm[i].size());
-            std::copy(cm[i].begin(), cm[i].end(), hent + i * cap);
-        }
-        // the context's size follows this chunk's width (a 256 < k <= 384
-        // context is larger at whole-tile widths than at ragged ones)
-        const size_t ctx_b = qi_gpu_decode_ctx_bytes(plan_, 1, static_cast<long long>(words));
-        sl.dev(sl.in, io_b);
-        sl.dev(sl.out, io_b);
-        sl.dev(sl.small, small_b);
-        sl.dev(sl.ctx, ctx_b);
-        uint8_t* ds = static_cast<uint8_t*>(sl.small.p);
-        const uint16_t* dids = reinterpret_cast<const uint16_t*>(ds);
-        const uint32_t* dcnt = reinterpret_cast<const uint32_t*>(ds + ids_b);
-        const uint32_t* dent = reinterpret_cast<const uint32_t*>(ds + ids_b + cnt_b);
-        check(hipMemcpyAsync(sl.in.p, h, io_b, hipMemcpyHostToDevice, sl.st), "H2D");
-        check(hipMemcpyAsync(sl.small.p, hs, small_b, hipMemcpyHostToDevice, sl.st),
-              "H2D");
-        check_rc(qi_gpu_decode_ctx_packed(plan_, dids, hids, 1, dcnt, dent,
+    two_slot_pipe(
+        pipe_->slot, CH, read, n_decode_ops,
+        [&](size_t offset) {
+            // the chunk's marks per received row (positions relative to it)
+            pm = stage::pack_marks(props, offset, P, &cursor);
+            small = stage::layout({k * 2, k * 4, stage::round64(k * pm.cap * 4)});
+            return 2 * io_b + small[3];
+        },
+        [&](StreamSlot& sl, uint8_t* h, size_t, size_t words, size_t) {
+            const size_t cap = pm.cap;
+            uint8_t* hs = h + 2 * io_b;
+            uint16_t* hids = reinterpret_cast<uint16_t*>(hs + small[0]);
+            std::copy(ids.begin(), ids.end(), hids);
+            std::copy(pm.counts.begin(), pm.counts.end(),
+                      reinterpret_cast<uint32_t*>(hs + small[1]));
+            std::copy(pm.entries.begin(), pm.entries.end(),
+                      reinterpret_cast<uint32_t*>(hs + small[2]));
+            // the context's size follows this chunk's width (a 256 < k <= 384
+            // context is larger at whole-tile widths than at ragged ones)
+            reserve(sl.in, io_b);
+            reserve(sl.out, io_b);
+            reserve(sl.small, small[3]);
+            reserve(sl.ctx, qi_gpu_decode_ctx_bytes(plan_, 1, static_cast<long long>(words)));
+            uint8_t* ds = static_cast<uint8_t*>(sl.small.p);
+            const uint16_t* dids = reinterpret_cast<const uint16_t*>(ds + small[0]);
+            const uint32_t* dcnt = reinterpret_cast<const uint32_t*>(ds + small[1]);
+            const uint32_t* dent = reinterpret_cast<const uint32_t*>(ds + small[2]);
+            h2d(sl.in.p, h, io_b, sl.st);
+            h2d(sl.small.p, hs, small[3], sl.st);
+            check_rc(qi_gpu_decode_ctx_packed(plan_, dids, hids, 1, dcnt, dent,
+                                              static_cast<int>(cap),
+                                              static_cast<long long>(words), sl.ctx.p, sl.st),
+                     "decode context");
+            check_rc(qi_gpu_decode_packed(plan_, sl.ctx.p, static_cast<uint16_t*>(sl.in.p), 0,
+                                          static_cast<long long>(P), dcnt, dent,
                                           static_cast<int>(cap),
-                                          static_cast<long long>(words), sl.ctx.p,
-                                          sl.st),
-                 "decode context");
-        check_rc(qi_gpu_decode_packed(plan_, sl.ctx.p, static_cast<uint16_t*>(sl.in.p),
-                                      0, static_cast<long long>(P), dcnt, dent,
-                                      static_cast<int>(cap),
-                                      static_cast<uint16_t*>(sl.out.p), 0,
-                                      static_cast<long long>(P),
-                                      static_cast<long long>(words), 1, sl.st),
-                 "decode");
-        check(hipMemcpyAsync(h + io_b, sl.out.p, io_b, hipMemcpyDeviceToHost, sl.st),
-              "D2H");
-        sl.got = got;
-        sl.offset = offset;
-        sl.busy = true;
-        offset += got / 2;
-        n_decode_ops++;
-        it++;
-    }
-    if (slot[it & 1].busy)
-        finish(slot[it & 1]);
-    if (slot[(it + 1) & 1].busy)
-        finish(slot[(it + 1) & 1]);
+                                          static_cast<uint16_t*>(sl.out.p), 0,
+                                          static_cast<long long>(P),
+                                          static_cast<long long>(words), 1, sl.st),
+                     "decode");
+            d2h(h + io_b, sl.out.p, io_b, sl.st);
+        },
+        [&](StreamSlot& sl) {
+            if (qi_gpu_take_error(plan_))
+                throw std::runtime_error("RsFnt: OOR marks lost (bucket capacity)");
+            write(sl.host + io_b, CH, sl.got, 2 * sl.offset);
+        });
 }
 
 // Blocks wider than one pipeline chunk (quadiron_fnt32_encode / _decode on
@@ -1091,29 +1010,11 @@ bool RsFnt::encode_blocks_pipe(const std::vector<uint8_t*>& data_bufs,
 {
     if (words <= chunk_bytes(buf_size) / 2)
         return false;
-    const size_t total = 2 * words;
-    size_t pos = 0;
     // one operation per block call, as the reference counts it
     // (src/fec_base.h:1136); the pipe counts its chunks
     const uint64_t ops = n_encode_ops;
-    encode_pipe(
-        [&](uint8_t* h, size_t pitch, bool& cont) {
-            const size_t got = std::min(pitch, total - pos);
-            parallel_for(n_data, [&](size_t i) {
-                std::memcpy(h + i * pitch, data_bufs[i] + pos, got);
-                std::memset(h + i * pitch + got, 0, pitch - got);
-            });
-            pos += got;
-            cont = pos < total;
-            return got;
-        },
-        [&](const uint8_t* hout, size_t pitch, size_t got, size_t off) {
-            parallel_for(n_outputs, [&](size_t i) {
-                if (outs[i])
-                    std::memcpy(outs[i] + off, hout + i * pitch, got);
-            });
-        },
-        props);
+    encode_pipe(mem_reader(data_bufs.data(), n_data, 2 * words),
+                mem_writer(outs.data(), n_outputs), props);
     n_encode_ops = ops + 1;
     return true;
 }
@@ -1125,27 +1026,9 @@ bool RsFnt::decode_blocks_pipe(const std::vector<int>& ids,
 {
     if (words <= chunk_bytes(buf_size) / 2)
         return false;
-    const size_t total = 2 * words;
-    size_t pos = 0;
     const uint64_t ops = n_decode_ops;  // one per block call (src/fec_base.h:1304)
-    decode_pipe(
-        ids, props,
-        [&](uint8_t* h, size_t pitch, bool& cont) {
-            const size_t got = std::min(pitch, total - pos);
-            parallel_for(n_data, [&](size_t i) {
-                std::memcpy(h + i * pitch, rows[i] + pos, got);
-                std::memset(h + i * pitch + got, 0, pitch - got);
-            });
-            pos += got;
-            cont = pos < total;
-            return got;
-        },
-        [&](const uint8_t* hout, size_t pitch, size_t got, size_t off) {
-            parallel_for(n_data, [&](size_t i) {
-                if (outs[i])
-                    std::memcpy(outs[i] + off, hout + i * pitch, got);
-            });
-        });
+    decode_pipe(ids, props, mem_reader(rows.data(), n_data, 2 * words),
+                mem_writer(outs.data(), n_data));
     n_decode_ops = ops + 1;
     return true;
 }
@@ -1313,7 +1196,7 @@ void RsFnt::decode(DecodeContext& context, vec::Buffers& output,
     // coded fragments (props by parity index) inside [offset, offset + size)
     // restore 65536; decode_apply (:1418-1448) + for systematic codes the
     // evaluation at r^t (:1336-1355): output = the k data rows
-    const bool sys = type == FecType::SYSTEMATIC;
+    const stage::FragMap map = frag_map(*this);
     const vec::Vector& ids = context.get_fragments_id();
     const size_t size = words.get_size();
     if (words.get_n() < static_cast<int>(n_data) || output.get_n() < static_cast<int>(n_data) ||
@@ -1331,21 +1214,19 @@ void RsFnt::decode(DecodeContext& context, vec::Buffers& output,
         const unsigned r = ord[i];
         id[i] = static_cast<int>(ids[r]);
         uint32_t* w = words.get(static_cast<int>(r));
-        if (!(sys && ids[r] < n_data)) {
-            const size_t pi = sys ? ids[r] - n_data : ids[r];
-            if (pi < props.size())
-                // decode_prepare restores the marks in [offset, offset +
-                // pkt_size) (src/fec_base.h:1372), which equals the Buffers'
-                // size on the reference's own paths; here the window is the
-                // Buffers' size: a Buffers wider than pkt_size keeps every
-                // mark (the reference would drop those past pkt_size) and a
-                // narrower one is never written past its end (deliberate
-                // deviation)
-                for (auto const& it : props[pi].get_map())
-                    if (it.second == OOR_MARK && it.first >= static_cast<size_t>(offset) &&
-                        it.first < static_cast<size_t>(offset) + size)
-                        w[it.first - static_cast<size_t>(offset)] = 65536u;
-        }
+        const auto fs = map.slot(ids[r]);
+        if (!fs.is_data && fs.slot < props.size())
+            // decode_prepare restores the marks in [offset, offset +
+            // pkt_size) (src/fec_base.h:1372), which equals the Buffers'
+            // size on the reference's own paths; here the window is the
+            // Buffers' size: a Buffers wider than pkt_size keeps every
+            // mark (the reference would drop those past pkt_size) and a
+            // narrower one is never written past its end (deliberate
+            // deviation)
+            for (auto const& it : props[fs.slot].get_map())
+                if (it.second == OOR_MARK && it.first >= static_cast<size_t>(offset) &&
+                    it.first < static_cast<size_t>(offset) + size)
+                    w[it.first - static_cast<size_t>(offset)] = 65536u;
         for (size_t j = 0; j < size; j++) {
             in[i][j] = static_cast<uint16_t>(w[j] & 0xffffu);
             if (w[j] == 65536u)
@@ -1366,36 +1247,14 @@ void RsFnt::decode(DecodeContext& context, vec::Buffers& output,
 
 // ----------------------------------------------------------------- RS-NF4
 
-void nf4_marks_from_lanes(const Properties& lanes, unsigned g,
-                          Properties& words)
+void nf4_marks_from_lanes(const Properties& lanes, unsigned g, Properties& words)
 {
-    // encode_post_process (src/fec_rs_nf4.h:271-289): one mark per word,
-    // bit c set when component c was 65536 (NF4::unpack, gf_nf4.h:421-446)
-    words.clear();
-    size_t cur = 0;
-    uint32_t mask = 0;
-    for (auto const& it : lanes.get_map()) {
-        const size_t w = it.first / g;
-        if (mask && w != cur) {
-            words.add(cur, mask);
-            mask = 0;
-        }
-        cur = w;
-        mask |= 1u << (it.first % g);
-    }
-    if (mask)
-        words.add(cur, mask);
+    stage::marks_from_lanes(lanes, g, words);
 }
 
 void nf4_marks_to_lanes(const Properties& words, unsigned g, Properties& lanes)
 {
-    // decode_prepare (src/fec_rs_nf4.h:291-317): NF4::pack(a, flag) sets the
-    // flagged components to 65536 (gf_nf4.h:372-383)
-    lanes.clear();
-    for (auto const& it : words.get_map())
-        for (unsigned c = 0; c < g; c++)
-            if ((it.second >> c) & 1u)
-                lanes.add(it.first * g + c, OOR_MARK);
+    stage::marks_to_lanes(words, g, lanes);
 }
 
 namespace {
@@ -1482,6 +1341,67 @@ struct qi_fec {
     qi::fec::RsFnt* f;
 };
 
+struct qi_nf4 {
+    qi::fec::RsNf4* f;
+};
+
+namespace {
+
+namespace stage = qi::fec::stage;
+
+// the block calls of both classes on flat (oor, flags, oor_count, cap)
+// arrays; flags null: RS-FNT's plain marks
+template <typename F>
+int encode_blocks_flat(F& f, uint8_t** data, uint8_t** outputs, size_t block_bytes,
+                       uint32_t* oor, uint32_t* flags, uint32_t* oor_count, uint32_t cap)
+{
+    std::vector<uint8_t*> dv(data, data + f.n_data);
+    std::vector<uint8_t*> pv(outputs, outputs + f.n_outputs);
+    std::vector<qi::Properties> props(f.n_outputs);
+    std::vector<bool> wanted(f.n_outputs);
+    for (unsigned i = 0; i < f.n_outputs; i++)
+        wanted[i] = outputs[i] != nullptr;
+    f.encode_blocks_vertical(dv, pv, props, wanted, block_bytes);
+    stage::props_to_flat(props, oor, flags, oor_count, cap);
+    return 0;
+}
+
+template <typename F>
+int decode_blocks_flat(F& f, uint8_t** data, uint8_t** parities, const uint32_t* oor,
+                       const uint32_t* flags, const uint32_t* oor_count, uint32_t cap,
+                       const int* missing, const int* wanted, size_t block_bytes)
+{
+    std::vector<uint8_t*> dv(data, data + f.n_data);
+    std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
+    std::vector<qi::Properties> props(f.n_outputs);
+    stage::props_from_flat(props, oor, flags, oor_count, cap);
+    std::vector<int> miss(missing, missing + f.code_len);
+    std::vector<bool> want(f.n_data);
+    for (unsigned i = 0; i < f.n_data; i++)
+        want[i] = wanted[i] != 0;
+    return f.decode_blocks_vertical(dv, pv, props, miss, want, block_bytes) ? 1 : 0;
+}
+
+// data rows (null: none, as for a non-systematic code) and coded rows with
+// their marks, as repair and verify take them
+struct FlatFragments {
+    std::vector<uint8_t*> dv, pv;
+    std::vector<qi::Properties> props;
+    std::vector<int> miss;
+    FlatFragments(const qi::fec::RsFnt& f, uint8_t** data, uint8_t** parities,
+                  const uint32_t* oor, const uint32_t* oor_count, uint32_t cap,
+                  const int* missing)
+        : dv(f.n_data, nullptr), pv(parities, parities + f.n_outputs), props(f.n_outputs),
+          miss(missing, missing + f.code_len)
+    {
+        if (data)
+            dv.assign(data, data + f.n_data);
+        stage::props_from_flat(props, oor, nullptr, oor_count, cap);
+    }
+};
+
+}  // namespace
+
 extern "C" {
 
 qi_fec* qi_fec_new(int systematic, int k, int m)
@@ -1516,25 +1436,8 @@ int qi_fec_encode_blocks(qi_fec* h, uint8_t** data, uint8_t** outputs,
                          uint32_t cap)
 {
     try {
-        qi::fec::RsFnt& f = *h->f;
-        std::vector<uint8_t*> dv(data, data + f.n_data);
-        std::vector<uint8_t*> pv(outputs, outputs + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        std::vector<bool> wanted(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++)
-            wanted[i] = outputs[i] != nullptr;
-        f.encode_blocks_vertical(dv, pv, props, wanted, block_bytes);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            uint32_t c = 0;
-            for (auto const& it : props[i].get_map()) {
-                if (c < cap)
-                    oor[static_cast<size_t>(i) * cap + c] =
-                        static_cast<uint32_t>(it.first);
-                c++;
-            }
-            oor_count[i] = c;
-        }
-        return 0;
+        return encode_blocks_flat(*h->f, data, outputs, block_bytes, oor, nullptr, oor_count,
+                                  cap);
     } catch (...) {
         return -1;
     }
@@ -1546,21 +1449,8 @@ int qi_fec_decode_blocks(qi_fec* h, uint8_t** data, uint8_t** parities,
                          size_t block_bytes)
 {
     try {
-        qi::fec::RsFnt& f = *h->f;
-        std::vector<uint8_t*> dv(data, data + f.n_data);
-        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            const uint32_t c = oor_count[i] < cap ? oor_count[i] : cap;
-            for (uint32_t e = 0; e < c; e++)
-                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
-        }
-        std::vector<int> miss(missing, missing + f.code_len);
-        std::vector<bool> want(f.n_data);
-        for (unsigned i = 0; i < f.n_data; i++)
-            want[i] = wanted[i] != 0;
-        return f.decode_blocks_vertical(dv, pv, props, miss, want, block_bytes) ? 1
-                                                                                : 0;
+        return decode_blocks_flat(*h->f, data, parities, oor, nullptr, oor_count, cap, missing,
+                                  wanted, block_bytes);
     } catch (...) {
         return -1;
     }
@@ -1577,32 +1467,14 @@ int qi_fec_repair_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const ui
         qi::fec::RsFnt& f = *h->f;
         if (!f.repair_supported(static_cast<size_t>(n_targets), block_bytes))
             return -2;
-        std::vector<uint8_t*> dv(f.n_data, nullptr);
-        if (data)
-            dv.assign(data, data + f.n_data);
-        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            const uint32_t c = oor_count[i] < cap ? oor_count[i] : cap;
-            for (uint32_t e = 0; e < c; e++)
-                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
-        }
-        std::vector<int> miss(missing, missing + f.code_len);
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
         std::vector<int> tg(targets, targets + n_targets);
         std::vector<uint8_t*> ov(out, out + n_targets);
         std::vector<qi::Properties> oprops;
-        if (!f.repair_blocks_vertical(dv, pv, props, miss, tg, ov, oprops, block_bytes))
+        if (!f.repair_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, tg, ov, oprops,
+                                      block_bytes))
             return 0;
-        for (int j = 0; j < n_targets; j++) {
-            uint32_t c = 0;
-            for (auto const& it : oprops[j].get_map()) {
-                if (c < out_cap)
-                    out_oor[static_cast<size_t>(j) * out_cap + c] =
-                        static_cast<uint32_t>(it.first);
-                c++;
-            }
-            out_count[j] = c;
-        }
+        stage::props_to_flat(oprops, out_oor, nullptr, out_count, out_cap);
         return 1;
     } catch (...) {
         return -1;
@@ -1619,19 +1491,11 @@ int qi_fec_verify_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const ui
         qi::fec::RsFnt& f = *h->f;
         if (!f.repair_supported(1, block_bytes))
             return -2;
-        std::vector<uint8_t*> dv(f.n_data, nullptr);
-        if (data)
-            dv.assign(data, data + f.n_data);
-        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            const uint32_t c = !oor_count ? 0 : oor_count[i] < cap ? oor_count[i] : cap;
-            for (uint32_t e = 0; e < c; e++)
-                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
-        }
-        std::vector<int> miss(missing, missing + f.code_len);
+        // (oor_count null: no marks)
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
         std::vector<qi::fec::VerifyResult> res;
-        const bool ok = f.verify_blocks_vertical(dv, pv, props, miss, res, block_bytes);
+        const bool ok = f.verify_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res,
+                                                 block_bytes);
         for (unsigned i = 0; i < f.code_len; i++) {
             result[3 * i] = res[i].value_mismatch;
             result[3 * i + 1] = res[i].mark_mismatch;
@@ -1706,16 +1570,7 @@ int qi_fec_encode_streams(qi_fec* h, const uint8_t** data, size_t bytes,
                 return -1;
         std::vector<qi::Properties> props(f.n_outputs);
         f.encode_streams_vertical(in, out, props);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            uint32_t c = 0;
-            for (auto const& it : props[i].get_map()) {
-                if (c < cap)
-                    oor[static_cast<size_t>(i) * cap + c] =
-                        static_cast<uint32_t>(it.first);
-                c++;
-            }
-            oor_count[i] = c;
-        }
+        stage::props_to_flat(props, oor, nullptr, oor_count, cap);
         return 0;
     } catch (...) {
         return -1;
@@ -1736,26 +1591,15 @@ int qi_fec_decode_streams(qi_fec* h, const uint8_t** data,
             din[i] = ms.in(data ? data[i] : nullptr, bytes);
             dout[i] = ms.out(out_data[i], bytes);
         }
-        std::vector<qi::Properties> props(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
+        for (unsigned i = 0; i < f.n_outputs; i++)
             pin[i] = ms.in(parities[i], bytes);
-            const uint32_t c = oor_count[i] < cap ? oor_count[i] : cap;
-            for (uint32_t e = 0; e < c; e++)
-                props[i].add(oor[static_cast<size_t>(i) * cap + e], qi::OOR_MARK);
-        }
+        std::vector<qi::Properties> props(f.n_outputs);
+        stage::props_from_flat(props, oor, nullptr, oor_count, cap);
         return f.decode_streams_vertical(din, pin, props, dout) ? 1 : 0;
     } catch (...) {
         return -1;
     }
 }
-
-}  // extern "C"
-
-struct qi_nf4 {
-    qi::fec::RsNf4* f;
-};
-
-extern "C" {
 
 qi_nf4* qi_nf4_new(int word_size, int k, int m)
 {
@@ -1795,27 +1639,7 @@ int qi_nf4_encode_blocks(qi_nf4* h, uint8_t** data, uint8_t** outputs,
                          uint32_t* oor_count, uint32_t cap)
 {
     try {
-        qi::fec::RsNf4& f = *h->f;
-        std::vector<uint8_t*> dv(data, data + f.n_data);
-        std::vector<uint8_t*> pv(outputs, outputs + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        std::vector<bool> wanted(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++)
-            wanted[i] = outputs[i] != nullptr;
-        f.encode_blocks_vertical(dv, pv, props, wanted, block_bytes);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            uint32_t c = 0;
-            for (auto const& it : props[i].get_map()) {
-                if (c < cap) {
-                    oor[static_cast<size_t>(i) * cap + c] =
-                        static_cast<uint32_t>(it.first);
-                    flags[static_cast<size_t>(i) * cap + c] = it.second;
-                }
-                c++;
-            }
-            oor_count[i] = c;
-        }
-        return 0;
+        return encode_blocks_flat(*h->f, data, outputs, block_bytes, oor, flags, oor_count, cap);
     } catch (...) {
         return -1;
     }
@@ -1828,22 +1652,8 @@ int qi_nf4_decode_blocks(qi_nf4* h, uint8_t** data, uint8_t** parities,
                          size_t block_bytes)
 {
     try {
-        qi::fec::RsNf4& f = *h->f;
-        std::vector<uint8_t*> dv(data, data + f.n_data);
-        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
-        std::vector<qi::Properties> props(f.n_outputs);
-        for (unsigned i = 0; i < f.n_outputs; i++) {
-            const uint32_t c = oor_count[i] < cap ? oor_count[i] : cap;
-            for (uint32_t e = 0; e < c; e++)
-                props[i].add(oor[static_cast<size_t>(i) * cap + e],
-                             flags[static_cast<size_t>(i) * cap + e]);
-        }
-        std::vector<int> miss(missing, missing + f.code_len);
-        std::vector<bool> want(f.n_data);
-        for (unsigned i = 0; i < f.n_data; i++)
-            want[i] = wanted[i] != 0;
-        return f.decode_blocks_vertical(dv, pv, props, miss, want, block_bytes) ? 1
-                                                                                : 0;
+        return decode_blocks_flat(*h->f, data, parities, oor, flags, oor_count, cap, missing,
+                                  wanted, block_bytes);
     } catch (...) {
         return -1;
     }

@@ -1,0 +1,256 @@
+// fec_stage.h -- the host facade's staging steps that need no device: which
+// fragments a decode uses and where each one lives, OOR marks packed into the
+// device's counts + entries[cap] form, the layout of the small device buffer,
+// the bounded capacity retry, and the flat C arrays <-> Properties.  No HIP,
+// no plan: fec.cpp and quadiron_c.cpp build on it, and
+// tests/host/test_fec_stage.cpp checks it on the CPU.
+#pragma once
+
+#include <algorithm>
+#include <array>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/qi_fec.hpp"
+
+namespace qi {
+namespace fec {
+namespace stage {
+
+// ---- fragment map -------------------------------------------------------
+// Fragment ids are the decode's id space: systematic f < k is data row f and
+// f >= k coded slot (parity) f - k; non-systematic f is coded slot f.
+struct FragMap {
+    bool sys;
+    unsigned k, n_outputs;
+    FragMap(FecType t, unsigned n_data, unsigned outputs)
+        : sys(t == FecType::SYSTEMATIC), k(n_data), n_outputs(outputs)
+    {
+    }
+    struct Slot {
+        bool is_data;
+        unsigned slot;
+    };
+    unsigned code_len() const { return sys ? k + n_outputs : n_outputs; }
+    unsigned data_rows() const { return sys ? k : 0; }
+    Slot slot(unsigned id) const
+    {
+        return sys && id < k ? Slot{true, id} : Slot{false, sys ? id - k : id};
+    }
+    unsigned coded_id(unsigned slot) const { return sys ? k + slot : slot; }
+    // the entry of fragment `id` in the caller's data / coded arrays
+    template <typename A, typename B>
+    auto pick(unsigned id, const A& data, const B& coded) const
+    {
+        const Slot s = slot(id);
+        return s.is_data ? data[s.slot] : coded[s.slot];
+    }
+    std::vector<int> present(const std::vector<int>& missing_idxs) const
+    {
+        std::vector<int> p(code_len());
+        for (unsigned i = 0; i < code_len(); i++)
+            p[i] = missing_idxs[i] ? 0 : 1;
+        return p;
+    }
+    // has_data(i) / has_coded(slot): whether the caller holds that fragment
+    template <typename D, typename C>
+    std::vector<int> present(D has_data, C has_coded) const
+    {
+        std::vector<int> p(code_len(), 0);
+        for (unsigned i = 0; i < data_rows(); i++)
+            p[i] = has_data(i) ? 1 : 0;
+        for (unsigned i = 0; i < n_outputs; i++)
+            p[coded_id(i)] = has_coded(i) ? 1 : 0;
+        return p;
+    }
+    // systematic with every data row present: nothing to decode
+    // (src/fec_base.h:1208-1211)
+    bool data_in_clear(const std::vector<int>& present) const
+    {
+        if (!sys)
+            return false;
+        for (unsigned i = 0; i < k; i++)
+            if (!present[i])
+                return false;
+        return true;
+    }
+    // first k present, data before parities: src/fec_base.h:1199-1236
+    bool select(const std::vector<int>& present, std::vector<int>& ids) const
+    {
+        ids.clear();
+        for (unsigned i = 0; i < data_rows(); i++)
+            if (present[i])
+                ids.push_back(static_cast<int>(i));
+        for (unsigned i = 0; i < n_outputs && ids.size() < k; i++)
+            if (present[coded_id(i)])
+                ids.push_back(static_cast<int>(coded_id(i)));
+        return ids.size() == k;
+    }
+};
+
+// ---- mark packing -------------------------------------------------------
+// rows.size() buckets of `cap` entries each: the marks of rows[i] (null: no
+// marks) inside [offset, offset + words), relative to offset, in list order;
+// cap is the largest count, at least 1
+struct PackedMarks {
+    std::vector<uint32_t> counts, entries;
+    size_t cap = 1;
+};
+
+// With a cursor (one position per row, zero before the first window) the
+// lists must ascend and the windows move forward: every mark is then taken
+// once and skipped once over the whole walk.
+inline PackedMarks pack_marks(const std::vector<const Properties*>& rows, size_t offset,
+                              size_t words, std::vector<size_t>* cursor = nullptr)
+{
+    const size_t n = rows.size();
+    std::vector<std::vector<uint32_t>> in(n);
+    PackedMarks pm;
+    for (size_t i = 0; i < n; i++) {
+        if (!rows[i])
+            continue;
+        auto const& mk = rows[i]->get_map();
+        size_t b = 0;
+        if (cursor) {
+            size_t& c = (*cursor)[i];
+            while (c < mk.size() && mk[c].first < offset)
+                c++;
+            b = c;
+        }
+        for (size_t e = b; e < mk.size(); e++) {
+            if (mk[e].first >= offset + words) {
+                if (cursor)
+                    break;
+                continue;
+            }
+            if (mk[e].first >= offset)
+                in[i].push_back(static_cast<uint32_t>(mk[e].first - offset));
+        }
+        pm.cap = std::max(pm.cap, in[i].size());
+    }
+    pm.counts.resize(n);
+    pm.entries.assign(n * pm.cap, 0);
+    for (size_t i = 0; i < n; i++) {
+        pm.counts[i] = static_cast<uint32_t>(in[i].size());
+        std::copy(in[i].begin(), in[i].end(), pm.entries.begin() + i * pm.cap);
+    }
+    return pm;
+}
+
+// ---- small-buffer layout ------------------------------------------------
+inline size_t round64(size_t n)
+{
+    return (n + 63) / 64 * 64;
+}
+
+// consecutive sections of the given byte sizes, each starting on a 64-byte
+// boundary: off[i] is the start of section i, off[N] the end of the last one
+template <size_t N>
+std::array<size_t, N + 1> layout(const size_t (&bytes)[N])
+{
+    std::array<size_t, N + 1> off{};
+    for (size_t i = 0; i < N; i++) {
+        off[i] = i ? round64(off[i]) : 0;
+        off[i + 1] = off[i] + bytes[i];
+    }
+    return off;
+}
+
+// ---- capacity retry -----------------------------------------------------
+// launch(cap), then read_max() -- the largest bucket count the launch
+// reported.  A count above cap (adversarial data) means entries were dropped:
+// between() and one more launch with the exact capacity, read back again.
+// At most two attempts; returns the capacity of the last one.
+template <typename Launch, typename ReadMax, typename Between>
+size_t run_with_retry(size_t cap, Launch launch, ReadMax read_max, Between between)
+{
+    launch(cap);
+    const size_t mx = read_max();
+    if (mx <= cap)
+        return cap;
+    between();
+    launch(mx);
+    (void)read_max();
+    return mx;
+}
+
+// ---- entries -> Properties ----------------------------------------------
+// a device bucket is unordered: its first `count` entries, ascending, become
+// marks at offset + entry
+inline void add_sorted(Properties& p, uint32_t* bucket, uint32_t count, size_t offset)
+{
+    std::sort(bucket, bucket + count);
+    for (uint32_t e = 0; e < count; e++)
+        p.add(offset + bucket[e], OOR_MARK);
+}
+
+// ---- flat C arrays <-> Properties ---------------------------------------
+// (oor, flags, count, cap): props.size() rows of cap locations (and markers;
+// flags null: OOR_MARK) with a count each.  A count above cap is clamped on
+// the way in; on the way out the count is exact and only cap entries are
+// written.  count null on the way in: no marks.
+inline void props_from_flat(std::vector<Properties>& props, const uint32_t* oor,
+                            const uint32_t* flags, const uint32_t* count, uint32_t cap)
+{
+    for (size_t i = 0; i < props.size(); i++) {
+        const uint32_t c = !count ? 0 : std::min(count[i], cap);
+        for (uint32_t e = 0; e < c; e++)
+            props[i].add(oor[i * cap + e], flags ? flags[i * cap + e] : OOR_MARK);
+    }
+}
+
+inline void props_to_flat(const std::vector<Properties>& props, uint32_t* oor, uint32_t* flags,
+                          uint32_t* count, uint32_t cap)
+{
+    for (size_t i = 0; i < props.size(); i++) {
+        uint32_t c = 0;
+        for (auto const& it : props[i].get_map()) {
+            if (c < cap) {
+                oor[i * cap + c] = static_cast<uint32_t>(it.first);
+                if (flags)
+                    flags[i * cap + c] = it.second;
+            }
+            c++;
+        }
+        count[i] = c;
+    }
+}
+
+// ---- RS-NF4 marks -------------------------------------------------------
+// (16-bit lane, OOR_MARK) marks <-> (word, component mask) marks of g lanes
+// per word; lane marks ascend
+inline void marks_from_lanes(const Properties& lanes, unsigned g, Properties& words)
+{
+    // encode_post_process (src/fec_rs_nf4.h:271-289): one mark per word,
+    // bit c set when component c was 65536 (NF4::unpack, gf_nf4.h:421-446)
+    words.clear();
+    size_t cur = 0;
+    uint32_t mask = 0;
+    for (auto const& it : lanes.get_map()) {
+        const size_t w = it.first / g;
+        if (mask && w != cur) {
+            words.add(cur, mask);
+            mask = 0;
+        }
+        cur = w;
+        mask |= 1u << (it.first % g);
+    }
+    if (mask)
+        words.add(cur, mask);
+}
+
+inline void marks_to_lanes(const Properties& words, unsigned g, Properties& lanes)
+{
+    // decode_prepare (src/fec_rs_nf4.h:291-317): NF4::pack(a, flag) sets the
+    // flagged components to 65536 (gf_nf4.h:372-383)
+    lanes.clear();
+    for (auto const& it : words.get_map())
+        for (unsigned c = 0; c < g; c++)
+            if ((it.second >> c) & 1u)
+                lanes.add(it.first * g + c, OOR_MARK);
+}
+
+}  // namespace stage
+}  // namespace fec
+}  // namespace qi

@@ -10,10 +10,12 @@
 
 #include "../../include/qi_fec.hpp"
 #include "../../include/quadiron_c.h"
+#include "fec_stage.h"
 
 using qi::Properties;
 using qi::fec::FecType;
 using qi::fec::RsFnt;
+using qi::fec::stage::FragMap;
 
 namespace {
 
@@ -32,35 +34,33 @@ uint32_t* hdr(uint8_t* p)
     return reinterpret_cast<uint32_t*>(p);
 }
 
+// fragment f of the C-ABI: data[f] below k, parity[f - k] from there on
+uint8_t* frag(uint8_t** data, uint8_t** parity, unsigned k, unsigned f)
+{
+    return f < k ? data[f] : parity[f - k];
+}
+
+FragMap frag_map(const RsFnt* fec)
+{
+    return FragMap(fec->type, fec->n_data, fec->n_outputs);
+}
+
 // deserialize the FNT1 headers of every present coded fragment and point the
 // coded-fragment vector at the payloads (src/quadiron_c.cpp:160-206,246-285)
 int load_props(RsFnt* fec, uint8_t** data, uint8_t** parity, const int* missing,
                int md, std::vector<uint8_t*>& par_vec,
                std::vector<Properties>& props, bool all_ptrs)
 {
-    const unsigned k = fec->n_data, m = fec->n_parities;
-    if (fec->type == FecType::SYSTEMATIC) {
-        for (unsigned i = 0; i < m; i++) {
-            if (!missing[k + i] &&
-                props[i].fnt_deserialize(hdr(parity[i]), md / 4) == -1)
-                return -1;
-            if (!missing[k + i] || all_ptrs)
-                par_vec[i] = parity[i] ? parity[i] + md : nullptr;
-        }
-    } else {
-        for (unsigned i = 0; i < k; i++) {
-            if (!missing[i] && props[i].fnt_deserialize(hdr(data[i]), md / 4) == -1)
-                return -1;
-            if (!missing[i] || all_ptrs)
-                par_vec[i] = data[i] ? data[i] + md : nullptr;
-        }
-        for (unsigned i = 0; i < m; i++) {
-            if (!missing[k + i] &&
-                props[k + i].fnt_deserialize(hdr(parity[i]), md / 4) == -1)
-                return -1;
-            if (!missing[k + i] || all_ptrs)
-                par_vec[k + i] = parity[i] ? parity[i] + md : nullptr;
-        }
+    const FragMap map = frag_map(fec);
+    for (unsigned f = 0; f < fec->code_len; f++) {
+        const auto fs = map.slot(f);
+        if (fs.is_data)
+            continue;
+        uint8_t* p = frag(data, parity, fec->n_data, f);
+        if (!missing[f] && props[fs.slot].fnt_deserialize(hdr(p), md / 4) == -1)
+            return -1;
+        if (!missing[f] || all_ptrs)
+            par_vec[fs.slot] = p ? p + md : nullptr;
     }
     return 0;
 }
@@ -107,24 +107,24 @@ int quadiron_fnt32_encode(struct QuadironFnt32* fecp, uint8_t** data,
         const int md = md_size(block_size);
         for (unsigned i = 0; i < no; i++)
             wanted[i] = wanted_idxs[i] != 0;
-        const bool sys = fec->type == FecType::SYSTEMATIC;
-        for (unsigned i = 0; i < k; i++) {
-            data_vec[i] = data[i] + md;
-            if (!sys)
-                par_vec[i] = data[i] + md;
-        }
-        for (unsigned i = 0; i < m; i++)
-            par_vec[sys ? i : k + i] = parity[i] ? parity[i] + md : nullptr;
-        fec->encode_blocks_vertical(data_vec, par_vec, props, wanted, block_size);
-        Properties null_prop;
+        const FragMap map = frag_map(fec);
         for (unsigned i = 0; i < k; i++)
-            if ((sys ? null_prop : props[i]).fnt_serialize(hdr(data[i]), md / 4) ==
-                -1)
+            data_vec[i] = data[i] + md;
+        for (unsigned f = 0; f < k + m; f++) {
+            uint8_t* p = frag(data, parity, k, f);
+            if (!map.slot(f).is_data)
+                par_vec[map.slot(f).slot] = p ? p + md : nullptr;
+        }
+        fec->encode_blocks_vertical(data_vec, par_vec, props, wanted, block_size);
+        // a data fragment of a systematic code gets an empty header
+        Properties null_prop;
+        for (unsigned f = 0; f < k + m; f++) {
+            uint8_t* p = frag(data, parity, k, f);
+            const auto fs = map.slot(f);
+            if ((f < k || p) &&
+                (fs.is_data ? null_prop : props[fs.slot]).fnt_serialize(hdr(p), md / 4) == -1)
                 return -1;
-        for (unsigned i = 0; i < m; i++)
-            if (parity[i] &&
-                props[sys ? i : k + i].fnt_serialize(hdr(parity[i]), md / 4) == -1)
-                return -1;
+        }
         return 0;
     } catch (...) {
         return -1;

@@ -1,6 +1,7 @@
 """Shared test helpers: ctypes access to the CPU oracle (test infrastructure)
 and golden-fixture loading.  Product code never imports this module."""
 import ctypes as C
+import functools
 import glob
 import os
 import subprocess
@@ -208,6 +209,25 @@ def craft_oor_columns(k, m, sys_, data_rows, rng, n_cols, rows=None, col_range=N
         d0 = ((65536 - b[i]) % Q) * pow(a[i], Q - 2, Q) % Q
         if d0 < 65536:
             data_rows[0, j] = d0
+
+
+@functools.lru_cache(maxsize=None)
+def retry_block(sys_):
+    """The block of the facade's retry tests, computed once per code type and
+    read-only: RS(4, 4) on 512 words, whose first-attempt bucket capacity is
+    64 + 512 // 512 = 65, with 100 columns of output row r crafted to 65536.
+    Returns (data bytes (k, 1024), oracle outputs, oor (n_outputs, 128),
+    counts, r, first-attempt capacity)."""
+    k, m, words = 4, 4, 512
+    rng = np.random.default_rng(4100 + int(sys_))
+    lanes = rng.integers(0, 65536, (k, words), dtype=np.uint16)
+    r = codec(k, m, sys_).n_outputs - 2   # not among the first k fragments
+    craft_oor_columns(k, m, sys_, lanes, rng, 100, rows=[r])
+    data = lanes.view(np.uint8).reshape(k, 2 * words)
+    outs, oor, cnt = oracle_encode_blocks(k, m, sys_, data, cap=128)
+    for a in (data, outs, oor, cnt):
+        a.setflags(write=False)
+    return data, outs, oor, cnt, r, 64 + words // 512
 
 
 def _solve_mod(A, b):

@@ -7,7 +7,7 @@ import pytest
 
 from qi_testlib import (Q, check_windows_vs_oracle, chunk_windows, codec,
                         craft_dense_oor, craft_oor_columns, golden_names, load, oracle,
-                        oracle_decode_blocks, oracle_encode_blocks)
+                        oracle_decode_blocks, oracle_encode_blocks, retry_block)
 
 pytestmark = pytest.mark.gpu
 
@@ -178,6 +178,47 @@ def test_cabi_multi_chunk_block_vs_oracle(hip_lib, k, m, sys_):
         assert (x == y).all()
     for i in range(k):
         assert (D[i][md:] == lanes[i].view(np.uint8)).all()
+
+
+@pytest.mark.parametrize("sys_", [0, 1])
+def test_block_encode_retry_vs_oracle(hip_lib, sys_):
+    """One output row of a 512-word block holds more marks than the first
+    attempt's buckets (64 + words / 512 = 65): the block encode runs again
+    with the exact capacity, and outputs, counts and ascending marks equal
+    the oracle's."""
+    k, m = 4, 4
+    data, o_out, o_oor, o_cnt, r, first_cap = retry_block(sys_)
+    assert first_cap < o_cnt[r] <= 128 and o_cnt.max() <= 128, o_cnt
+    outs, oor, cnt = fec_encode(hip_lib, k, m, sys_, data, 128)
+    assert (outs == o_out).all()
+    assert (cnt == o_cnt).all(), (cnt, o_cnt)
+    assert (oor == o_oor).all()   # ascending, zero past the counts
+
+
+def test_pipeline_chunk_redo_vs_oracle(hip_lib):
+    """A block of two pipeline chunks (4 MiB + 1 KiB per fragment) whose
+    first chunk holds more marks on one output row than a chunk's buckets
+    (64 + 2^21 / 512 = 4160): the pipeline redoes that chunk synchronously
+    with the exact capacity and goes on; the second chunk's marks follow at
+    their absolute offsets."""
+    k, m, r = 4, 4, 6
+    chunk = 2**21
+    words = chunk + 512
+    rng = np.random.default_rng(4300)
+    lanes = rng.integers(0, 65536, (k, words), dtype=np.uint16)
+    _craft(k, m, 0, lanes, rng, 4300, rows=[r], col_range=(0, chunk))
+    _craft(k, m, 0, lanes, rng, 12, rows=[r], col_range=(chunk, words))
+    data = lanes.view(np.uint8).reshape(k, 2 * words)
+    cap = 8192
+    o_out, o_oor, o_cnt = oracle_encode_blocks(k, m, 0, data, cap)
+    marks = o_oor[r, :o_cnt[r]]
+    assert (marks < chunk).sum() > 64 + chunk // 512, (marks < chunk).sum()
+    assert (marks >= chunk).sum() >= 6 and o_cnt.max() <= cap
+    outs, oor, cnt = fec_encode(hip_lib, k, m, 0, data, cap)
+    assert cnt[r] == o_cnt[r] and (oor[r, :cnt[r]] == marks).all()
+    assert (cnt == o_cnt).all() and (oor == o_oor).all()
+    assert (outs == o_out).all()
+    check_windows_vs_oracle(k, m, 0, data, outs, oor, cnt, chunk_windows(words))
 
 
 def test_cabi_word_size_1_rejected(hip_lib):

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from qi_testlib import (craft_dense_oor, craft_oor_columns, decode_matrix,
-                        generator_matrix, matvec_mod, oracle_encode_blocks, row_scale)
+                        generator_matrix, matvec_mod, oracle_encode_blocks, retry_block,
+                        row_scale)
 
 pytestmark = pytest.mark.gpu
 
@@ -399,6 +400,31 @@ def test_fec_repair_blocks_vs_oracle(sys_, targets, extra):
         fec.repair_blocks(drows, pars, oor, cnt, miss, [present[0]])
     with pytest.raises(ValueError):
         fec.repair_blocks(drows, pars, oor, cnt, miss, [])
+
+
+@pytest.mark.parametrize("sys_", [0, 1])
+def test_fec_repair_blocks_retry(sys_):
+    """The single target holds more marks than the first attempt's output
+    buckets (64 + words / 512 = 65): Fec.repair_blocks runs the repair again
+    with the exact capacity; the row and its ascending marks equal the
+    oracle's."""
+    import quadiron_amd as qa
+    _torch()
+    k, m = 4, 4
+    data, outs, oor, cnt, r, first_cap = retry_block(sys_)
+    assert first_cap < cnt[r] <= 128 and cnt.max() <= 128, cnt
+    target = k + r if sys_ else r
+    miss = np.zeros(k + m, np.int32)
+    miss[target] = 1
+    pars = [None if i == r else outs[i].copy() for i in range(outs.shape[0])]
+    drows = [data[i].copy() for i in range(k)] if sys_ else None
+    fec = qa.Fec(k, m, bool(sys_))
+    res = fec.repair_blocks(drows, pars, oor, cnt, miss, [target], out_cap=128)
+    assert res is not None
+    rows, o_oor, o_cnt = res
+    assert (rows[0] == outs[r]).all(), np.flatnonzero(rows[0] != outs[r])[:8]
+    assert o_cnt[0] == cnt[r], (o_cnt[0], cnt[r])
+    assert (o_oor[0, :o_cnt[0]] == oor[r, :cnt[r]]).all()  # ascending
 
 
 @pytest.mark.parametrize("k,m,sys_", [(16, 48, 0), (16, 48, 1), (6, 3, 1)])

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from qi_testlib import (craft_dense_oor, craft_oor_columns, decode_matrix, generator_matrix,
-                        matvec_mod, oracle_encode_blocks)
+                        matvec_mod, oracle_encode_blocks, retry_block)
 
 pytestmark = pytest.mark.gpu
 
@@ -447,6 +447,39 @@ def test_verify_errors():
 
 
 # ---- upper layers -------------------------------------------------------
+
+@pytest.mark.parametrize("sys_", [0, 1])
+def test_fec_verify_blocks_retry(sys_):
+    """Every fragment present; one checked fragment recomputes to 65536 in
+    more columns than the first attempt's work buckets hold (64 + words / 512
+    = 65): Fec.verify_blocks runs the group again with the exact capacity.
+    Clean fragments report (0, 0, none); one flipped stored word of that
+    fragment then reports one value mismatch at its column, there alone."""
+    import quadiron_amd as qa
+    _torch()
+    k, m = 4, 4
+    data, outs, oor, cnt, r, first_cap = retry_block(sys_)
+    assert first_cap < cnt[r] <= 128 and cnt.max() <= 128, cnt
+    crafted = k + r if sys_ else r
+    miss = np.zeros(k + m, np.int32)
+    checked = list(range(k, k + m))   # the basis is the first k fragments
+    assert crafted in checked
+    pars = [outs[i].copy() for i in range(outs.shape[0])]
+    drows = [data[i].copy() for i in range(k)] if sys_ else None
+    fec = qa.Fec(k, m, bool(sys_))
+    res = fec.verify_blocks(drows, pars, oor, cnt, miss)
+    assert res is not None
+    for f in range(k + m):
+        assert res[f].tolist() == ([0, 0, NONE] if f in checked else [-1, -1, -1]), (f, res[f])
+    col = next(c for c in range(100, 512) if c not in set(oor[r, :cnt[r]].tolist()))
+    pars[r].view(np.uint16)[col] ^= 0x0400
+    res = fec.verify_blocks(drows, pars, oor, cnt, miss)
+    assert res is not None
+    for f in range(k + m):
+        exp = ([1, 0, col] if f == crafted else [0, 0, NONE] if f in checked
+               else [-1, -1, -1])
+        assert res[f].tolist() == exp, (f, res[f])
+
 
 @pytest.mark.parametrize("k,m,sys_", [(6, 3, 1), (16, 48, 0), (16, 100, 0)])
 def test_fec_verify_blocks(k, m, sys_):
