@@ -379,6 +379,17 @@ def matvec_mod(M, X):
     return Y.astype(np.int64) % Q
 
 
+def repair_matrix(k, m, sys_, ids, targets):
+    """(R, k) int64, entries 0..65536: row j rebuilds fragment targets[j]
+    from the symbols received at `ids` -- the rows `targets` of the full
+    generator (systematic: the k identity rows on top of the parity rows)
+    times decode_matrix(ids).  What repair_ctx_kernel builds on the device."""
+    G = generator_matrix(k, m, sys_)
+    if sys_:
+        G = np.concatenate([np.eye(k, dtype=np.int64), G])
+    return matvec_mod(G[np.asarray(targets, np.int64)], decode_matrix(k, m, sys_, ids))
+
+
 def split_i8_np(M):
     """matrix_pack.h split_i8: canonical c -> (a, b) in [-128, 127] with
     c = 256 a + b mod q (every residue but balanced 32640)."""
@@ -510,30 +521,132 @@ def pattern_rows(k, P):
     return X.astype(np.uint16)
 
 
-def craft_received(k, m, sys_, ids, cols, rng, n_spread=8):
+def craft_received(k, m, sys_, ids, cols, rng, n_spread=8, against=None, no_mark_rows=(),
+                   extra_marks=None):
     """Decode-side extremes inside valid use: received symbols r crafted
     against decode_matrix(ids) (every 8th column with its one to three
     largest-|c| entries at 65536, the true maximum of a received symbol,
     which arrives as an OOR mark; systematic: parity positions only, data
     rows carry no marks), d = M r mod q their data.  A column whose data
     holds a 65536 is not representable and is replaced by random data.
+
+    against: an (R, k) matrix over the same received positions (a
+    repair_matrix of the ids) whose rows the symbols are crafted against
+    instead; d still comes from the decode matrix.  Then, besides,
+      - extra_marks, a (k, cols) bool mask of markable positions, are
+        received 65536 values on top of the crafted ones;
+      - column 4 + 8 n is crafted for the n-th (target, mode) pair over the
+        targets outside no_mark_rows (the rows whose output cannot be 65536:
+        a systematic code's data rows), in craft_columns' order, and then one
+        of its symbols is solved so that this target's output A[t] r is
+        exactly 65536: the one at the markable position with the smallest
+        non-zero |balanced c| in the row crafted against (a solved 65536 is
+        an input mark there, which a markable position can carry).  The other
+        k - 1 symbols keep their extreme values, so the output mark sits in a
+        column within one term of the bound.
     Returns (d (k, cols) uint16, r (k, cols) int64 as received, kept (cols)
-    bool, M, meta)."""
+    bool, M, meta, solved (cols) int64: the solved position, -1 in a column
+    not altered)."""
     ids = np.asarray(ids, np.int64)
     M = decode_matrix(k, m, sys_, ids)
-    r, meta = craft_columns(M, extreme_targets(M, n_spread), ALL_MODES, cols)
+    A = M if against is None else np.asarray(against, np.int64)
+    tg = extreme_targets(A, n_spread)
+    r, meta = craft_columns(A, tg, ALL_MODES, cols)
     markable = np.flatnonzero(ids >= k) if sys_ else np.arange(k)
     for n, j in enumerate(range(0, cols, 8)):
         t, s, _ = meta[j]
-        mag = np.abs(balanced_np(M[t] * s % Q))[markable]
+        mag = np.abs(balanced_np(A[t] * s % Q))[markable]
         top = markable[np.argsort(-mag, kind="stable")[:1 + n % 3]]
         r[top, j] = 65536
+    solved = np.full(cols, -1, np.int64)
+    if against is not None:
+        if extra_marks is not None:
+            assert not np.delete(extra_marks, markable, axis=0).any()
+            r[extra_marks] = 65536
+        out_tg = [(t, s) for t, s in tg if t not in no_mark_rows]
+        for n, j in enumerate(range(4, cols, 8) if out_tg and len(markable) else ()):
+            i = n % len(out_tg)
+            t, s = out_tg[i]
+            mode = ALL_MODES[(i + n // len(out_tg)) % len(ALL_MODES)]
+            row = A[t] * s % Q
+            col = np.where(r[:, j] == 65536, 65536, craft_column(row, mode))
+            meta[j] = (t, s, mode)
+            mag = np.abs(balanced_np(row))[markable]
+            for p in markable[np.argsort(mag, kind="stable")]:
+                if row[p] == 0 or col[p] == 65536:
+                    continue
+                rest = int(A[t] @ col) - int(A[t, p] * col[p])
+                col[p] = (65536 - rest) % Q * pow(int(A[t, p]), Q - 2, Q) % Q
+                solved[j] = p
+                break
+            r[:, j] = col
     d = matvec_mod(M, r)
     kept = (d < 65536).all(axis=0)
     nrep = int((~kept).sum())
     if nrep:
         d[:, ~kept] = rng.integers(0, 65536, (k, nrep))
-    return d.astype(np.uint16), r, kept, M, meta
+    return d.astype(np.uint16), r, kept, M, meta, solved
+
+
+@functools.lru_cache(maxsize=None)
+def repair_case(k, m, sys_, R, need_scale=False):
+    """A seeded repair of R fragments: (ids (k) ascending, targets (R) in
+    seeded order, their repair_matrix), read-only.  Systematic: the targets
+    hold data and parity rows (min(k, R) // 2 data rows) and the ids both
+    regions.  need_scale: the first seed whose matrix has a row that needs
+    pack_row's scale (five residues are not coef_ok, so a row of k entries
+    needs one with probability about 5 k / 65537)."""
+    n = k + m
+    for seed in range(200):
+        rng = np.random.default_rng([k, m, sys_, R, seed])
+        if sys_ and R >= 2:
+            a = min(k, R) // 2
+            tg = np.concatenate([rng.choice(k, a, replace=False),
+                                 k + rng.choice(m, R - a, replace=False)])
+        else:
+            tg = rng.choice(n, R, replace=False)
+        tg = rng.permutation(tg)
+        ids = np.sort(rng.choice(np.setdiff1d(np.arange(n), tg), k, replace=False))
+        if sys_ and not ((ids < k).any() and (ids >= k).any()):
+            continue
+        M = repair_matrix(k, m, sys_, ids, tg)
+        if need_scale and coef_ok_np(M).all():
+            continue
+        for a in (ids, tg, M):
+            a.setflags(write=False)
+        return ids, tg, M
+    raise AssertionError("no seed gives such a repair")
+
+
+class CraftedRepair:
+    """repair_case(k, m, sys, R) and the `cols` columns craft_received crafts
+    against its matrix A (read-only; one per shape, shared by the tests):
+    ids, targets, A, d, r, kept, meta, solved as craft_received returns them,
+    data_rows (the rows of A that rebuild a systematic data row) and y = A r,
+    the rebuilt symbols in 0..65536.  dense: the first `dense` columns carry
+    one more received 65536 each, at a seeded markable position."""
+
+    def __init__(self, k, m, sys_, R, cols, dense=0):
+        self.ids, self.targets, self.A = repair_case(k, m, sys_, R, R >= 32 and k >= 64)
+        self.data_rows = tuple(np.flatnonzero(self.targets < k)) if sys_ else ()
+        rng = np.random.default_rng([k, m, sys_, R, cols, dense])
+        extra = None
+        if dense:
+            markable = np.flatnonzero(self.ids >= k) if sys_ else np.arange(k)
+            extra = np.zeros((k, cols), bool)
+            extra[rng.choice(markable, dense), np.arange(dense)] = True
+        self.d, self.r, self.kept, _, self.meta, self.solved = craft_received(
+            k, m, sys_, self.ids, cols, rng, against=self.A, no_mark_rows=self.data_rows,
+            extra_marks=extra)
+        self.y = matvec_mod(self.A, self.r)
+        self.share = 1 - self.kept.mean()
+        for a in (self.d, self.r, self.kept, self.solved, self.y):
+            a.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_repair(k, m, sys_, R, cols, dense=0):
+    return CraftedRepair(k, m, sys_, R, cols, dense)
 
 
 # ------------------------------------------------------------------------

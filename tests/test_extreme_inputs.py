@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 
 from qi_testlib import (ALL_MODES, Q, balanced_np, closed_form, coef_ok_np, craft_column,
-                        craft_columns, craft_oor_columns, craft_received, decode_matrix,
-                        extreme_targets, generator_matrix, matvec_mod, model_sums,
-                        oracle_encode_blocks, pattern_rows, row_scale, split_i8_np)
+                        craft_columns, craft_oor_columns, craft_received, crafted_repair,
+                        decode_matrix, extreme_targets, generator_matrix, matvec_mod,
+                        model_sums, oracle_encode_blocks, pattern_rows, row_scale,
+                        split_i8_np)
 
 SHAPES = [(16, 48, 0), (100, 50, 1), (200, 56, 0), (640, 384, 0)]
 COLS = 512
@@ -155,7 +156,8 @@ def test_decode_side_construction_keeps_its_columns(k, m, sys_):
     marks, and hold the crafted received symbols."""
     rng = np.random.default_rng(k + 7)
     ids = _ids(k, m, 100 * k + m)
-    d, r, kept, M, meta = craft_received(k, m, sys_, ids, COLS, rng)
+    d, r, kept, M, meta, solved = craft_received(k, m, sys_, ids, COLS, rng)
+    assert (solved == -1).all()
     share = 1 - kept.mean()
     print(f"\n({k},{m},{sys_}): {100 * share:.1f} % of {COLS} columns replaced, "
           f"{int((r[:, kept] == 65536).sum())} marks kept")
@@ -165,6 +167,104 @@ def test_decode_side_construction_keeps_its_columns(k, m, sys_):
     cw = matvec_mod(_gen(k, m, sys_), d)
     cw = np.concatenate([d.astype(np.int64), cw]) if sys_ else cw
     assert (cw[ids][:, kept] == r[:, kept]).all()
+
+
+# k, m, sys, R: the repairs tests/test_gpu_extremes.py runs (R = min(64, m),
+# and at k = 256 one live row in the first and in a second 16-row block)
+REPAIR_SHAPES = [(16, 48, 0, 48), (32, 32, 0, 32), (64, 960, 0, 64), (128, 128, 0, 64),
+                 (256, 768, 0, 64), (256, 768, 0, 1), (256, 768, 0, 17),
+                 (16, 48, 1, 48), (100, 50, 1, 50), (200, 56, 1, 56)]
+
+
+def _target_rows(k, m, sys_, c, cols):
+    """The oracle's encode of c.d on the target rows: per target its symbols
+    (cols) u16 and its marks (a data target: the data row, no marks)."""
+    outs, oor, cnt = oracle_encode_blocks(k, m, sys_, c.d.view(np.uint8).reshape(k, 2 * cols),
+                                          cols)
+    outs = outs.view(np.uint16)
+    for t in c.targets:
+        if sys_ and t < k:
+            yield c.d[t], []
+        else:
+            sl = t - k if sys_ else t
+            yield outs[sl], oor[sl, :cnt[sl]].tolist()
+
+
+@pytest.mark.parametrize("k,m,sys_,R", REPAIR_SHAPES)
+def test_repair_side_construction(k, m, sys_, R):
+    """craft_received against a repair matrix A (qi_testlib crafted_repair):
+      - A is the oracle's: A r mod q equals the oracle's encode of the decoded
+        data on the target rows, symbols and marks, on every kept column;
+      - a crafted column without a mark that was not altered reaches the
+        closed form on the raw or scaled row it was crafted against, exactly;
+      - a column altered for an output mark does so once its solved symbol is
+        put back, and as it stands is within the replaced term of it: two
+        values of c (x - 32768) differ by at most 65536 |c|; two values of a
+        byte-plane term, h' and l' in [-128, 127], by at most 255 |coefficient|
+        (D0: a, D1: b, D2: both), bounded here by 2 * 128 (|a| + |b|), twice
+        the largest single term (compared where the solved symbol is no mark:
+        a 65536 has no byte planes);
+      - at most 5 % of the columns are replaced, and every crafted target that
+        can hold one has an output mark in a kept column."""
+    c = crafted_repair(k, m, sys_, R, COLS)
+    A, r = c.A, c.r
+    assert A.shape == (R, k) and A.min() >= 0 and A.max() <= 65536
+    assert (r[:, c.kept] == 65536).sum() > 0
+    assert c.share <= 0.05
+    cols = np.flatnonzero(c.kept)
+    for j, (exp, marks) in enumerate(_target_rows(k, m, sys_, c, COLS)):
+        assert ((c.y[j, cols] & 0xFFFF) == exp[cols]).all(), j
+        assert [w for w in marks if c.kept[w]] == cols[c.y[j, cols] == 65536].tolist(), j
+    top = {"dot": 0, "d2": 0, "d0": 0, "d1": 0}
+    n_altered = 0
+    for j, (t, s, mode) in enumerate(c.meta):
+        row = A[t] * s % Q
+        col = r[:, j].copy()
+        p = c.solved[j]
+        if p >= 0:
+            n_altered += 1
+            assert j % 8 == 4 and t not in c.data_rows and c.y[t, j] == 65536
+            col[p] = craft_column(row, mode)[p]
+        else:
+            assert j % 8 != 4 or len(c.data_rows) == R
+        if (col == 65536).any():
+            assert j % 8 == 0
+            continue
+        want = closed_form(row, mode)
+        sums = model_sums(row, col[:, None])
+        for key, w in want.items():
+            assert int(sums[key][0]) == w, (j, t, s, mode, key)
+            top[key] = max(top[key], abs(w))
+        if p >= 0 and r[p, j] < 65536:
+            a, b = (abs(int(v[p])) for v in split_i8_np(row))
+            bound = 65536 * abs(int(balanced_np(row)[p])) if mode.startswith("dot") \
+                else 2 * 128 * (a + b)
+            got = model_sums(row, r[:, j:j + 1])
+            for key, w in want.items():
+                assert abs(int(got[key][0]) - w) <= bound, (j, t, s, mode, key)
+    assert n_altered == len(range(4, COLS, 8))
+    for t in {t for t, _ in extreme_targets(A)} - set(c.data_rows):
+        hit = [j for j in cols if c.solved[j] >= 0 and c.meta[j][0] == t]
+        assert hit and (c.y[t, hit] == 65536).all(), t
+    need = np.flatnonzero(~coef_ok_np(A).all(axis=1))
+    print(f"\n({k},{m},{sys_}) R={R}: {100 * c.share:.1f} % of {COLS} columns replaced, "
+          f"{len(need)} rows need a scale, max |dot| {top['dot']}, |D2| {top['d2']}, "
+          f"|D0| {top['d0']}, |D1| {top['d1']}")
+
+
+@pytest.mark.parametrize("k,m", [(256, 768), (64, 960)])
+def test_repair_matrix_rows_that_need_a_scale(k, m):
+    """The 64-row repair matrices of these codes hold rows that pack_row must
+    scale, and row_scale finds their scale."""
+    A = crafted_repair(k, m, 0, 64, COLS).A
+    need = np.flatnonzero(~coef_ok_np(A).all(axis=1))
+    assert len(need) >= 1
+    tg = extreme_targets(A)
+    for t in need:
+        s = row_scale(A[t])
+        assert s >= 2 and coef_ok_np(A[t] * s % Q).all()
+        assert abs(int(balanced_np(pow(s, Q - 2, Q)))) <= 32766
+        assert (int(t), 1) in tg and (int(t), s) in tg
 
 
 def test_pattern_rows():

@@ -7,16 +7,21 @@ KS = 16 up and carried over two K chunks at KS = 40, the NTT engine's lazy
 are a random walk.  These tests feed columns crafted from the codes' own
 matrices (qi_testlib craft_columns; tests/test_extreme_inputs.py shows on
 the CPU that they reach what they claim) and the 0x00 / 0xFF / 0x80 / 0x7F
-planes stored files are full of.  Each case names the kernel family it is
-there for and asserts that the plan routes to it.  Run with -m gpu."""
+planes stored files are full of.  Fused repair and verify get the same from
+columns crafted against their own R x k matrix (qi_testlib crafted_repair),
+with the helpers of test_gpu_repair.py and test_gpu_verify.py.  Each case
+names the kernel family it is there for and asserts that the plan routes to
+it.  Run with -m gpu."""
 import functools
 
 import numpy as np
 import pytest
 
-from qi_testlib import (ALL_MODES, craft_columns, craft_received, extreme_targets,
-                        generator_matrix, oracle_decode_blocks, oracle_encode_blocks,
-                        pattern_rows)
+from qi_testlib import (ALL_MODES, craft_columns, craft_received, crafted_repair,
+                        extreme_targets, generator_matrix, oracle_decode_blocks,
+                        oracle_encode_blocks, pattern_rows)
+from test_gpu_repair import _encode_oracle, _repair_and_check, _slot
+from test_gpu_verify import NONE, Stripes, _check as _verify_check
 
 pytestmark = pytest.mark.gpu
 
@@ -230,7 +235,7 @@ def test_decode_extremes_vs_oracle(k, m, sys_, P, ids_kind, fam):
     _routes(plan, P, "decode", fam)
     rng = np.random.default_rng(77 * k + m + P)
     ids = _ids_for(ids_kind, rng, k, m)
-    d, r, kept, _, _ = craft_received(k, m, sys_, ids, P, rng)
+    d, r, kept, _, _, _ = craft_received(k, m, sys_, ids, P, rng)
     share = 1 - kept.mean()
     print(f"replaced {100 * share:.1f} % of {P} columns")
     assert share <= 0.05
@@ -251,3 +256,163 @@ def test_decode_extremes_vs_oracle(k, m, sys_, P, ids_kind, fam):
         n_marks += len(want)
     assert n_marks > 0
     b.check_decode(np.stack([ids, ids]))
+
+
+# Fused repair and verify.  Their kernels are instantiations of their own
+# (the _both epilogue records output marks, the _verify one compares with the
+# stored row), their matrix is the R x k Lagrange matrix repair_ctx_kernel
+# builds and packs on the device, and a repair at 128 < k <= 256 is all that
+# reaches the KS = 16 geometry with one row block per wave.  {} is _both or
+# _verify.
+_OS16 = "matrix_os_kernel{}<16, 8, 1, false>"
+REPAIR_CASES = [
+    # the matrix cores, one whole 1024-column tile, the largest k of each
+    # K-step; at k = 256 also 15 dead rows (R = 1) and a second row block
+    # with one live row (R = 17)
+    (16, 48, 0, 1024, 48, "matrix_mfma_kernel{}<1,"),
+    (32, 32, 0, 1024, 32, "matrix_mfma_kernel{}<2,"),
+    (64, 960, 0, 1024, 64, "matrix_os_kernel{}<4, 4, 1, false>"),
+    (128, 128, 0, 1024, 64, "matrix_os_kernel{}<8, 8, 1, false>"),
+    (256, 768, 0, 1024, 64, _OS16),
+    (256, 768, 0, 1024, 1, _OS16),
+    (256, 768, 0, 1024, 17, _OS16),
+    # systematic: data and parity rows among the targets and among the ids
+    # (two source regions)
+    (16, 48, 1, 1024, 48, "matrix_mfma_kernel{}<1,"),
+    (100, 50, 1, 1024, 50, "matrix_os_kernel{}<8, 8, 1, true>"),
+    (200, 56, 1, 1024, 56, "matrix_os_kernel{}<16, 8, 1, true>"),
+    # the dot2 kernel (a ragged width below one tile)
+    (16, 48, 0, 300, 48, "matrix_kernel{}<8,"),
+    (128, 128, 0, 300, 64, "matrix_kernel{}<64,"),
+    (256, 768, 0, 300, 64, "matrix_kernel{}<128,"),
+    (200, 56, 1, 300, 56, "matrix_kernel{}<128,"),
+]
+
+
+def _crafted_stripes(k, m, sys_, P, R, dense=0):
+    """The inputs of a repair / verify case, checked before any launch.
+    Stripe 0's data is what received symbols crafted against the repair
+    matrix decode to (qi_testlib crafted_repair: the accumulator extremes of
+    its rows, input marks at the largest coefficients, and columns one term
+    off the extreme whose target is exactly 65536), stripe 1's pattern_rows;
+    the coded rows and buckets are the oracle's encode of that data.  On the
+    kept columns the oracle's received rows and marks are the crafted ones,
+    and its target rows hold the crafted output marks.
+    Returns (crafted, data (S, k, P), oracle encode per stripe)."""
+    c = crafted_repair(k, m, sys_, R, P, dense)
+    print(f"replaced {100 * c.share:.1f} % of {P} columns")
+    assert c.share <= 0.05
+    data = np.stack([c.d, pattern_rows(k, P)])
+    enc = _encode_oracle(k, m, sys_, data)
+    outs, oor, cnt = enc[0]
+    cols = np.flatnonzero(c.kept)
+    full = np.concatenate([c.d, outs]) if sys_ else outs
+    assert (full[c.ids][:, cols] == (c.r[:, cols] & 0xFFFF)).all()
+
+    def marks(fid):   # the oracle's, on the kept columns
+        sl = _slot(k, sys_, int(fid))
+        got = np.zeros(0, np.int64) if sl is None else oor[sl, :cnt[sl]].astype(np.int64)
+        return got[c.kept[got]]
+    n_in = n_out = 0
+    for pos, fid in enumerate(c.ids):
+        want = cols[c.r[pos, cols] == 65536]
+        assert np.array_equal(marks(fid), want), (pos, fid)
+        n_in += len(want)
+    for j, t in enumerate(c.targets):
+        want = cols[c.y[j, cols] == 65536]
+        assert np.array_equal(marks(t), want), (j, t)
+        n_out += int((c.solved[want] >= 0).sum())
+    assert n_in > 0 and n_out > 0, (n_in, n_out)
+    return c, data, enc
+
+
+def _both_stripes(a):
+    return np.ascontiguousarray(np.stack([a, a]), np.uint16)
+
+
+@pytest.mark.parametrize("k,m,sys_,P,R,fam", REPAIR_CASES)
+def test_repair_extremes_vs_oracle(k, m, sys_, P, R, fam):
+    """Every rebuilt row, count and sorted mark list of both stripes equals
+    the oracle's output for that target (a data target: the data row, no
+    marks), over the whole block, from a context buffer that held garbage."""
+    import quadiron_amd as qa
+    plan = qa.Plan(k, m, sys_)
+    names = plan.repair_kernels(R, P)
+    print(f"\n{(k, m, sys_, P, R)}: {names}")
+    assert fam.format("_both") in names, (fam, names)
+    c, data, enc = _crafted_stripes(k, m, sys_, P, R)
+    _repair_and_check(plan, k, m, sys_, data, enc, _both_stripes(c.ids),
+                      _both_stripes(c.targets))
+    assert plan.take_error() == 0
+
+
+@pytest.mark.parametrize("k,m,sys_,P,R,fam", REPAIR_CASES)
+def test_verify_extremes(k, m, sys_, P, R, fam):
+    """The same stored rows, checked: clean, no (stripe, check) reports a
+    mismatch -- a spurious one at a crafted column is what an accumulator
+    error would produce.  Then every check row that has a crafted column
+    without a mark has one bit of its stored word flipped there, and one row
+    loses one stored output mark: one value mismatch per flipped row with
+    `first` at its column, one mark mismatch for the row that lost its mark
+    (`first` the smaller of its two columns), and nothing anywhere else."""
+    import quadiron_amd as qa
+    plan = qa.Plan(k, m, sys_)
+    names = plan.verify_kernels(R, P)
+    print(f"\n{(k, m, sys_, P, R)}: {names}")
+    assert fam.format("_verify") in names, (fam, names)
+    c, data, _ = _crafted_stripes(k, m, sys_, P, R)
+    st = Stripes(k, m, sys_, data)
+    basis, checks = _both_stripes(c.ids), _both_stripes(c.targets)
+    evm, emm, efirst = _verify_check(plan, st, basis, checks)
+    assert not evm.any() and not emm.any() and (efirst == NONE).all()
+    cols = np.flatnonzero(c.kept)
+    plain = [j for j in cols if c.solved[j] < 0 and (c.r[:, j] < 65536).all()]
+    want_vm, want_mm = np.zeros((S, R), int), np.zeros((S, R), int)
+    want_first = np.full((S, R), NONE)
+    for t in sorted({t for t, _, _ in c.meta}):
+        j = next((j for j in plain if c.meta[j][0] == t and c.y[t, j] < 65536), None)
+        if j is not None:
+            st.stored_row(0, int(c.targets[t]))[j] ^= 1 << (j % 16)
+            want_vm[0, t], want_first[0, t] = 1, j
+    assert want_vm.any()
+    j = next(j for j in cols if c.solved[j] >= 0)
+    t = c.meta[j][0]
+    assert j in st.stored_marks(0, int(c.targets[t]))
+    st.stored_marks(0, int(c.targets[t])).discard(j)
+    want_mm[0, t], want_first[0, t] = 1, min(j, want_first[0, t])
+    evm, emm, efirst = _verify_check(plan, st, basis, checks)
+    assert (evm == want_vm).all() and (emm == want_mm).all() and (efirst == want_first).all()
+
+
+@pytest.mark.parametrize("unaligned", [False, True])
+def test_repair_verify_extremes_slow_tile(unaligned):
+    """The slow-tile forms: the first 320 columns of stripe 0 are crafted
+    columns that each carry one more received 65536 (besides the marks at the
+    largest coefficients), so the first 256 columns hold more than 256 input
+    marks, and every 8th of them is one whose target is 65536.  Whole tiles
+    on aligned rows: the matrix-core kernel redoes its own tile; rows off the
+    4-word boundary: the dot2 kernel and matrix_redo_kernel_both / _verify
+    (the plan names the aligned route only; its dot2 forms are read off a
+    ragged width).  The repair equals the oracle's -- each output mark
+    recorded exactly once -- and the clean verify reports nothing."""
+    import quadiron_amd as qa
+    k, m, P, R = 16, 48, 1024, 48
+    plan = qa.Plan(k, m, False)
+    for names, sfx in ((plan.repair_kernels(R, P), "_both"),
+                       (plan.verify_kernels(R, P), "_verify")):
+        print(f"\n{(k, m, 0, P, R)}: {names}")
+        assert f"matrix_mfma_kernel{sfx}<1," in names
+    for names, sfx in ((plan.repair_kernels(R, P - 1), "_both"),
+                       (plan.verify_kernels(R, P - 1), "_verify")):
+        assert f"matrix_kernel{sfx}<8," in names and f"matrix_redo_kernel{sfx}" in names, names
+    c, data, enc = _crafted_stripes(k, m, 0, P, R, dense=320)
+    _, oor, cnt = enc[0]
+    in_tile = sum(int((oor[f, :cnt[f]] < 256).sum()) for f in c.ids)
+    out_tile = sum(int((oor[t, :cnt[t]] < 320).sum()) for t in c.targets)
+    print(f"{in_tile} input marks in the first 256 columns, {out_tile} output marks in 320")
+    assert in_tile > 256 and out_tile >= 320 // 8
+    basis, checks = _both_stripes(c.ids), _both_stripes(c.targets)
+    _repair_and_check(plan, k, m, 0, data, enc, basis, checks, unaligned)
+    assert plan.take_error() == 0
+    evm, emm, efirst = _verify_check(plan, Stripes(k, m, 0, data), basis, checks, unaligned)
+    assert not evm.any() and not emm.any() and (efirst == NONE).all()

@@ -7,9 +7,8 @@ here comes from the product."""
 import numpy as np
 import pytest
 
-from qi_testlib import (craft_dense_oor, craft_oor_columns, decode_matrix,
-                        generator_matrix, matvec_mod, oracle_encode_blocks, retry_block,
-                        row_scale)
+from qi_testlib import (craft_dense_oor, craft_oor_columns, oracle_encode_blocks,
+                        repair_matrix, retry_block, row_scale)
 
 pytestmark = pytest.mark.gpu
 
@@ -246,11 +245,10 @@ def _find_scaled(k, m, seed):
     """(ids, scaled target, unscaled target): a seeded search over erasure
     patterns for a repair row that needs pack_row's row scale"""
     rng = np.random.default_rng(seed)
-    G = generator_matrix(k, m, 0)
     for _ in range(40):
         ids = np.sort(rng.choice(k + m, k, replace=False))
         rest = np.setdiff1d(np.arange(k + m), ids)
-        M = matvec_mod(G[rest], decode_matrix(k, m, 0, ids))
+        M = repair_matrix(k, m, 0, ids, rest)
         sc = np.array([row_scale(r) for r in M])
         if (sc != 1).any() and (sc == 1).any():
             return (ids.astype(np.uint16), int(rest[np.flatnonzero(sc != 1)[0]]),
