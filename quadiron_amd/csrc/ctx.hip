@@ -1,7 +1,9 @@
-// Per-stripe decode contexts on the GPU for the matrix paths (k <= 256):
-// the Lagrange form of DecodeContext::init (src/fec_context.h:232-274), the
-// packed / matrix-core forms of the interpolation matrix (matrix_pack.h)
-// and the OOR route tables of decode_prepare (src/fec_base.h:1361-1404).
+// Per-stripe matrix contexts on the GPU: the decode contexts of the matrix
+// paths (k <= 640; above 256 at whole-tile widths only) and the repair
+// contexts (k <= 256).  The Lagrange form of DecodeContext::init
+// (src/fec_context.h:232-274), the packed / matrix-core forms of the
+// interpolation matrix (matrix_pack.h) and the OOR route tables of
+// decode_prepare (src/fec_base.h:1361-1404).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,7 +22,10 @@ namespace qi {
 //   mode 1: M[t][i] = Q_i(r^t)   / A'(x_i)        (systematic)
 // plus the OOR route table of the stripe (decode_prepare's props walk,
 // src/fec_base.h:1361-1404, precomputed per tile).
-// One workgroup per stripe (64 lanes for k <= 32, else 256); k <= 256.
+// k <= 128: decode_ctx_lds_kernel, one workgroup per stripe (128 threads for
+// k <= 32, else 256), the whole matrix in LDS.  k > 128: decode_ctx_kernel
+// <1024, true>, one or more workgroups per stripe.  The stages all context
+// kernels share (repair_ctx_kernel too) come first.
 // ---------------------------------------------------------------------------
 // canonical a * b mod 65537 for a, b in [0, 65536]: with 2^16 = -1 and
 // 2^32 = 1, p = p0 + p1 2^16 + p2 2^32 reduces to p0 - p1 + p2
@@ -142,11 +147,140 @@ __device__ __forceinline__ int32_t div_steps(const int32_t* c, int32_t x, int32_
     return q;
 }
 
-// NT threads: the Lagrange part runs on the first wave (lane = point); the
-// row packing and the MFMA operand tiles use every thread (NT = 256 for
-// k > 32, where they dominate and there are few stripes per launch).
+// --- the stages every context kernel shares --------------------------------
+// kcorr / rscale of row t, and kmf / rscale_mf of its matrix-core section,
+// from the sum of the row's canonical row-scaled entries (< 2^26: k <= 640)
+// and the row's balanced inverse scale rs (1 = unscaled)
+__device__ __forceinline__ void store_row_sums(int32_t* block, const MatLayout& L, int t,
+                                               uint32_t sum, int32_t rs)
+{
+    // sum mod q by one fold (2^16 = -1), then canonical
+    int32_t f = static_cast<int32_t>(sum & 0xffffu) - static_cast<int32_t>(sum >> 16);
+    f = f < 0 ? f + 65537 : f;
+    const uint32_t sq = static_cast<uint32_t>(f >= 65537 ? f - 65537 : f);
+    block[L.kcorr() + t] = static_cast<int32_t>(mulm(sq, 32768u));
+    block[L.rscale() + t] = rs;
+    if (L.KS()) {
+        block[L.kmf() + t] = static_cast<int32_t>(mulm(sq, 32896u));
+        block[L.rscale_mf() + t] = rs;
+    }
+}
+
+// The a / b byte words (split_i8, entry jb in byte jb) of entries i0 .. i0 + 3
+// of row tl of row block rb into their dwords of the three operand tiles
+// (pack_mf_dword's layout; mf: the block's tile section).  The decode
+// contexts leave out what the kernels never read: the zero halves of
+// [a | 0] and [0 | b] at KS >= 4 (matrix_mfma_kernel skips those K-steps) and
+// the [b | a] tiles at KS >= 2 (the kernels rebuild them).  ALL: every dword
+// of all three (the repair contexts).
+template <bool ALL = false>
+__device__ __forceinline__ void store_tile_words(int32_t* mf, int KS, int rb, int tl, int i0,
+                                                 uint32_t aw, uint32_t bw)
+{
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const size_t base = mf_dword_index(KS, rb, half * 16 * KS + i0, tl);
+        if (ALL || KS < 4 || half == 0)
+            mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
+        if (ALL || KS < 4 || half == 1)
+            mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
+        if (ALL || KS < 2)
+            mf[base + 256] = static_cast<int32_t>(half ? aw : bw);  // [b | a]
+    }
+}
+
+// The ids behind the k received ones, up to the section's 2 KP dwords
+__device__ __forceinline__ void clear_cids_pad(int32_t* cids, int k, int KP, int tid, int nt)
+{
+    for (int i = k + tid; i < 2 * KP; i += nt)
+        cids[i] = 0;
+}
+
+// Clears a stripe's route table (every tile's count), its slow-tile list and
+// its lazy word (lazy0: the sections the builder itself writes).  Tiles t0,
+// t0 + step, ...; `last` is the one thread that writes the two single words.
+// A context built without the buckets (ids only: init_context_dec,
+// src/fec_context.h) marks every tile unrouted (count > kRouteCap): a decode
+// given marks then scans the buckets itself.  Which threads clear, and what
+// orders the clears before the marks, is each kernel's own (DESIGN.md
+// section 4.6).
+__device__ __forceinline__ void clear_route(uint32_t* route, long long words, bool routed,
+                                            uint32_t lazy0, long long t0, int step, bool last)
+{
+    const long long ntiles = route_tiles(words);
+    const uint32_t rt0 = routed ? 0u : static_cast<uint32_t>(kRouteCap) + 1u;
+    for (long long t = t0; t < ntiles; t += step)
+        route[t * kRouteStride] = rt0;
+    if (last) {
+        route[ntiles * kRouteStride] = 0;  // the slow-tile list starts empty
+        route[lazy_word_off(words)] = lazy0;
+    }
+}
+
+// an id that is not a point of the code (not below n) raises kErrBadIds
+__device__ __forceinline__ void check_id(uint32_t id, uint32_t n, uint32_t* err)
+{
+    if (id >= n)
+        atomicOr(err, kErrBadIds);
+}
+
+// The marks of bucket bk (count c, as loaded) into the stripe's route table,
+// for the received row at position pos of the context's order: each mark
+// takes the next entry of its tile's list (position << 16 | column in tile),
+// a tile past kRouteCap entries only counts on (the decode then scans the
+// buckets).  A count above the capacity is clamped and raises
+// kErrOorTruncated; marks past the width are skipped.  PRE: entry 0 was
+// loaded ahead by the caller (ent0).  keep(tile): the caller's tile filter.
+template <bool PRE, class Keep>
+__device__ __forceinline__ void route_bucket(uint32_t* route, const Oor& oor, long long bk,
+                                             uint32_t c, uint32_t ent0, int pos, long long words,
+                                             uint32_t* err, Keep&& keep)
+{
+    if (c > static_cast<uint32_t>(oor.cap)) {
+        atomicOr(err, kErrOorTruncated);
+        c = static_cast<uint32_t>(oor.cap);
+    }
+    for (uint32_t e = 0; e < c; e++) {
+        const uint32_t w = PRE && e == 0 ? ent0 : oor.entries[bk * oor.cap + e];
+        if (w >= words || !keep(w / kRouteTile))
+            continue;
+        uint32_t* rt = route + (w / kRouteTile) * kRouteStride;
+        const uint32_t p = atomicAdd(rt, 1u);
+        if (p < static_cast<uint32_t>(kRouteCap))
+            rt[1 + p] = (static_cast<uint32_t>(pos) << 16) | (w % kRouteTile);
+    }
+}
+// (no filter: every tile)
+struct EveryTile {
+    __device__ __forceinline__ bool operator()(uint32_t) const { return true; }
+};
+
+// A slice [i0, i1) of a systematic row t: the inverses of d_i = r^t - x_i
+// from one inversion (prefix products into the row, the running inverse
+// walked back), then row[i] = fin(i, d_i, 1 / d_i); d_i = 0 (r^t is the
+// received point x_i itself) takes part as 1 and leaves the entry to fin.
+template <class Fin>
+__device__ __forceinline__ void sys_row_slice(uint32_t* row, const uint32_t* xs, uint32_t et,
+                                              int i0, int i1, Fin&& fin)
+{
+    uint32_t pre = 1;
+    for (int i = i0; i < i1; i++) {
+        const uint32_t d = subm(et, xs[i]);
+        row[i] = pre;
+        pre = mulm(pre, d ? d : 1u);
+    }
+    uint32_t inv = powm(pre, 65535u);
+    for (int i = i1 - 1; i >= i0; i--) {
+        const uint32_t d = subm(et, xs[i]);
+        const uint32_t inv_i = mulm(inv, row[i]);
+        inv = mulm(inv, d ? d : 1u);
+        row[i] = fin(i, d, inv_i);
+    }
+}
+
+// --- row packing -----------------------------------------------------------
 // pack_row (matrix_pack.h) on a group of LPR adjacent lanes (a power of 2,
-// <= 16), lane `sub` taking entries sub, sub + LPR, ...: the column scale
+// <= 32), lane `sub` taking entries sub, sub + LPR, ...: the column scale
 // 1 / A'(x_i) applied, the same row scale search (uniform in the group),
 // packed pairs, canonical `plain` entries, kcorr / rscale / kmf, and the
 // row-scaled entries written back to the LDS row for the tiles.  Entries
@@ -222,8 +356,7 @@ __device__ __forceinline__ void pack_row_grp(uint32_t* row, const uint32_t* csca
             if (dot2 && !(sub & 1)) {
                 const int32_t lo = balanced(v[m]);
                 const int32_t hi = i + 1 < kin ? balanced(odd) : 0;
-                packed[i >> 1] = static_cast<int32_t>((static_cast<uint32_t>(lo) & 0xffffu) |
-                                                      (static_cast<uint32_t>(hi) << 16));
+                packed[i >> 1] = pack_pair(lo, hi);
             }
         }
     }
@@ -231,32 +364,17 @@ __device__ __forceinline__ void pack_row_grp(uint32_t* row, const uint32_t* csca
     for (int j = (kin + 1) / 2 + sub; dot2 && j < KP; j += lpr)
         packed[j] = 0;
     sum = grp_add(sum, lpr);
-    if (sub == 0) {
-        // sum mod q by two folds (2^16 = -1), then canonical
-        int32_t f = static_cast<int32_t>(sum & 0xffffu) - static_cast<int32_t>(sum >> 16);
-        f = f < 0 ? f + 65537 : f;
-        const uint32_t sq = static_cast<uint32_t>(f >= 65537 ? f - 65537 : f);
-        block[L.kcorr() + t] = static_cast<int32_t>(mulm(sq, 32768u));
-        block[L.rscale() + t] = s == 1 ? 1 : inv_small(s);
-        if (L.KS()) {
-            block[L.kmf() + t] = static_cast<int32_t>(mulm(sq, 32896u));
-            block[L.rscale_mf() + t] = block[L.rscale() + t];
-        }
-    }
+    if (sub == 0)
+        store_row_sums(block, L, t, sum, s == 1 ? 1 : inv_small(s));
 }
 
-// The BIG contexts' packing for whole-tile widths (see decode_ctx_kernel):
-// rows t of Mt (canonical coef_t(Q_i), pitch kp, global memory) scaled by
-// the columns' 1 / A'(x_i), row-scaled when an entry breaks coef_ok (as
-// pack_row_grp: the row's scale search on its 32-lane group), summed into
-// kcorr / kmf, and written as the [a | 0], [0 | b], [b | a] operand tiles.
-// rows per chunk of the non-systematic k > 128 contexts (decode_ctx_kernel):
-// (the kernel's static LDS + the largest chunk, ctx_chunk(k) rows x k
-// entries, must fit kCtxLdsCap; launch_decode_ctx checks)
-// 64 rows = 4 row blocks per packing pass at 16 lanes per row (32 rows at 32
-// lanes: twice the passes and barriers for the same work; contexts k256
-// 120 -> 114 us, k300 179 -> 161 us, k384 219 -> 206 us); 32 rows above
-// k = 384 (a 64 x 640 chunk would not fit LDS)
+// Rows per chunk of the whole-tile k > 128 contexts (decode_ctx_kernel; the
+// kernel's static LDS + the largest chunk, ctx_chunk(k) rows x k entries,
+// must fit kCtxLdsCap: launch_decode_ctx checks).  64 rows = 4 row blocks per
+// packing pass at 16 lanes per row (32 rows at 32 lanes: twice the passes
+// and barriers for the same work; contexts k256 120 -> 114 us, k300 179 ->
+// 161 us, k384 219 -> 206 us); 32 rows above k = 384 (a 64 x 640 chunk would
+// not fit LDS)
 constexpr int kCtxChunk = 64;
 
 // a canonical entry a row may not hold unscaled (!coef_ok): the dot2
@@ -299,10 +417,14 @@ constexpr int kPackStg = 12288;
 constexpr int kTreeBuf = 2 * 512 + 4;
 static_assert(2 * kTreeBuf <= kPackStg, "tree buffers inside the packing stage");
 
-// One pass: NT / LPR rows from row block rb0 on (LPR lanes per row); row
-// t's canonical entries i0 .. i0 + 3, already column-scaled by 1 / A'(x_i),
-// from ent(t, i0, e).  stg: a row per pass row of the (aw, bw) words of each
-// group (LDS).
+// The packing of the k > 128 contexts for whole-tile widths (see
+// decode_ctx_kernel), one pass: NT / LPR rows from row block rb0 on (LPR
+// lanes per row); row t's canonical entries i0 .. i0 + 3, already
+// column-scaled by 1 / A'(x_i), from ent(t, i0, e).  A row is row-scaled when
+// an entry breaks coef_ok (as pack_row_grp: the scale search on the row's
+// lane group), summed into kcorr / kmf, and written as the [a | 0], [0 | b],
+// [b | a] operand tiles.  stg: a row per pass row of the (aw, bw) words of
+// each group (LDS).
 template <int NT, int LPR, class Ent>
 __device__ __forceinline__ void pack_tiles_pass(int rb0, const Ent& ent, const MatLayout& L,
                                 int32_t* mat, uint32_t* stg_base)
@@ -311,7 +433,7 @@ __device__ __forceinline__ void pack_tiles_pass(int rb0, const Ent& ent, const M
     // 16 lanes per row: the 64-row chunks of k <= 384; 32: k <= 640
     constexpr int MM = ((LPR <= 16 ? kMatGenMaxKin : kMatMaxKin) / 4 + LPR - 1) / LPR;
     static_assert(ROWS % 16 == 0, "whole row blocks per pass");
-    const int k = L.kin, KS = L.KS(), KH = 16 * KS, nj = KH / 4, RB = L.RB();
+    const int k = L.kin, KS = L.KS(), nj = 4 * KS, RB = L.RB();
     auto stg = [&](int r, int c) -> uint32_t& { return stg_base[r * 2 * nj + c]; };
     const int tid = threadIdx.x, sub = tid % LPR, rl = tid / LPR;
     int32_t* mf = mat + L.mf();
@@ -371,16 +493,8 @@ __device__ __forceinline__ void pack_tiles_pass(int rb0, const Ent& ent, const M
                 }
             }
             sum = grp_add(sum, LPR);
-            if (sub == 0) {
-                int32_t f = static_cast<int32_t>(sum & 0xffffu) - static_cast<int32_t>(sum >> 16);
-                f = f < 0 ? f + 65537 : f;
-                const uint32_t sq = static_cast<uint32_t>(f >= 65537 ? f - 65537 : f);
-                mat[L.kcorr() + t] = static_cast<int32_t>(mulm(sq, 32768u));
-                const int32_t rs = sc == 1 ? 1 : inv_small(sc);
-                mat[L.rscale() + t] = rs;
-                mat[L.kmf() + t] = static_cast<int32_t>(mulm(sq, 32896u));
-                mat[L.rscale_mf() + t] = rs;
-            }
+            if (sub == 0)
+                store_row_sums(mat, L, t, sum, sc == 1 ? 1 : inv_small(sc));
         } else {
             for (int jg = sub; jg < nj; jg += LPR)
                 stg(rl, 2 * jg) = stg(rl, 2 * jg + 1) = 0;
@@ -393,26 +507,17 @@ __device__ __forceinline__ void pack_tiles_pass(int rb0, const Ent& ent, const M
         for (int it = tid; it < nrb * nj * 16; it += NT) {
             const int tl = it & 15, jj = it >> 4;
             const int jg = jj % nj, rbl = jj / nj, rb = rb0 + rbl;
-            const uint32_t aw = stg(16 * rbl + tl, 2 * jg), bw = stg(16 * rbl + tl, 2 * jg + 1);
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                const int K = half * KH + 4 * jg;
-                const int ks = K >> 5, g = (K & 31) >> 3, dw = (K & 7) >> 2;
-                const size_t base =
-                    static_cast<size_t>((rb * KS + ks) * 3) * 128 + (16 * g + tl) * 2 + dw;
-                if (KS < 4 || half == 0)
-                    mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
-                if (KS < 4 || half == 1)
-                    mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
-                if (KS < 2)  // [b | a]: the kernels rebuild it at KS >= 2
-                    mf[base + 256] = static_cast<int32_t>(half ? aw : bw);
-            }
+            store_tile_words(mf, KS, rb, tl, 4 * jg, stg(16 * rbl + tl, 2 * jg),
+                             stg(16 * rbl + tl, 2 * jg + 1));
         }
         __syncthreads();
     }
 }
 
-// LDS row pitch of the context kernel's k x k matrix: 4 x odd, >= k
+// LDS row pitch of the k <= 128 and repair kernels' matrix: 4 x odd (>= k, a
+// multiple of 4 words), so the tile pass reads 16 rows x 16 bytes per wave
+// (ds_read_b128) conflict-free (the odd pitch k | 1 had SQ_LDS_BANK_CONFLICT
+// at 7.4 cycles per LDS instruction at k = 64)
 __host__ __device__ inline int ctx_pitch(int k)
 {
     return (k + 3) / 8 * 8 + 4;
@@ -466,45 +571,31 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
     __shared__ uint32_t aprime[kMatMaxKin];  // A'(x_i)
     __shared__ uint16_t pid[kMatMaxKin];     // the ids in the context's order
     __shared__ int wtot[NT / 64];
-    // k x k matrix, sized by the launch: 1 KiB at k = 16 instead of a fixed 32 KiB, which had
-    // limited the kernel to 4 workgroups per CU
+    // the whole-tile forms' row chunk, sized by the launch (none for dot2)
     extern __shared__ __attribute__((aligned(16))) uint32_t qi_ctx_lds[];
-    // row pitch = 4 x odd (>= k, a multiple of 4 words): the tile pass
-    // reads 16 rows x 16 bytes per wave (ds_read_b128) conflict-free (the
-    // odd pitch k | 1 had SQ_LDS_BANK_CONFLICT at 7.4 cycles per LDS
-    // instruction at k = 64)
     // nb blocks per stripe (the whole-tile forms only; nb = 1 otherwise):
     // block cb builds the row chunks [c0, c1) of its stripe's
     // matrix, block 0 also the ids and the route table; each computes A(x)
     // and the A'(x_i) itself (few stripes per launch left most CUs idle
     // behind one block per stripe: k300, 32 stripes, 147 us)
+    static_assert(BIG && NT == 1024, "the one form left: the k > 128 contexts");
     const int s = blockIdx.x / nb, cb = blockIdx.x - s * nb;
     const int tid = threadIdx.x;
     int32_t* mat = ctx + s * ctx_stride;
-    // BIG (128 < k <= 256): the k x k matrix (up to 256 KB) does not fit
-    // LDS; its rows live in the context's own `plain` section (pitch k),
-    // which the packing pass rewrites in place with the row-scaled entries
-    const int kp = BIG ? k : ctx_pitch(k);
-    uint32_t* Mt = BIG ? reinterpret_cast<uint32_t*>(mat + L.plain()) : qi_ctx_lds;
+    // the k x k matrix (up to 256 KB at k = 256) does not fit LDS: its rows
+    // live in the context's own `plain` section (pitch k), which the packing
+    // pass rewrites in place with the row-scaled entries (the dot2 forms;
+    // the whole-tile forms stage row chunks in LDS, below)
+    const int kp = k;
+    uint32_t* Mt = reinterpret_cast<uint32_t*>(mat + L.plain());
     int32_t* cids = mat + L.words();
     uint32_t* route = reinterpret_cast<uint32_t*>(cids + 2 * L.KP);
     const bool lead = cb == 0;  // block-uniform
-    const long long ntiles = route_tiles(words);
     if (lead) {
-        for (int i = k + tid; i < 2 * L.KP; i += NT)
-            cids[i] = 0;
-        // route table: clear, then (after the barrier below) fill; the
-        // slow-tile list behind it starts empty.  A context built without
-        // the buckets (ids only: init_context_dec, src/fec_context.h) marks
-        // every tile unrouted (count > kRouteCap): a decode given marks then
-        // scans the buckets itself
-        const uint32_t rt0 = in_oor.counts ? 0u : static_cast<uint32_t>(kRouteCap) + 1u;
-        for (long long t = tid; t < ntiles; t += NT)
-            route[t * kRouteStride] = rt0;
-        if (tid == 0) {
-            route[ntiles * kRouteStride] = 0;
-            route[lazy_word_off(words)] = 0;  // no lazily filled section yet
-        }
+        clear_cids_pad(cids, k, L.KP, tid, NT);
+        // route table: clear, then (after the barrier below) fill; no lazily
+        // filled section yet
+        clear_route(route, words, in_oor.counts != nullptr, 0u, tid, NT, tid == 0);
     }
     order_ids<NT>(ids + static_cast<long long>(s) * k, k, mode != 0 && !by_pos, pid, wtot);
     if (tid < k) {
@@ -512,8 +603,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
         xs[tid] = powm(r, id);
         if (lead) {
             cids[tid] = static_cast<int32_t>(id);
-            if (id >= static_cast<uint32_t>(n))  // not a point of the code
-                atomicOr(err, kErrBadIds);
+            check_id(id, static_cast<uint32_t>(n), err);
         }
     }
     // the route-table clears (every thread of the lead block, above) must
@@ -528,34 +618,20 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
         // slot_base; bad ids past it) have no marks here
         if (slot >= 0 && slot < in_oor.slots) {
             const long long bk = static_cast<long long>(s) * in_oor.slots + slot;
-            uint32_t c = in_oor.counts[bk];
-            if (c > static_cast<uint32_t>(in_oor.cap)) {
-                atomicOr(err, kErrOorTruncated);
-                c = static_cast<uint32_t>(in_oor.cap);
-            }
-            for (uint32_t e = 0; e < c; e++) {
-                const uint32_t w = in_oor.entries[bk * in_oor.cap + e];
-                if (w >= words)
-                    continue;
-                uint32_t* rt = route + (w / kRouteTile) * kRouteStride;
-                const uint32_t p = atomicAdd(rt, 1u);
-                if (p < static_cast<uint32_t>(kRouteCap))
-                    rt[1 + p] = (static_cast<uint32_t>(tid) << 16) | (w % kRouteTile);
-            }
+            route_bucket<false>(route, in_oor, bk, in_oor.counts[bk], 0u, tid, words, err,
+                                EveryTile{});
         }
     }
-    // A(x) = prod_i (x - x_i) on wave 0: slot u of lane d holds coefficient
-    // 64 u + d (u < nslot <= 6), lazy (folded once per step, |a| < 2^17):
-    // the shift by DPP (wave_shr:1) with the slot carry by readlane, the
-    // product as mul_lz, x_i by readlane from the lane-held points (the
-    // ds_bpermute shifts and canonical mulm of round 2 took ~620 cycles per
-    // step: 62 us of a k = 200 context).  A is monic: A[k] = 1 is set
-    // explicitly, so k = 64 u needs no extra slot.  Stored balanced.
-    // (BIG: the product tree's levels, then the split Horner chains of the
-    // A'(x_i))
-    __shared__ __attribute__((aligned(16))) uint32_t big_lds[BIG ? kPackStg : 2 * kTreeBuf];
+    // A(x) = prod_i (x - x_i), lazy (folded once per step, |a| < 2^17): the
+    // shift by DPP (wave_shr:1), the product as mul_lz, x_i by readlane from
+    // the lane-held points (the ds_bpermute shifts and canonical mulm of
+    // round 2 took ~620 cycles per step: 62 us of a k = 200 context).  A is
+    // monic: A[k] = 1 is set explicitly.  Stored balanced.  big_lds: the
+    // product tree's levels, then the split Horner chains of the A'(x_i),
+    // then the packing stage
+    __shared__ __attribute__((aligned(16))) uint32_t big_lds[kPackStg];
     int32_t(*pt)[kTreeBuf] = reinterpret_cast<int32_t(*)[kTreeBuf]>(big_lds);
-    if constexpr (BIG) {
+    {
         // k > 128: A(x) by a product tree instead of k dependent steps on one
         // wave (k = 256: 256 steps x 4 coefficient slots of DPP shifts and
         // products).  Leaves: wave w multiplies out the points [w g, w g +
@@ -643,55 +719,11 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
             A[i] = static_cast<uint32_t>(pt[cur][i]);
         if (tid == 0)
             A[k] = 1;
-    } else if (tid < 64) {  // wave 0 (wave-uniform)
-        constexpr int NS = kMatGenMaxKin / 64;
-        const int nslot = (k + 63) / 64;
-        int32_t xv[NS], au[NS];
-#pragma unroll
-        for (int u = 0; u < NS; u++) {
-            const int i = 64 * u + tid;
-            xv[u] = i < k ? balanced(xs[i]) : 0;
-            au[u] = (u == 0 && tid == 0) ? 1 : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < NS; u++) {
-            if (u >= nslot)
-                break;
-            const int cnt = min(64, k - 64 * u);
-            for (int i0 = 0; i0 < cnt; i0++) {
-                const int32_t x = __builtin_amdgcn_readlane(xv[u], i0);
-                int32_t prev[NS];
-#pragma unroll
-                for (int v = 0; v < NS; v++) {
-                    if (v >= nslot)
-                        break;
-                    prev[v] = __builtin_amdgcn_update_dpp(0, au[v], 0x138, 0xf, 0xf, false);
-                    if (v > 0) {
-                        const int32_t top = __builtin_amdgcn_readlane(au[v - 1], 63);
-                        prev[v] = tid == 0 ? top : prev[v];
-                    }
-                }
-#pragma unroll
-                for (int v = 0; v < NS; v++) {
-                    if (v >= nslot)
-                        break;
-                    au[v] = fold(prev[v] - mul_lz(au[v], x));
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NS; u++) {
-            const int i = 64 * u + tid;
-            if (u < nslot && i < k)
-                A[i] = static_cast<uint32_t>(balanced(canon_lz(au[u])));
-        }
-        if (tid == 0)
-            A[k] = 1;
     }
     __syncthreads();
-    // (the chunked BIG rows are written by a second division below)
-    const bool rows = mode == 0 && !(BIG && !dot2);
-    if (BIG && !rows) {
+    // (the chunked rows are written by a second division below)
+    const bool rows = mode == 0 && dot2;
+    if (!rows) {
         // only the A'(x_i): the derivative's coefficients d_j = (j + 1)
         // A[j + 1], then PP = NT / k threads per point, each a Horner chain
         // over a k / PP slice of them, combined with powers x^len (the one
@@ -751,7 +783,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
         if (ap == 0u)  // repeated ids
             atomicOr(err, kErrBadIds);
     }
-    if (mode != 0 && !(BIG && !dot2)) {
+    if (mode != 0 && dot2) {
         // systematic: M[t][i] = Q_i(r^t) / A'(x_i), one thread per row t,
         // with Q_i(r^t) = A(r^t) / (r^t - x_i): 0 when r^t is another
         // received point (A(r^t) = 0), A'(x_i) when it is x_i itself.  The
@@ -769,23 +801,13 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
             for (int j = k - 1; j >= 0; j--)
                 al = Ab[j] + mul_lz(al, eb);
             const uint32_t av = canon_lz(fold(al));
-            uint32_t pre = 1;
-            for (int i = 0; i < k; i++) {
-                const uint32_t d = subm(et, xs[i]);
-                row[i] = pre;
-                pre = mulm(pre, d ? d : 1u);
-            }
-            uint32_t inv = powm(pre, 65535u);
-            for (int i = k - 1; i >= 0; i--) {
-                const uint32_t d = subm(et, xs[i]);
-                const uint32_t inv_i = mulm(inv, row[i]);
-                inv = mulm(inv, d ? d : 1u);
-                row[i] = d ? mulm(av, inv_i) : aprime[i];
-            }
+            sys_row_slice(row, xs, et, 0, k, [&](int i, uint32_t d, uint32_t inv_i) {
+                return d ? mulm(av, inv_i) : aprime[i];
+            });
         }
     }
     __syncthreads();
-    if constexpr (BIG) {
+    {
         uint32_t* stg = big_lds;  // the tree's buffers are dead now
         if (!dot2) {
             // whole-tile widths: the rows in chunks of CH (ctx_chunk), this
@@ -845,20 +867,11 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
                     }
                     const uint32_t av = grp_add(term, TPR) % 65537u;  // A(r^t)
                     uint32_t* row = ch + rl * kpc;
-                    const int i0 = sub * seg, i1 = min(k, i0 + seg);
-                    uint32_t pre = 1;
-                    for (int i = i0; i < i1; i++) {
-                        const uint32_t d = subm(et, xs[i]);
-                        row[i] = pre;
-                        pre = mulm(pre, d ? d : 1u);
-                    }
-                    uint32_t inv = powm(pre, 65535u);
-                    for (int i = i1 - 1; i >= i0; i--) {
-                        const uint32_t d = subm(et, xs[i]);
-                        const uint32_t inv_i = mulm(inv, row[i]);
-                        inv = mulm(inv, d ? d : 1u);
-                        row[i] = d ? mulm(mulm(av, inv_i), cinv[i]) : 1u;
-                    }
+                    // (column-scaled: A'(x_i) / A'(x_i) = 1 where r^t = x_i)
+                    sys_row_slice(row, xs, et, sub * seg, min(k, sub * seg + seg),
+                                  [&](int i, uint32_t d, uint32_t inv_i) {
+                                      return d ? mulm(mulm(av, inv_i), cinv[i]) : 1u;
+                                  });
                 }
                 __syncthreads();
                 auto ent = [&](int t, int i0, uint32_t (&e)[4]) {
@@ -895,13 +908,13 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
         // stores cover whole 128-byte tile lines (16 rows x 2 dwords).  At
         // KS >= 4 the zero halves of [a | 0] and [0 | b] are not written:
         // matrix_mfma_kernel skips those K-steps (and never loads them).
-        const int KS = L.KS(), KH = 16 * KS, nj = KH / 4, RB = L.RB();
+        const int KS = L.KS(), nj = 4 * KS, RB = L.RB();
         int32_t* mf = mat + L.mf();
-        // BIG: the rows come from global memory; 4 items per thread have
-        // their loads in flight together (the stores to the tiles may alias
-        // the rows as far as the compiler knows, so it would not overlap
-        // the iterations itself)
-        constexpr int IB = BIG ? 4 : 1;
+        // the rows come from global memory; 4 items per thread have their
+        // loads in flight together (the stores to the tiles may alias the
+        // rows as far as the compiler knows, so it would not overlap the
+        // iterations itself)
+        constexpr int IB = 4;
         const int items = RB * nj * 16;
         for (int it0 = tid; it0 < items; it0 += IB * NT) {
             uint32_t e[IB][4];
@@ -911,17 +924,10 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
                 const int tl4 = it & 15, jj = it >> 4;
                 const int t = 16 * (jj / nj) + tl4, i0 = 4 * (jj % nj);
                 const bool live = it < items && t < L.R && i0 < k;
-                if constexpr (BIG) {  // global rows, pitch k: no 16-byte alignment
+                // (pitch k: no 16-byte alignment)
 #pragma unroll
-                    for (int jb = 0; jb < 4; jb++)
-                        e[ib][jb] = live && i0 + jb < k ? Mt[t * kp + i0 + jb] : 0u;
-                } else if (live) {
-                    const uint4 e4 = *reinterpret_cast<const uint4*>(Mt + t * kp + i0);
-                    e[ib][0] = e4.x;
-                    e[ib][1] = e4.y;
-                    e[ib][2] = e4.z;
-                    e[ib][3] = e4.w;
-                }
+                for (int jb = 0; jb < 4; jb++)
+                    e[ib][jb] = live && i0 + jb < k ? Mt[t * kp + i0 + jb] : 0u;
             }
 #pragma unroll
             for (int ib = 0; ib < IB; ib++) {
@@ -943,19 +949,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
                         }
                     }
                 }
-#pragma unroll
-                for (int half = 0; half < 2; half++) {
-                    const int K = half * KH + i0;
-                    const int ks = K >> 5, g = (K & 31) >> 3, dw = (K & 7) >> 2;
-                    const size_t base =
-                        static_cast<size_t>((rb * KS + ks) * 3) * 128 + (16 * g + tl4) * 2 + dw;
-                    if (KS < 4 || half == 0)
-                        mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
-                    if (KS < 4 || half == 1)
-                        mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
-                    if (KS < 2)  // [b | a]: the kernels rebuild it at KS >= 2
-                    mf[base + 256] = static_cast<int32_t>(half ? aw : bw);
-                }
+                store_tile_words(mf, KS, rb, tl4, i0, aw, bw);
             }
         }
     }
@@ -981,6 +975,18 @@ __global__ __launch_bounds__(NT) void decode_ctx_kernel(
 struct RPow2 {
     int32_t v[16];
 };
+// (host) the table for the code's root r, and lgn = ceil(log2 n)
+static RPow2 make_rpow2(uint32_t r, int n, int* lgn)
+{
+    RPow2 rp{};
+    uint32_t e = r;
+    for (int b = 0; b < 16; b++, e = mulmod_c(e, e))
+        rp.v[b] = balanced(e);
+    *lgn = 0;
+    while (*lgn < 16 && (1u << *lgn) < static_cast<uint32_t>(n))
+        ++*lgn;
+    return rp;
+}
 
 __device__ __forceinline__ int32_t rpow_lz(const RPow2& rp, uint32_t e, int lgn)
 {
@@ -1010,10 +1016,8 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
     uint32_t* Mt = qi_ctx_lds;
     int32_t* cids = mat + L.words();
     uint32_t* route = reinterpret_cast<uint32_t*>(cids + 2 * L.KP);
-    const long long ntiles = route_tiles(words);
 
-    for (int i = k + tid; i < 2 * L.KP; i += NT)
-        cids[i] = 0;
+    clear_cids_pad(cids, k, L.KP, tid, NT);
     // the route table belongs to the routing waves (1 .. NT / 64 - 1, while
     // wave 0 builds A(x), below): tile t to wave 1 + t % nrw, which clears
     // its count and then adds its marks -- a count cleared by another wave
@@ -1021,14 +1025,9 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
     constexpr int nrw = NT / 64 - 1;
     const int rw = (tid >> 6) - 1, rl = tid & 63;
     if (tid >= 64) {
-        // (ids only, no buckets: every tile unrouted, as decode_ctx_kernel)
-        const uint32_t rt0 = in_oor.counts ? 0u : static_cast<uint32_t>(kRouteCap) + 1u;
-        for (long long t = rw + static_cast<long long>(nrw) * rl; t < ntiles; t += 64 * nrw)
-            route[t * kRouteStride] = rt0;
-        if (tid == 64) {
-            route[ntiles * kRouteStride] = 0;  // the slow-tile list starts empty
-            route[lazy_word_off(words)] = 0;   // no lazily filled section yet
-        }
+        // (no lazily filled section yet)
+        clear_route(route, words, in_oor.counts != nullptr, 0u,
+                    rw + static_cast<long long>(nrw) * rl, 64 * nrw, tid == 64);
         __builtin_amdgcn_s_waitcnt(0);  // this wave's clears before its atomics
     }
     order_ids<NT>(ids + static_cast<long long>(s) * k, k, mode != 0 && !by_pos, pid, wtot);
@@ -1040,8 +1039,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
         xt = balanced(canon_lz(rpow_lz(rp, id, lgn)));
         xs[tid] = static_cast<uint32_t>(xt < 0 ? xt + kQ : xt);
         cids[tid] = static_cast<int32_t>(id);
-        if (id >= (1u << lgn))  // not a point of the code
-            atomicOr(err, kErrBadIds);
+        check_id(id, 1u << lgn, err);
     }
     if (tid < 64 && 64 + tid < k)
         xt1 = balanced(canon_lz(rpow_lz(rp, pid[64 + tid], lgn)));
@@ -1086,20 +1084,8 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
             if (slot < 0 || slot >= in_oor.slots)
                 continue;
             const long long bk = static_cast<long long>(s) * in_oor.slots + slot;
-            uint32_t c = in_oor.counts[bk];
-            if (c > static_cast<uint32_t>(in_oor.cap)) {
-                atomicOr(err, kErrOorTruncated);
-                c = static_cast<uint32_t>(in_oor.cap);
-            }
-            for (uint32_t e = 0; e < c; e++) {
-                const uint32_t w = in_oor.entries[bk * in_oor.cap + e];
-                if (w >= words || static_cast<int>((w / kRouteTile) % nrw) != rw)
-                    continue;
-                uint32_t* rt = route + (w / kRouteTile) * kRouteStride;
-                const uint32_t p = atomicAdd(rt, 1u);
-                if (p < static_cast<uint32_t>(kRouteCap))
-                    rt[1 + p] = (static_cast<uint32_t>(i) << 16) | (w % kRouteTile);
-            }
+            route_bucket<false>(route, in_oor, bk, in_oor.counts[bk], 0u, i, words, err,
+                                [&](uint32_t tile) { return static_cast<int>(tile % nrw) == rw; });
         }
     }
     __syncthreads();
@@ -1216,7 +1202,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
     // pack_row), kcorr / rscale / kmf, and the row's operand tiles.  (Round
     // 5 ran three passes with a barrier between each: column scale by
     // items, rows, tiles by items.)
-    const int KS = L.KS(), KH = 16 * KS, RB = L.RB();
+    const int KS = L.KS(), RB = L.RB();
     int32_t* mf = mat + L.mf();
     {
         constexpr int MG = 8;  // k <= 128: at most 8 groups per lane
@@ -1295,16 +1281,8 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
             }
             sum += __builtin_amdgcn_update_dpp(0u, sum, 0xB1, 0xf, 0xf, false);
             sum += __builtin_amdgcn_update_dpp(0u, sum, 0x4E, 0xf, 0xf, false);
-            if (t < L.R && sub == 0) {
-                // sum < 2^24: two folds, then canonical
-                const uint32_t sq = canon_lz(fold(static_cast<int32_t>(sum)));
-                mat[L.kcorr() + t] = static_cast<int32_t>(canon_lz(mul_lz(balanced(sq), 32768)));
-                mat[L.rscale() + t] = rs;
-                if (KS) {
-                    mat[L.kmf() + t] = static_cast<int32_t>(canon_lz(mul_lz(balanced(sq), 32896)));
-                    mat[L.rscale_mf() + t] = rs;
-                }
-            }
+            if (t < L.R && sub == 0)
+                store_row_sums(mat, L, t, sum, rs);
             // the operand tiles (pack_mf_dword's layout: [a | 0], [0 | b],
             // [b | a]; the zero halves are not written at KS >= 4, the kernel
             // never reads them), zeros past the rows and entries: a wave
@@ -1318,39 +1296,11 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
                 const int i0 = 4 * sub + 16 * m;
                 if (m >= KS)  // groups j = sub + 4 m < KH / 4
                     break;
-                // split_i8 of the 4 entries (0 past k and past R: a = b = 0):
-                // v = 256 a + b in [-32896, 32639], b = the signed low byte
-                // of v, a = (v - b) / 256; entry jb's bytes into byte jb of
-                // aw / bw by three byte permutes each
+                // (0 past k and past R: a = b = 0)
                 const uint32_t e[4] = {ev[m].x, ev[m].y, ev[m].z, ev[m].w};
-                uint32_t vb[4], va[4];
-#pragma unroll
-                for (int jb = 0; jb < 4; jb++) {
-                    int32_t v = balanced(e[jb]);
-                    v = v > 32639 ? v - kQ : v;
-                    const int32_t b = (v << 24) >> 24;
-                    vb[jb] = static_cast<uint32_t>(v);      // b's byte: byte 0
-                    va[jb] = static_cast<uint32_t>(v - b);  // a's byte: byte 1
-                }
-                const uint32_t bw = __builtin_amdgcn_perm(
-                    __builtin_amdgcn_perm(vb[3], vb[2], 0x0c0c0400u),
-                    __builtin_amdgcn_perm(vb[1], vb[0], 0x0c0c0400u), 0x05040100u);
-                const uint32_t aw = __builtin_amdgcn_perm(
-                    __builtin_amdgcn_perm(va[3], va[2], 0x0c0c0501u),
-                    __builtin_amdgcn_perm(va[1], va[0], 0x0c0c0501u), 0x05040100u);
-#pragma unroll
-                for (int half = 0; half < 2; half++) {
-                    const int K = half * KH + i0;
-                    const int ks = K >> 5, g = (K & 31) >> 3, dw = (K & 7) >> 2;
-                    const size_t base =
-                        static_cast<size_t>((rb * KS + ks) * 3) * 128 + (16 * g + tl) * 2 + dw;
-                    if (KS < 4 || half == 0)
-                        mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
-                    if (KS < 4 || half == 1)
-                        mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
-                    if (KS < 2)  // [b | a]: the kernels rebuild it at KS >= 2
-                        mf[base + 256] = static_cast<int32_t>(half ? aw : bw);
-                }
+                uint32_t aw, bw;
+                split_i8_x4(e, aw, bw);
+                store_tile_words(mf, KS, rb, tl, i0, aw, bw);
             }
         }
     }
@@ -1382,8 +1332,7 @@ __global__ __launch_bounds__(NT) void decode_ctx_lds_kernel(
             if (i < k) {
                 const int32_t lo = balanced(e[2 * h]);
                 const int32_t hi = i + 1 < k ? balanced(e[2 * h + 1]) : 0;
-                packed[i >> 1] = static_cast<int32_t>((static_cast<uint32_t>(lo) & 0xffffu) |
-                                                      (static_cast<uint32_t>(hi) << 16));
+                packed[i >> 1] = pack_pair(lo, hi);
             }
         }
     }
@@ -1418,8 +1367,7 @@ __global__ __launch_bounds__(256) void fill_dot2_kernel(MatLayout L, int32_t* ct
                 v[h] = balanced(e);
             }
         }
-        mat[static_cast<size_t>(t) * L.KP + j] = static_cast<int32_t>(
-            (static_cast<uint32_t>(v[0]) & 0xffffu) | (static_cast<uint32_t>(v[1]) << 16));
+        mat[static_cast<size_t>(t) * L.KP + j] = pack_pair(v[0], v[1]);
     }
     __syncthreads();
     if (threadIdx.x == 0)
@@ -1493,13 +1441,8 @@ int launch_decode_ctx(int k, int n, uint32_t r, int mode, const MatLayout& L,
                            slot_base, by_pos, words, dot2, err, nb);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    RPow2 rp{};
-    uint32_t e = r;
-    for (int b = 0; b < 16; b++, e = mulmod_c(e, e))
-        rp.v[b] = balanced(e);
     int lgn = 0;
-    while (lgn < 16 && (1u << lgn) < static_cast<uint32_t>(n))
-        lgn++;
+    const RPow2 rp = make_rpow2(r, n, &lgn);
     const size_t lds = static_cast<size_t>(k) * ctx_pitch(k) * 4;
     // k > 64: up to 68 KB (k = 128) of dynamic LDS, opted in
     // per launch (cheap; the device may differ between calls)
@@ -1567,25 +1510,16 @@ __global__ __launch_bounds__(NT) void repair_ctx_kernel(
     uint32_t* Mt = qi_ctx_lds;
     int32_t* cids = mat + L.words();
     uint32_t* route = reinterpret_cast<uint32_t*>(cids + 2 * L.KP);
-    const long long ntiles = route_tiles(words);
 
-    for (int i = k + tid; i < 2 * L.KP; i += NT)
-        cids[i] = 0;
-    // (ids only, no buckets: every tile unrouted, as the decode contexts)
-    const uint32_t rt0 = in_oor.counts ? 0u : static_cast<uint32_t>(kRouteCap) + 1u;
-    for (long long t = tid; t < ntiles; t += NT)
-        route[t * kRouteStride] = rt0;
-    if (tid == 0) {
-        route[ntiles * kRouteStride] = 0;          // the slow-tile list starts empty
-        route[lazy_word_off(words)] = kLazyDot2;   // the dot2 sections are built here
-    }
+    clear_cids_pad(cids, k, L.KP, tid, NT);
+    // (the dot2 sections are built here, so the lazy word says so)
+    clear_route(route, words, in_oor.counts != nullptr, kLazyDot2, tid, NT, tid == 0);
     order_ids<NT>(ids + static_cast<long long>(s) * k, k, sys != 0, pid, wtot);
     if (tid < k) {
         const uint32_t id = pid[tid];
         xs[tid] = canon_lz(rpow_lz(rp, id, lgn));
         cids[tid] = static_cast<int32_t>(id);
-        if (id >= (1u << lgn))  // not a point of the code
-            atomicOr(err, kErrBadIds);
+        check_id(id, 1u << lgn, err);
     }
     if (tid < R) {
         const uint32_t t = targets[static_cast<long long>(s) * R + tid];
@@ -1674,22 +1608,8 @@ __global__ __launch_bounds__(NT) void repair_ctx_kernel(
     // them at the top stalled the one-wave form for a store round trip
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    if (bk >= 0) {
-        uint32_t c = bcnt;
-        if (c > static_cast<uint32_t>(in_oor.cap)) {
-            atomicOr(err, kErrOorTruncated);
-            c = static_cast<uint32_t>(in_oor.cap);
-        }
-        for (uint32_t e = 0; e < c; e++) {
-            const uint32_t w = e ? in_oor.entries[bk * in_oor.cap + e] : bent0;
-            if (w >= words)
-                continue;
-            uint32_t* rt = route + (w / kRouteTile) * kRouteStride;
-            const uint32_t p = atomicAdd(rt, 1u);
-            if (p < static_cast<uint32_t>(kRouteCap))
-                rt[1 + p] = (static_cast<uint32_t>(tid) << 16) | (w % kRouteTile);
-        }
-    }
+    if (bk >= 0)
+        route_bucket<true>(route, in_oor, bk, bcnt, bent0, tid, words, err, EveryTile{});
     {
         // the column scale, pack_row's row scale, the packed pairs, `plain`,
         // kcorr / rscale / kmf; the row-scaled entries back into the LDS rows
@@ -1705,7 +1625,7 @@ __global__ __launch_bounds__(NT) void repair_ctx_kernel(
     // [b | a], zeros past the rows and entries), from the LDS rows: per (row
     // t, 4 consecutive entries) split once, items rows-fastest so a wave's
     // stores cover whole 128-byte tile lines
-    const int KS = L.KS(), KH = 16 * KS, nj = KH / 4, RB = L.RB();
+    const int KS = L.KS(), nj = 4 * KS, RB = L.RB();
     int32_t* mf = mat + L.mf();
     for (int it = tid; it < RB * nj * 16; it += NT) {
         const int tl4 = it & 15, jj = it >> 4;
@@ -1725,16 +1645,7 @@ __global__ __launch_bounds__(NT) void repair_ctx_kernel(
                 }
             }
         }
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const int K = half * KH + i0;
-            const int ks = K >> 5, g = (K & 31) >> 3, dw = (K & 7) >> 2;
-            const size_t base =
-                static_cast<size_t>((rb * KS + ks) * 3) * 128 + (16 * g + tl4) * 2 + dw;
-            mf[base] = static_cast<int32_t>(half ? 0u : aw);        // [a | 0]
-            mf[base + 128] = static_cast<int32_t>(half ? bw : 0u);  // [0 | b]
-            mf[base + 256] = static_cast<int32_t>(half ? aw : bw);  // [b | a]
-        }
+        store_tile_words<true>(mf, KS, rb, tl4, i0, aw, bw);
     }
 }
 
@@ -1746,13 +1657,8 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
     if (k > 256 || L.kin != k || L.R < 1 || L.R > kRepairMaxR || S <= 0)
         return -3;
     Oor none{nullptr, nullptr, 0, 0};
-    RPow2 rp{};
-    uint32_t e = r;
-    for (int b = 0; b < 16; b++, e = mulmod_c(e, e))
-        rp.v[b] = balanced(e);
     int lgn = 0;
-    while (lgn < 16 && (1u << lgn) < static_cast<uint32_t>(n))
-        lgn++;
+    const RPow2 rp = make_rpow2(r, n, &lgn);
     // up to 65 KB of rows (R = 64, k = 256): opted in per launch (cheap; the
     // device may differ between calls)
     const size_t lds = static_cast<size_t>(L.R) * ctx_pitch(k) * 4;

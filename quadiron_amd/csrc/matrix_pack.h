@@ -100,6 +100,14 @@ QI_HD void split_i8(uint32_t c, int32_t& a, int32_t& b)
     a = (v - b) / 256;
 }
 
+// The dot2 kernel's pair word: two balanced entries (|c| <= 32766) as int16
+// halves, the even entry low.
+QI_HD int32_t pack_pair(int32_t lo, int32_t hi)
+{
+    return static_cast<int32_t>((static_cast<uint32_t>(lo) & 0xffffu) |
+                                (static_cast<uint32_t>(hi) << 16));
+}
+
 // Pack row t (kin canonical entries) of the block.  Rows holding a
 // coefficient that breaks coef_ok are scaled by a unit s first and the
 // result is multiplied back by s^-1 (rscale, also |s^-1| <= 32766).
@@ -132,8 +140,7 @@ QI_HD uint32_t pack_row(const uint32_t* row, const MatLayout& L, int t,
             lo = balanced(mulmod_c(row[2 * j], s));
         if (2 * j + 1 < kin)
             hi = balanced(mulmod_c(row[2 * j + 1], s));
-        packed[j] = static_cast<int32_t>((static_cast<uint32_t>(lo) & 0xffffu) |
-                                         (static_cast<uint32_t>(hi) << 16));
+        packed[j] = pack_pair(lo, hi);
     }
     for (int i = 0; i < kin; i++) {
         const uint32_t c = mulmod_c(row[i], s);
@@ -187,6 +194,17 @@ QI_HD int32_t pack_mf_dword(const MatLayout& L, const int32_t* rows, size_t d)
     return static_cast<int32_t>(v);
 }
 
+// The dword of the operand tiles (pack_mf_dword's layout, KS K-steps per row
+// block) that holds byte K of row tl (< 16) of row block rb in the tile of
+// type ty (0: [a | 0], 1: [0 | b], 2: [b | a]; 128 dwords apart).  Byte K & 3
+// of the dword.
+QI_HD size_t mf_dword_index(int KS, int rb, int K, int tl, int ty = 0)
+{
+    const int ks = K >> 5, g = (K & 31) >> 3, dw = (K >> 2) & 1;
+    return (static_cast<size_t>(rb * KS + ks) * 3 + ty) * 128 +
+           static_cast<size_t>((16 * g + tl) * 2 + dw);
+}
+
 // Entry (t, i) of the row-scaled matrix read back from its operand tiles
 // (pack_mf_dword's layout): a from [a | 0] at K = i, b from [0 | b] at
 // K = KH + i; 256 a + b, canonical.  The decode paths that need single
@@ -200,10 +218,8 @@ QI_HD uint32_t mf_entry(const MatLayout& L, const int32_t* mf, int t, int i)
     int32_t e[2];
     for (int h = 0; h < 2; h++) {
         const int K = h ? KH + i : i;
-        const int ks = K >> 5, g = (K & 31) >> 3, dw = (K >> 2) & 1, jb = K & 3;
-        const size_t d = (static_cast<size_t>((t >> 4) * KS + ks) * 3 + h) * 128 +
-                         static_cast<size_t>((16 * g + (t & 15)) * 2 + dw);
-        e[h] = static_cast<int8_t>(static_cast<uint32_t>(mf[d]) >> (8 * jb));
+        const size_t d = mf_dword_index(KS, t >> 4, K, t & 15, h);
+        e[h] = static_cast<int8_t>(static_cast<uint32_t>(mf[d]) >> (8 * (K & 3)));
     }
     const int32_t c = 256 * e[0] + e[1];
     return static_cast<uint32_t>(c < 0 ? c + kQ : c);

@@ -20,8 +20,9 @@ RES = [os.path.join(ROOT, "build", "obj", f)
 # Round 6: the k > 128 decode context (1024 threads, 128 VGPRs: a few values
 # kept across the chunk loop, 5 reloads per chunk; the non-systematic k300 /
 # k600 contexts measured 48 / 102 us either way, gpurun_out/r6k).
-ALLOWED = ("matrix_redo_kernel", "encode_fnt_kernelILi64E",
-           "decode_ctx_kernelILi1024ELb1E")
+ALLOWED = ("matrix_redo_kernel", "encode_fnt_kernelILi64E")
+# ... which may keep the scratch it has, in bytes per lane, and no more
+CAPPED = {"decode_ctx_kernelILi1024ELb1E": 16}
 
 
 def kernels():
@@ -49,9 +50,12 @@ def test_report_lists_the_hot_kernels():
 
 
 def test_no_scratch_in_hot_kernels():
+    def cap(k):
+        return next((c for a, c in CAPPED.items() if a in k), 0)
     bad = {k: v.get("ScratchSize") for k, v in kernels().items()
-           if v.get("ScratchSize", 0) > 0 and not any(a in k for a in ALLOWED)}
+           if v.get("ScratchSize", 0) > cap(k) and not any(a in k for a in ALLOWED)}
     assert not bad, bad
+    assert all(any(a in k for k in kernels()) for a in CAPPED), CAPPED
 
 
 def _lds_waves_per_simd(ks, nst, rsplit):
