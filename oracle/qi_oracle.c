@@ -8,6 +8,7 @@
  */
 #include "qi_oracle.h"
 
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -17,17 +18,28 @@
 uint32_t qo_add(uint32_t a, uint32_t b)
 {
     uint32_t c = a + b; /* src/gf_ring.h:214-224 */
-    return c >= QO_Q ? c - QO_Q : c;
+    return c - (QO_Q & (0u - (uint32_t)(c >= QO_Q)));
 }
 
 uint32_t qo_sub(uint32_t a, uint32_t b)
 {
-    return a >= b ? a - b : QO_Q - (b - a); /* src/gf_ring.h:226-236 */
+    /* src/gf_ring.h:226-236 */
+    return a - b + (QO_Q & (0u - (uint32_t)(a < b)));
 }
 
 uint32_t qo_mul(uint32_t a, uint32_t b)
 {
-    return (uint32_t)(((uint64_t)a * b) % QO_Q); /* src/gf_ring.h:238-244 */
+    /* src/gf_ring.h:238-244; the same residue as p % q, without the
+     * division: 2^16 = -1 and 2^32 = 1 mod q, for a product below 2^48 */
+    uint64_t p = (uint64_t)a * b;
+    int32_t v;
+    if (p >> 48)
+        return (uint32_t)(p % QO_Q);
+    v = (int32_t)(p & 0xffffu) - (int32_t)((p >> 16) & 0xffffu) +
+        (int32_t)(p >> 32);
+    v += (int32_t)QO_Q & -(v < 0);
+    v -= (int32_t)QO_Q & -(v >= (int32_t)QO_Q);
+    return (uint32_t)v;
 }
 
 uint32_t qo_exp(uint32_t a, uint32_t e)
@@ -113,15 +125,18 @@ void qo_fft(int n, int data_len, uint32_t w, const uint32_t* in, int in_len,
         for (i = s; i < s + group_len; i++)
             out[i] = 0;
     }
+    /* the butterflies of a stage are independent: block by block, so that
+     * the inner loop runs over neighbouring words */
     for (m = group_len; m < (unsigned)n; m *= 2) {
         unsigned dm = 2 * m, ratio = (unsigned)n / dm;
-        for (j = 0; j < m; j++) {
-            uint32_t r = W[j * ratio];
-            for (i = j; i < (unsigned)n; i += dm) {
-                uint32_t a = out[i];
-                uint32_t b = qo_mul(r, out[i + m]);
-                out[i] = qo_add(a, b);
-                out[i + m] = qo_sub(a, b);
+        for (i = 0; i < (unsigned)n; i += dm) {
+            uint32_t* lo = out + i;
+            uint32_t* hi = out + i + m;
+            for (j = 0; j < m; j++) {
+                uint32_t a = lo[j];
+                uint32_t b = qo_mul(W[j * ratio], hi[j]);
+                lo[j] = qo_add(a, b);
+                hi[j] = qo_sub(a, b);
             }
         }
     }
@@ -144,13 +159,14 @@ void qo_fft_inv(int n, uint32_t w, const uint32_t* in, uint32_t* out)
 
     memcpy(out, in, sizeof(uint32_t) * (size_t)n);
     for (m = (unsigned)n / 2; m >= 1; m /= 2) {
-        unsigned dm = 2 * m;
-        for (j = 0; j < m; j++) {
-            uint32_t r = iW[j * (unsigned)n / dm];
-            for (i = j; i < (unsigned)n; i += dm) {
-                uint32_t a = out[i], b = out[i + m];
-                out[i] = qo_add(a, b);
-                out[i + m] = qo_mul(r, qo_sub(a, b));
+        unsigned dm = 2 * m, ratio = (unsigned)n / dm;
+        for (i = 0; i < (unsigned)n; i += dm) {
+            uint32_t* lo = out + i;
+            uint32_t* hi = out + i + m;
+            for (j = 0; j < m; j++) {
+                uint32_t a = lo[j], b = hi[j];
+                lo[j] = qo_add(a, b);
+                hi[j] = qo_mul(iW[j * ratio], qo_sub(a, b));
             }
         }
     }
@@ -170,8 +186,10 @@ void qo_fft_inv(int n, uint32_t w, const uint32_t* in, uint32_t* out)
 /* Codec plan: src/fec_rs_fnt.h:69-163 */
 int qo_codec_init(qo_codec* c, int k, int m, int sys)
 {
-    /* oracle limits: k <= QO_KMAX, k + m <= 65536 (fixed-size scratch) */
-    if (k < 1 || m < 1 || k > QO_KMAX || k + m > 65536)
+    /* the field's limits: n = ceil2(k + m) and len_2k = ceil2(2k) must
+     * divide q - 1 = 65536 (src/fec_rs_fnt.h:106-119) */
+    if (k < 1 || m < 1 || 2 * (int64_t)k >= QO_Q ||
+        (int64_t)k + m > QO_Q - 1)
         return -1;
     c->sys = sys ? 1 : 0;
     c->k = k;
@@ -185,6 +203,39 @@ int qo_codec_init(qo_codec* c, int k, int m, int sys)
     return 0;
 }
 
+/* qo_ctx is one allocation sized from the codec: ids[k], inv_A_i[k],
+ * A_fft_2k[len_2k] back to back in v[]. */
+size_t qo_ctx_bytes(const qo_codec* c)
+{
+    return offsetof(qo_ctx, v) +
+           sizeof(uint32_t) * (2 * (size_t)c->k + (size_t)c->len_2k);
+}
+
+static uint32_t* ctx_ids(const qo_ctx* ctx)
+{
+    return (uint32_t*)ctx->v;
+}
+
+static uint32_t* ctx_inv_A_i(const qo_ctx* ctx)
+{
+    return (uint32_t*)ctx->v + ctx->k;
+}
+
+static uint32_t* ctx_A_fft_2k(const qo_ctx* ctx)
+{
+    return (uint32_t*)ctx->v + 2 * (size_t)ctx->k;
+}
+
+static qo_ctx* ctx_alloc(const qo_codec* c)
+{
+    return (qo_ctx*)malloc(qo_ctx_bytes(c));
+}
+
+static void* xalloc(size_t count, size_t size)
+{
+    return calloc(count ? count : 1, size);
+}
+
 /* DecodeContext ctor+init: src/fec_context.h:66-142, :232-274;
  * vx from src/fec_base.h:758-793 (x_i = r^{id_i}, vx_zero = -1). */
 int qo_ctx_init(const qo_codec* c, qo_ctx* ctx, const uint32_t* ids)
@@ -192,8 +243,6 @@ int qo_ctx_init(const qo_codec* c, qo_ctx* ctx, const uint32_t* ids)
     int k = c->k, n = c->n, i, d;
     uint32_t *A, *Ad, *A_fft, *A2k;
 
-    if (k > QO_KMAX || c->len_2k > 2 * QO_KMAX)
-        return -1;
     A = (uint32_t*)calloc((size_t)n + 1, sizeof(uint32_t));
     Ad = (uint32_t*)calloc((size_t)n, sizeof(uint32_t));
     A_fft = (uint32_t*)calloc((size_t)n, sizeof(uint32_t));
@@ -201,15 +250,23 @@ int qo_ctx_init(const qo_codec* c, qo_ctx* ctx, const uint32_t* ids)
 
     ctx->k = k;
     for (i = 0; i < k; i++)
-        ctx->ids[i] = ids[i];
+        ctx_ids(ctx)[i] = ids[i];
 
     /* A(x) = prod (x - x_i): Poly::mul_to_x_plus_coef src/vec_poly.h:218-228 */
     A[0] = 1;
     for (i = 0; i < k; i++) {
         uint32_t coef = qo_sub(0, qo_exp(c->r, ids[i]));
         uint32_t top = A[i];
-        for (d = i; d > 0; d--)
-            A[d] = qo_add(A[d - 1], qo_mul(A[d], coef));
+        /* the O(k^2) part, branch-free so that it vectorises: p < 2^34,
+         * 2^16 = -1 and 2^32 = 1 mod q */
+        for (d = i; d > 0; d--) {
+            uint64_t p = (uint64_t)A[d] * coef + A[d - 1];
+            int32_t v = (int32_t)(p & 0xffffu) - (int32_t)((p >> 16) & 0xffffu) +
+                        (int32_t)(p >> 32);
+            v += (int32_t)QO_Q & -(v < 0);
+            v -= (int32_t)QO_Q & -(v >= (int32_t)QO_Q);
+            A[d] = (uint32_t)v;
+        }
         A[0] = qo_mul(A[0], coef);
         A[i + 1] = top;
     }
@@ -220,13 +277,13 @@ int qo_ctx_init(const qo_codec* c, qo_ctx* ctx, const uint32_t* ids)
     qo_fft(n, c->data_len, c->r, Ad, n, A_fft);
     /* inv_A_i = 1 / (A'(x_i) * x_i): src/fec_context.h:259-267 */
     for (i = 0; i < k; i++)
-        ctx->inv_A_i[i] =
+        ctx_inv_A_i(ctx)[i] =
             qo_inv(qo_mul(A_fft[ids[i]], qo_exp(c->r, ids[i])));
     /* A_fft_2k = FFT_2k(A zero-extended): src/fec_context.h:270-273 */
     for (d = 0; d <= k && d < c->len_2k; d++)
         A2k[d] = A[d];
     qo_fft(c->len_2k, c->len_2k, qo_nth_root((uint32_t)c->len_2k), A2k,
-           c->len_2k, ctx->A_fft_2k);
+           c->len_2k, ctx_A_fft_2k(ctx));
 
     free(A);
     free(Ad);
@@ -249,12 +306,12 @@ static void decode_apply(const qo_codec* c, const qo_ctx* ctx,
 
     /* N(x) = sum_i (v_i * inv_A_i) x^{z_i} */
     for (i = 0; i < k; i++)
-        v1n[ctx->ids[i]] = qo_mul(words[i], ctx->inv_A_i[i]);
+        v1n[ctx_ids(ctx)[i]] = qo_mul(words[i], ctx_inv_A_i(ctx)[i]);
     qo_fft_inv(n, c->r, v1n, v2n);
     /* FFT_2k of the first k outputs (zero extended) */
     qo_fft(L, L, wL, v2n, k, v1);
     for (i = 0; i < L; i++)
-        v1[i] = qo_mul(v1[i], ctx->A_fft_2k[i]);
+        v1[i] = qo_mul(v1[i], ctx_A_fft_2k(ctx)[i]);
     /* ifft = fft_inv * len_2k^-1: src/fft_2n.h:630-639 */
     qo_fft_inv(L, wL, v1, v2);
     for (i = 0; i < k; i++)
@@ -272,11 +329,8 @@ void qo_decode_column(const qo_codec* c, const qo_ctx* ctx,
     if (c->sys) {
         /* fft(dec_inter_codeword, output); keep rows 0..k-1 */
         uint32_t* cw = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)c->n);
-        uint32_t tmp[QO_KMAX];
         int i;
-        for (i = 0; i < c->k; i++)
-            tmp[i] = data[i];
-        qo_fft(c->n, c->data_len, c->r, tmp, c->k, cw);
+        qo_fft(c->n, c->data_len, c->r, data, c->k, cw);
         for (i = 0; i < c->k; i++)
             data[i] = cw[i];
         free(cw);
@@ -288,10 +342,11 @@ void qo_encode_column(const qo_codec* c, const qo_ctx* enc_ctx,
                       const uint32_t* data, uint32_t* codeword)
 {
     if (c->sys) {
-        uint32_t inter[QO_KMAX];
+        uint32_t* inter = (uint32_t*)xalloc((size_t)c->k, sizeof(uint32_t));
         /* decode_data over ids 0..k-1: src/fec_rs_fnt.h:204-234 */
         decode_apply(c, enc_ctx, data, inter);
         qo_fft(c->n, c->data_len, c->r, inter, c->k, codeword);
+        free(inter);
     } else {
         qo_fft(c->n, c->data_len, c->r, data, c->k, codeword);
     }
@@ -318,15 +373,16 @@ void qo_encode_blocks(const qo_codec* c, uint8_t* const* data,
     size_t words = block_bytes / 2, j;
     int k = c->k, n = c->n, i, first = c->sys ? k : 0;
     qo_ctx* ctx = NULL;
-    uint32_t in[QO_KMAX];
+    uint32_t* in = (uint32_t*)xalloc((size_t)k, sizeof(uint32_t));
     uint32_t* cw = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)n);
 
     if (c->sys) {
-        uint32_t ids[QO_KMAX];
-        ctx = (qo_ctx*)malloc(sizeof(qo_ctx));
+        uint32_t* ids = (uint32_t*)xalloc((size_t)k, sizeof(uint32_t));
+        ctx = ctx_alloc(c);
         for (i = 0; i < k; i++)
             ids[i] = (uint32_t)i;
         qo_ctx_init(c, ctx, ids); /* src/fec_rs_fnt.h:141-156 */
+        free(ids);
     }
     for (i = 0; i < c->n_outputs; i++)
         oor_count[i] = 0;
@@ -347,6 +403,7 @@ void qo_encode_blocks(const qo_codec* c, uint8_t* const* data,
         }
     }
     free(cw);
+    free(in);
     free(ctx);
 }
 
@@ -364,16 +421,16 @@ int qo_decode_blocks(const qo_codec* c, uint8_t* const* data,
                      const int* missing, const int* wanted,
                      size_t block_bytes)
 {
-    int k = c->k, i, fi = 0, avail_data = 0;
-    uint32_t ids[QO_KMAX] = {0};
-    const uint8_t* src[QO_KMAX];
-    const uint32_t* marks[QO_KMAX];
-    uint32_t nmarks[QO_KMAX];
-    uint32_t* sorted[QO_KMAX];
-    uint32_t pos[QO_KMAX];
+    int k = c->k, i, fi = 0, ret = 0;
+    /* per-fragment state, all k long, off the stack */
+    uint32_t* u32 = (uint32_t*)xalloc(5 * (size_t)k, sizeof(uint32_t));
+    uint32_t *ids = u32, *nmarks = u32 + k, *pos = u32 + 2 * (size_t)k,
+             *in = u32 + 3 * (size_t)k, *out = u32 + 4 * (size_t)k;
+    const uint8_t** src = (const uint8_t**)xalloc((size_t)k, sizeof(*src));
+    const uint32_t** marks = (const uint32_t**)xalloc((size_t)k, sizeof(*marks));
+    uint32_t** sorted = (uint32_t**)xalloc((size_t)k, sizeof(*sorted));
     size_t words = block_bytes / 2, j;
     qo_ctx* ctx;
-    uint32_t in[QO_KMAX], out[QO_KMAX];
 
     if (c->sys) {
         for (i = 0; i < k; i++) {
@@ -384,12 +441,12 @@ int qo_decode_blocks(const qo_codec* c, uint8_t* const* data,
                 nmarks[fi] = 0;
                 fi++;
             }
-            avail_data = fi;
-            if (fi == k)
-                return 1; /* src/fec_base.h:1208-1211 */
+            if (fi == k) {
+                ret = 1; /* src/fec_base.h:1208-1211 */
+                goto done;
+            }
         }
     }
-    (void)avail_data;
     for (i = 0; i < c->n_outputs && fi < k; i++) {
         int id = c->sys ? k + i : i;
         if (!missing[id]) {
@@ -401,10 +458,10 @@ int qo_decode_blocks(const qo_codec* c, uint8_t* const* data,
         }
     }
     if (fi < k)
-        return 0;
+        goto done;
     /* ids are already ascending (fragments_ids.sort(), :1236) */
 
-    ctx = (qo_ctx*)malloc(sizeof(qo_ctx));
+    ctx = ctx_alloc(c);
     qo_ctx_init(c, ctx, ids);
     /* props.sort() src/fec_context.h:93-97 */
     for (i = 0; i < k; i++) {
@@ -437,7 +494,13 @@ int qo_decode_blocks(const qo_codec* c, uint8_t* const* data,
     for (i = 0; i < k; i++)
         free(sorted[i]);
     free(ctx);
-    return 1;
+    ret = 1;
+done:
+    free(u32);
+    free(src);
+    free(marks);
+    free(sorted);
+    return ret;
 }
 
 /* ------------------------------------------------------------------ */
@@ -459,7 +522,7 @@ void qo_nf4_encode_blocks(const qo_codec* c, int word_size,
 {
     const int g = word_size / 2, k = c->k, no = c->n_outputs;
     const size_t words = block_bytes / (size_t)word_size; /* fec_base.h:1083 */
-    uint32_t in[QO_KMAX];
+    uint32_t* in = (uint32_t*)xalloc((size_t)c->k, sizeof(uint32_t));
     uint32_t* cw = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)c->n);
     uint32_t* mask = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)no);
     size_t j;
@@ -498,6 +561,7 @@ void qo_nf4_encode_blocks(const qo_codec* c, int word_size,
     }
     free(mask);
     free(cw);
+    free(in);
 }
 
 static int cmp_u64(const void* a, const void* b)
@@ -515,12 +579,14 @@ int qo_nf4_decode_blocks(const qo_codec* c, int word_size,
 {
     const int g = word_size / 2, k = c->k;
     const size_t words = block_bytes / (size_t)word_size;
-    uint32_t ids[QO_KMAX] = {0};
-    const uint8_t* src[QO_KMAX];
-    uint64_t* marks[QO_KMAX]; /* word << 8 | component mask, sorted */
-    uint32_t nmarks[QO_KMAX], pos[QO_KMAX], cur[QO_KMAX];
-    uint32_t in[QO_KMAX], out[QO_KMAX];
-    int i, fi = 0, comp;
+    uint32_t* u32 = (uint32_t*)xalloc(6 * (size_t)k, sizeof(uint32_t));
+    uint32_t *ids = u32, *nmarks = u32 + k, *pos = u32 + 2 * (size_t)k,
+             *cur = u32 + 3 * (size_t)k, *in = u32 + 4 * (size_t)k,
+             *out = u32 + 5 * (size_t)k;
+    const uint8_t** src = (const uint8_t**)xalloc((size_t)k, sizeof(*src));
+    /* word << 8 | component mask, sorted */
+    uint64_t** marks = (uint64_t**)xalloc((size_t)k, sizeof(*marks));
+    int i, fi = 0, comp, ret = 0;
     size_t j, e;
     qo_ctx* ctx;
 
@@ -540,12 +606,9 @@ int qo_nf4_decode_blocks(const qo_codec* c, int word_size,
             fi++;
         }
     }
-    if (fi < k) {
-        for (i = 0; i < fi; i++)
-            free(marks[i]);
-        return 0;
-    }
-    ctx = (qo_ctx*)malloc(sizeof(qo_ctx));
+    if (fi < k)
+        goto done;
+    ctx = ctx_alloc(c);
     qo_ctx_init(c, ctx, ids);
     for (j = 0; j < words; j++) {
         for (i = 0; i < k; i++) {
@@ -572,10 +635,15 @@ int qo_nf4_decode_blocks(const qo_codec* c, int word_size,
             }
         }
     }
-    for (i = 0; i < k; i++)
-        free(marks[i]);
     free(ctx);
-    return 1;
+    ret = 1;
+done:
+    for (i = 0; i < fi; i++)
+        free(marks[i]);
+    free(u32);
+    free(src);
+    free(marks);
+    return ret;
 }
 
 /* ------------------------------------------------------------------ */
@@ -644,8 +712,8 @@ int qo_fnt32_encode(const qo_codec* c, uint8_t** data, uint8_t** parity,
 {
     int md = qo_metadata_size(block_size), nd = md / 4, i, k = c->k;
     uint32_t cap = (uint32_t)nd;
-    uint8_t* in[QO_KMAX];
-    uint8_t* out[QO_NMAX];
+    uint8_t** in = (uint8_t**)xalloc((size_t)k, sizeof(*in));
+    uint8_t** out = (uint8_t**)xalloc((size_t)c->n_outputs, sizeof(*out));
     uint32_t* oor = (uint32_t*)malloc(sizeof(uint32_t) * cap *
                                       (size_t)c->n_outputs);
     uint32_t* cnt = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)c->n_outputs);
@@ -687,6 +755,8 @@ int qo_fnt32_encode(const qo_codec* c, uint8_t** data, uint8_t** parity,
     }
     free(oor);
     free(cnt);
+    free(in);
+    free(out);
     return ret;
 }
 
@@ -727,9 +797,9 @@ int qo_fnt32_decode(const qo_codec* c, uint8_t** data, uint8_t** parity,
     uint32_t* oor = (uint32_t*)malloc(sizeof(uint32_t) * cap *
                                       (size_t)c->n_outputs);
     uint32_t* cnt = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)c->n_outputs);
-    uint8_t* dv[QO_KMAX];
-    uint8_t* pv[QO_NMAX];
-    int wanted[QO_KMAX];
+    uint8_t** dv = (uint8_t**)xalloc((size_t)k, sizeof(*dv));
+    uint8_t** pv = (uint8_t**)xalloc((size_t)c->n_outputs, sizeof(*pv));
+    int* wanted = (int*)xalloc((size_t)k, sizeof(int));
     int ret = 0;
 
     if (load_props(c, data, parity, missing_idxs, nd, oor, cnt, cap)) {
@@ -771,6 +841,9 @@ int qo_fnt32_decode(const qo_codec* c, uint8_t** data, uint8_t** parity,
 out:
     free(oor);
     free(cnt);
+    free(dv);
+    free(pv);
+    free(wanted);
     return ret;
 }
 
@@ -786,15 +859,13 @@ int qo_fnt32_reconstruct(const qo_codec* c, uint8_t** data, uint8_t** parity,
     uint32_t* eoor = (uint32_t*)malloc(sizeof(uint32_t) * cap *
                                        (size_t)c->n_outputs);
     uint32_t* ecnt = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)c->n_outputs);
-    uint8_t* dv[QO_KMAX];
-    uint8_t* pv[QO_NMAX];
-    uint8_t* ov[QO_NMAX];
-    uint8_t* tmp[QO_KMAX];
-    int wanted[QO_KMAX];
+    uint8_t** dv = (uint8_t**)xalloc((size_t)k, sizeof(*dv));
+    uint8_t** pv = (uint8_t**)xalloc((size_t)c->n_outputs, sizeof(*pv));
+    uint8_t** ov = (uint8_t**)xalloc((size_t)c->n_outputs, sizeof(*ov));
+    uint8_t** tmp = (uint8_t**)xalloc((size_t)k, sizeof(*tmp));
+    int* wanted = (int*)xalloc((size_t)k, sizeof(int));
     int ret = 0, need_decode = 0;
 
-    for (i = 0; i < k; i++)
-        tmp[i] = NULL;
     if (load_props(c, data, parity, missing_idxs, nd, oor, cnt, cap)) {
         ret = -1;
         goto out;
@@ -874,6 +945,11 @@ int qo_fnt32_reconstruct(const qo_codec* c, uint8_t** data, uint8_t** parity,
 out:
     for (i = 0; i < k; i++)
         free(tmp[i]);
+    free(tmp);
+    free(dv);
+    free(pv);
+    free(ov);
+    free(wanted);
     free(oor);
     free(cnt);
     free(eoor);

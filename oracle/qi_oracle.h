@@ -24,9 +24,9 @@ extern "C" {
 #endif
 
 #define QO_Q 65537u
-/* oracle limits (fixed-size scratch): k <= QO_KMAX, k + m <= 65536 */
-#define QO_KMAX 4096
-#define QO_NMAX 65536
+/* Limits: the field's own, 2k < q and k + m <= q - 1 (qo_codec_init).  Every
+ * buffer is sized from the codec and lives on the heap, so a worker thread's
+ * stack will do. */
 
 /* ---- GF(65537) scalar arithmetic: src/gf_ring.h:214-286 ---- */
 uint32_t qo_add(uint32_t a, uint32_t b);
@@ -59,13 +59,14 @@ void qo_fft(int n, int data_len, uint32_t w, const uint32_t* in, int in_len,
 void qo_fft_inv(int n, uint32_t w, const uint32_t* in, uint32_t* out);
 
 /* Decode context for a set of k fragment ids (src/fec_context.h:66-274). */
+/* The caller provides qo_ctx_bytes(c) bytes; v holds ids[k], inv_A_i[k] and
+ * A_fft_2k[len_2k] back to back. */
 typedef struct {
     int k;
-    uint32_t ids[QO_KMAX];
-    uint32_t inv_A_i[QO_KMAX];
-    uint32_t A_fft_2k[2 * QO_KMAX];
+    uint32_t v[1];
 } qo_ctx;
 
+size_t qo_ctx_bytes(const qo_codec* c);
 int qo_ctx_init(const qo_codec* c, qo_ctx* ctx, const uint32_t* ids);
 
 /* One column: words[k] (OOR already restored) -> data[k].

@@ -1902,9 +1902,23 @@ static int launch_ntt_ctx(const qi_plan* p, const NttCtxArgs& a, int S, hipStrea
 {
     const size_t lds =
         static_cast<size_t>((p->k + kCtxChains - 1) / kCtxChains * kCtxChains) * 4;
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_ctx_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds)) != hipSuccess)
+    // the kernel's static LDS (pm[kPosChunk]) counts against the 64 KiB a
+    // launch gets without opting in: 14336 < k <= 16384 passes it with a
+    // dynamic part still below it.  Queried once per process (a property of
+    // the code object); a failed query is kept too, and every context
+    // launch then reports -2, as launch_decode_ctx's once-per-device setup does
+    const void* fn = reinterpret_cast<const void*>(&ntt_ctx_kernel);
+    static const long long fixed = [fn] {
+        hipFuncAttributes fa{};
+        return hipFuncGetAttributes(&fa, fn) == hipSuccess
+                   ? static_cast<long long>(fa.sharedSizeBytes)
+                   : -1LL;
+    }();
+    if (fixed < 0)
+        return -2;
+    const size_t total = static_cast<size_t>(fixed) + lds;
+    if (total > 65536 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(total)) != hipSuccess)
         return -2;
     const int items = p->len2k + p->k;
     hipLaunchKernelGGL(ntt_ctx_kernel, dim3(S, (items + kNttBlock - 1) / kNttBlock),

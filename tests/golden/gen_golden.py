@@ -46,16 +46,18 @@ def vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def craft_oor(ora, codec, data, rng, n_cols):
+def craft_oor(ora, codec, data, rng, n_cols, rows=None):
     """Overwrite data[0] at n_cols random columns so that one chosen output
-    row equals 65536 there (exercises the OOR side channel)."""
+    row (among `rows`, where given) equals 65536 there (exercises the OOR
+    side channel)."""
     k, no = codec.k, codec.n_outputs
     words = data.shape[1] // 2
     first = k if codec.sys else 0
     cw = (C.c_uint32 * codec.n)()
     din = (C.c_uint32 * k)()
     ids = (C.c_uint32 * k)(*range(k))
-    ctx = C.create_string_buffer(4 + 16 * 4096 + 64)
+    ora.qo_ctx_bytes.restype = C.c_size_t
+    ctx = C.create_string_buffer(ora.qo_ctx_bytes(C.byref(codec)))
     if codec.sys:
         ora.qo_ctx_init(C.byref(codec), ctx, ids)
 
@@ -76,7 +78,7 @@ def craft_oor(ora, codec, data, rng, n_cols):
             data[:, 2 * j + 1].astype(np.uint32) << 8)
         col[0] = 0
         b = enc(col)
-        i = int(rng.integers(0, no))
+        i = int(rng.choice(rows)) if rows else int(rng.integers(0, no))
         if a[i] == 0:
             continue
         d0 = ((65536 - b[i]) % Q) * pow(a[i], Q - 2, Q) % Q
@@ -88,15 +90,20 @@ def craft_oor(ora, codec, data, rng, n_cols):
 
 
 def _gen_blocks(ref, ora, name, k, m, sys_, pkt, block_bytes, seed,
-               n_patterns, n_craft, out_dir):
+               n_patterns, n_craft, out_dir, cap=None, keep=()):
+    """cap: the OOR capacity per output (default 64 + block_bytes // 2048).
+    keep: fragment ids that the first erasure pattern must leave received;
+    with it given, that pattern must also receive a row with an OOR mark."""
     rng = np.random.default_rng(seed)
     codec = Codec()
     assert ora.qo_codec_init(C.byref(codec), k, m, sys_) == 0
     no = codec.n_outputs
     data = rng.integers(0, 256, (k, block_bytes), dtype=np.uint8)
     if n_craft:
-        craft_oor(ora, codec, data, rng, n_craft)
-    cap = 64 + block_bytes // 2048
+        first = k if sys_ else 0
+        craft_oor(ora, codec, data, rng, n_craft,
+                  [i - first for i in keep if i >= first])
+    cap = cap or 64 + block_bytes // 2048
     outs = np.zeros((no, block_bytes), np.uint8)
     oor = np.zeros((no, cap), np.uint32)
     cnt = np.zeros(no, np.uint32)
@@ -109,8 +116,13 @@ def _gen_blocks(ref, ora, name, k, m, sys_, pkt, block_bytes, seed,
     missing = np.zeros((n_patterns, k + m), np.int32)
     decoded = np.zeros((n_patterns, k, block_bytes), np.uint8)
     for p in range(n_patterns):
-        miss = rng.choice(k + m, m, replace=False)
+        pool = np.setdiff1d(np.arange(k + m), keep) if p == 0 else k + m
+        miss = rng.choice(pool, m, replace=False)
         missing[p, miss] = 1
+        if keep and p == 0:
+            first = k if sys_ else 0
+            recv = np.flatnonzero(missing[p, first:] == 0)
+            assert cnt[recv].sum() > 0, "no OOR mark among the received rows"
         dec = [np.zeros(block_bytes, np.uint8) if (not sys_ or missing[p, i])
                else data[i].copy() for i in range(k)]
         par = [None if missing[p, (k + i) if sys_ else i] else outs[i].copy()
@@ -283,9 +295,9 @@ def main():
     # `python gen_golden.py name ...` regenerates only the named fixtures
     only = set(sys.argv[1:])
 
-    def gen_blocks(*a):
+    def gen_blocks(*a, **kw):
         if not only or a[2] in only:
-            _gen_blocks(*a)
+            _gen_blocks(*a, **kw)
 
     def gen_cabi(*a):
         if not only or a[2] in only:
@@ -345,6 +357,21 @@ def main():
     # systematic 384 < k <= 640 (round 6): the encode from the closed-form
     # Lagrange generator and the two-region decode, both at KS = 40
     gen_blocks(ref, ora, "blk_k450_m200_sys_w1024", 450, 200, 1, 256, 2048, 56, 1, 10, out)
+
+    # the top of the size range: n and len_2k up to 65536 (the multi-pass
+    # engine's 32.32.32 and four-pass plans), k up to 32768, fragment ids
+    # past 32767 kept by the first pattern together with a marked row.  Tiny
+    # blocks with an odd trailing word keep every file below 1 MiB (the two
+    # n = 65536 fixtures: 4 + 2 and 8 + 2 bytes per row instead of 16 + 2);
+    # cap 4 holds the marks (a row has at most block_bytes / 2 of them)
+    gen_blocks(ref, ora, "blk_k5000_m3000", 5000, 3000, 0, 8, 16 + 2, 61, 2, 8, out,
+               cap=4, keep=(0, 7999))
+    gen_blocks(ref, ora, "blk_k16384_m16384", 16384, 16384, 0, 8, 8 + 2, 62, 1, 8, out,
+               cap=4, keep=(0, 32767))
+    gen_blocks(ref, ora, "blk_k32768_m32768", 32768, 32768, 0, 8, 4 + 2, 63, 1, 8, out,
+               cap=4, keep=(0, 32767, 32768, 65535))
+    gen_blocks(ref, ora, "blk_k260_m65276_sys", 260, 65276, 1, 8, 8 + 2, 64, 2, 8, out,
+               cap=4, keep=(0, 32767, 32768, 65535))
 
     def gen_scn(*a):
         if not only or a[2] in only:

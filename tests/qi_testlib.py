@@ -36,6 +36,7 @@ def oracle():
         for fn in ("qo_add", "qo_sub", "qo_mul", "qo_exp", "qo_inv",
                    "qo_nth_root", "qo_code_len"):
             getattr(lib, fn).restype = C.c_uint32
+        lib.qo_ctx_bytes.restype = C.c_size_t
         _oracle = lib
     return _oracle
 
@@ -48,6 +49,17 @@ def ptrs(arrs):
     return p
 
 
+def row_ptrs(a, present=None):
+    """ptrs() of the rows of one C-contiguous 2-D uint8 array (rows where
+    `present` is false: NULL), built from the addresses: a code of 65536 rows
+    needs no 65536 ctypes casts.  The caller keeps `a` alive."""
+    assert a.dtype == np.uint8 and a.ndim == 2 and a.flags.c_contiguous
+    addr = a.ctypes.data + np.arange(a.shape[0], dtype=np.uint64) * np.uint64(a.strides[0])
+    if present is not None:
+        addr = np.where(np.asarray(present, bool), addr, np.uint64(0))
+    return (C.POINTER(C.c_uint8) * a.shape[0]).from_buffer_copy(addr.astype(np.uint64).tobytes())
+
+
 def vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -56,6 +68,11 @@ def codec(k, m, sys_):
     c = Codec()
     assert oracle().qo_codec_init(C.byref(c), k, m, int(sys_)) == 0
     return c
+
+
+def ctx_buffer(c):
+    """Room for the oracle's qo_ctx of codec c (sized by the oracle itself)."""
+    return C.create_string_buffer(oracle().qo_ctx_bytes(C.byref(c)))
 
 
 def load(name):
@@ -123,9 +140,8 @@ def oracle_encode_blocks(k, m, sys_, data, cap=None):
     outs = np.zeros((c.n_outputs, B), np.uint8)
     oor = np.zeros((c.n_outputs, cap), np.uint32)
     cnt = np.zeros(c.n_outputs, np.uint32)
-    rows = [np.ascontiguousarray(data[i]) for i in range(k)]
-    oracle().qo_encode_blocks(C.byref(c), ptrs(rows),
-                              ptrs([outs[i] for i in range(c.n_outputs)]),
+    rows = np.ascontiguousarray(data)
+    oracle().qo_encode_blocks(C.byref(c), row_ptrs(rows), row_ptrs(outs),
                               C.c_size_t(B), vp(oor), vp(cnt),
                               C.c_uint32(cap))
     return outs, oor, cnt
@@ -135,16 +151,20 @@ def oracle_decode_blocks(k, m, sys_, outputs, oor, cnt, missing, data=None):
     """Decode from the encoded outputs with `missing` (code_len flags)."""
     c = codec(k, m, sys_)
     B = outputs.shape[1]
-    dec = [np.zeros(B, np.uint8) if (not sys_ or missing[i] or data is None)
-           else data[i].copy() for i in range(k)]
-    par = [None if missing[(k + i) if sys_ else i] else outputs[i].copy()
-           for i in range(c.n_outputs)]
     missing = np.ascontiguousarray(missing, np.int32)
+    dec = np.zeros((k, B), np.uint8)
+    if sys_ and data is not None:
+        have = missing[:k] == 0
+        dec[have] = data[have]
+    par = np.ascontiguousarray(outputs).copy()
+    first = k if sys_ else 0
     wanted = np.ones(k, np.int32)
-    ok = oracle().qo_decode_blocks(C.byref(c), ptrs(dec), ptrs(par), vp(oor),
-                                   vp(cnt), C.c_uint32(oor.shape[1]),
-                                   vp(missing), vp(wanted), C.c_size_t(B))
-    return ok, np.stack(dec)
+    ok = oracle().qo_decode_blocks(
+        C.byref(c), row_ptrs(dec),
+        row_ptrs(par, missing[first:first + c.n_outputs] == 0), vp(oor),
+        vp(cnt), C.c_uint32(oor.shape[1]), vp(missing), vp(wanted),
+        C.c_size_t(B))
+    return ok, dec
 
 
 def oracle_nf4_encode_blocks(ws, k, m, data, cap):
@@ -185,7 +205,7 @@ def craft_oor_columns(k, m, sys_, data_rows, rng, n_cols, rows=None, col_range=N
     first = k if sys_ else 0
     cw = (C.c_uint32 * c.n)()
     din = (C.c_uint32 * k)()
-    ctx = C.create_string_buffer(4 + 16 * 4096 + 64)
+    ctx = ctx_buffer(c)
     if sys_:
         o.qo_ctx_init(C.byref(c), ctx, (C.c_uint32 * k)(*range(k)))
 
@@ -318,7 +338,6 @@ def check_windows_vs_oracle(k, m, sys_, data, outs, oor, cnt, wins, missing=None
 # hoped for (uniform random symbols make the sums a random walk, an order of
 # magnitude short of the bounds the kernels' range arguments rest on).
 
-_CTX_BYTES = 4 + 16 * 4096 + 64   # >= sizeof(qo_ctx)
 DOT_MODES = ("dot+", "dot-")
 MFMA_MODES = ("d2+", "d2-", "d01+", "d01-")
 ALL_MODES = DOT_MODES + MFMA_MODES
@@ -339,7 +358,7 @@ def generator_matrix(k, m, sys_):
     first = k if sys_ else 0
     cw = (C.c_uint32 * c.n)()
     din = (C.c_uint32 * k)()
-    ctx = C.create_string_buffer(_CTX_BYTES)
+    ctx = ctx_buffer(c)
     if sys_:
         assert o.qo_ctx_init(C.byref(c), ctx, (C.c_uint32 * k)(*range(k))) == 0
     G = np.zeros((c.n_outputs, k), np.int64)
@@ -357,7 +376,7 @@ def decode_matrix(k, m, sys_, ids):
     and loses the entries equal to 65536."""
     o = oracle()
     c = codec(k, m, sys_)
-    ctx = C.create_string_buffer(_CTX_BYTES)
+    ctx = ctx_buffer(c)
     assert o.qo_ctx_init(C.byref(c), ctx,
                          (C.c_uint32 * k)(*[int(v) for v in ids])) == 0
     win = (C.c_uint32 * k)()

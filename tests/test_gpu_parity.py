@@ -1066,6 +1066,13 @@ def test_plan_argument_checks():
     with pytest.raises(ValueError):
         plan.encode(good, out, cnt, torch.zeros(10, dtype=torch.int32,
                                                 device="cuda"), 64)
+    # the field's limits: 2k < 65537 and k + m <= 65536
+    for k, m in [(32768, 1), (32768, 32768)]:
+        big = qa.Plan(k, m)
+        assert (big.k, big.m, big.n_outputs) == (k, m, k + m)
+    for k, m in [(32769, 1), (32769, 32767), (32768, 32769), (1, 65536)]:
+        with pytest.raises(ValueError):
+            qa.Plan(k, m)
 
 
 # ------------------------------------------------------------------- RS-NF4

@@ -312,3 +312,115 @@ def test_erasure_decode_math(n, k, sys_):
             out[j + R1 * m] = sum(Y[v][j] * pow(ri, j * v, Q) * pow(w0i, v * m, Q)
                                   for v in range(R0)) % Q
     assert [out[t] * ninv % Q for t in range(k)] == P
+
+
+# ---------------------------------------------------------------------------
+# The multi-pass engine (ntt.hip: radices, transform, ntt_pass_kernel) for
+# max(n, len_2k) > 2048, mirrored with numpy in exact integer arithmetic: one
+# launch per radix over an N-point scratch column.  Pass 0 gathers its input
+# digit-reversed (trest, step) straight from the source rows, rows outside
+# [0, in_rows) reading as zero; pass q > 0 works in place on the groups of
+# stride S = R_0 ... R_{q-1} with the twiddle tw[ss j tstep twstep] from the
+# plan's w_nmax table; an inverse transform takes the inverse table and reads
+# the forward codelet's outputs at (R - u) % R.  Checked against the oracle's
+# radix-2 transforms at the lengths of the largest codes: 8192 = 32.16.16,
+# 32768 = 32.32.32 and 65536 = 16.16.16.16, the only four-pass plan.
+
+def radices(N):
+    """ntt.hip radices: radices <= 32, as even as possible."""
+    bits = N.bit_length() - 1
+    m = max(1, (bits + 4) // 5)
+    r, left = [], bits
+    for p in range(m):
+        bp = (left + (m - p) - 1) // (m - p)
+        r.append(1 << bp)
+        left -= bp
+    return r
+
+
+def multipass(x, N, nmax, inverse, in_rows):
+    """transform(): x (>= in_rows values) -> the N outputs in natural order."""
+    import numpy as np
+    rs = radices(N)
+    w = root(nmax)
+    if inverse:
+        w = pow(w, Q - 2, Q)
+    tw = np.ones(nmax, np.int64)
+    for e in range(1, nmax):
+        tw[e] = tw[e - 1] * w % Q
+    twstep = nmax // N
+    src = np.zeros(N, np.int64)
+    src[:in_rows] = np.asarray(x[:in_rows], np.int64)
+    scr = np.full(N, -1, np.int64)
+    S = 1
+    for q, R in enumerate(rs):
+        wr = root(R)
+        M = np.array([[pow(wr, u * j, Q) for j in range(R)] for u in range(R)], np.int64)
+        grp = np.arange(N // R)
+        ss = grp % S
+        b = (grp // S) * (S * R)
+        j = np.arange(R)
+        pos = (b + ss)[:, None] + j[None, :] * S
+        if q == 0:
+            trest, Sp = np.zeros_like(b), R
+            for Rp in rs[1:]:
+                trest += ((b // Sp) % Rp) * (N // (Sp * Rp))
+                Sp *= Rp
+            t = trest[:, None] + j[None, :] * (N // R)
+            assert sorted(t.ravel().tolist()) == list(range(N))   # a permutation
+            v = src[t]
+        else:
+            tstep = N // (S * R)
+            e = ss[:, None] * j[None, :] * tstep * twstep
+            assert e.max() < nmax
+            v = scr[pos] * tw[e] % Q
+        y = v @ M.T % Q
+        if inverse:
+            y = y[:, (R - j) % R]
+        scr[pos] = y
+        S *= R
+    assert S == N
+    return scr
+
+
+def test_multipass_radices():
+    assert radices(4096) == [16, 16, 16] and radices(8192) == [32, 16, 16]
+    assert radices(16384) == [32, 32, 16] and radices(32768) == [32, 32, 32]
+    assert radices(65536) == [16, 16, 16, 16]
+    for bits in range(1, 17):
+        r = radices(1 << bits)
+        assert max(r) <= 32 and len(r) <= 4
+        prod = 1
+        for v in r:
+            prod *= v
+        assert prod == 1 << bits
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("N,nmax,in_rows", [
+    (8192, 16384, 5000),     # NTT_n of (5000, 3000): len_2k = 16384 > n
+    (8192, 8192, 8192),
+    (32768, 65536, 16385),   # n of (16385, 16383), len_2k = 65536
+    (32768, 32768, 260),     # NTT_n of (260, 32508): most groups read zeros
+    (65536, 65536, 32768),   # four passes: (32768, 32768)
+    (65536, 65536, 65536),
+])
+def test_multipass_vs_oracle(N, nmax, in_rows, inverse):
+    import ctypes as C
+
+    import numpy as np
+    from qi_testlib import oracle, vp
+    o = oracle()
+    rng = np.random.default_rng([N, nmax, in_rows, inverse])
+    x = rng.integers(0, Q, N).astype(np.uint32)
+    x[rng.integers(0, in_rows, 4)] = 65536
+    x[in_rows:] = 0
+    ref = np.zeros(N, np.uint32)
+    if inverse:
+        o.qo_fft_inv(N, C.c_uint32(root(N)), vp(x), vp(ref))
+    else:
+        dl = 1 << (in_rows - 1).bit_length()
+        o.qo_fft(N, dl, C.c_uint32(root(N)), vp(x), in_rows, vp(ref))
+    got = multipass(x, N, nmax, inverse, in_rows)
+    bad = np.flatnonzero(got != ref)
+    assert len(bad) == 0, (len(bad), bad[:8].tolist())

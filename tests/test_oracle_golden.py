@@ -167,3 +167,29 @@ def test_oracle_fewer_than_k_fails():
     miss[:m + 1] = 1
     ok, _ = oracle_decode_blocks(k, m, 0, outs, oor, cnt, miss)
     assert ok == 0
+
+
+def test_oracle_largest_k_from_a_worker_thread():
+    """Every buffer of the oracle is sized from the codec and lives on the
+    heap: an encode and a decode at k = 32768, n = 65536 run from a thread
+    with a 256 KiB stack (the pool of test_cfg2_full_batch_vs_oracle calls
+    the oracle from worker threads)."""
+    import threading
+    g = load("blk_k32768_m32768")
+    k, m, sys_, pkt, B, cap = (int(v) for v in g["params"])
+    res = {}
+
+    def work():
+        outs, oor, cnt = oracle_encode_blocks(k, m, sys_, g["data"], cap)
+        res["enc"] = (outs == g["outputs"]).all() and (oor == g["oor"]).all()
+        ok, dec = oracle_decode_blocks(k, m, sys_, g["outputs"], g["oor"], g["oor_count"],
+                                       g["missing"][0], g["data"])
+        res["dec"] = ok == 1 and (dec == g["decoded"][0]).all()
+    old = threading.stack_size(256 * 1024)
+    try:
+        t = threading.Thread(target=work)
+        t.start()
+        t.join()
+    finally:
+        threading.stack_size(old)
+    assert res == {"enc": True, "dec": True}
