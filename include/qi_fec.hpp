@@ -158,6 +158,25 @@ class RsFnt {
     // code in its own slot (at most 256 MiB of rows)
     bool repair_supported(size_t n_targets, size_t block_size_bytes) const;
 
+    // Delta update (qi_gpu_update): data rows ids[u] (below n_data, distinct)
+    // go from old_bufs[u] to new_bufs[u]; the coded fragments held here
+    // (parities_bufs[j] != nullptr, n_outputs entries) follow in place, and
+    // their parities_props[j] are replaced by the marks of the updated rows
+    // (ascending).  Only those 2 ids.size() + held rows are staged: the other
+    // data rows of the stripe are not needed.  A bucket overflow on the
+    // device is retried once with the exact capacity, as by the other block
+    // calls.  Throws std::invalid_argument where update_supported() is false,
+    // or an id is out of range or repeated, or no fragment is held.
+    void update_blocks_vertical(const std::vector<int>& ids, std::vector<uint8_t*>& old_bufs,
+                                std::vector<uint8_t*>& new_bufs,
+                                std::vector<uint8_t*>& parities_bufs,
+                                std::vector<Properties>& parities_props,
+                                size_t block_size_bytes);
+    // 1 <= n_rows <= min(8, n_data), 1 <= n_held <= n_outputs, and a block
+    // whose 2 n_rows + n_held rows fit the single-chunk device staging (at
+    // most 256 MiB of rows)
+    bool update_supported(size_t n_rows, size_t n_held, size_t block_size_bytes) const;
+
     // Fused verify (scrubbing): check the present fragments against each
     // other on the device without rebuilding a row (qi_gpu_verify).  The
     // basis is the first n_data present fragments, chosen as

@@ -32,7 +32,9 @@
  * the dot2 and register-codelet kernels (k <= 256, 64-bit row offsets) or the
  * NTT engine (k > 256) instead of the matrix cores.  That path is tested bit
  * for bit against the reference, regions past 4 GiB included, but nobody has
- * timed it: expect it to be slower, by an unmeasured amount.
+ * timed it: expect it to be slower, by an unmeasured amount.  (qi_gpu_update
+ * has one kernel for every layout: it addresses its rows flat, with 64-bit
+ * row offsets, whatever the size of the regions.)
  *
  * OOR marks are kept in *buckets*: counts[s*slots + slot] (u32) and
  * entries[(s*slots + slot)*cap + e] (u32 word offset within the row).  Encode
@@ -300,6 +302,79 @@ int qi_gpu_verify(qi_plan* plan, const void* d_ctx, int n_checks,
  * until its next call. */
 const char* qi_gpu_verify_kernels(const qi_plan* plan, int n_checks, long long words);
 
+/* ---- Delta update: some data rows of a stripe change and the coded rows
+ * must follow.  Both code types are linear, so when data row i goes from old
+ * to new, coded slot f moves by a constant times the difference,
+ *   out_f = coded_f + c(f, i) (new_i - old_i)   (mod 65537)
+ *   c(f, i) = r^(f i)      non-systematic (fragment f = sum_t d_t r^(f t))
+ *   c(f, i) = l_i(r^(k+f)) systematic (l_i: the Lagrange basis over r^0 ..
+ *                          r^(k-1); slot f is parity f)
+ * and an update of U rows reads 2 U + R rows and writes R: no other data row
+ * of the stripe is needed, and the cost does not depend on k.  (A full
+ * qi_gpu_encode reads k rows and writes n_outputs: by bytes the update wins
+ * when 2 U + 2 R < k + n_outputs for R = n_outputs.  At k = 16, m = 48 it
+ * moves MORE bytes than the encode -- it is then still the only way for a
+ * node that does not hold the other 15 rows.)
+ *
+ * Supported on every plan qi_plan_create accepts (any k, both code types),
+ * for 1 <= n_rows <= min(QI_UPDATE_MAX_ROWS, k) changed rows and 1 <= n_slots
+ * <= n_outputs coded rows, the same counts for every stripe of a call; the
+ * ids and slots themselves may differ per stripe.  A count out of range
+ * returns -1 (qi_gpu_update_ctx_bytes: 0) and launches nothing.
+ *
+ * Slots are the encode's output indices (parity j of a systematic plan, coded
+ * row j otherwise).  The coded rows, the output rows and both bucket sets are
+ * addressed by slot (slots = n_outputs), exactly as qi_gpu_encode wrote them;
+ * rows and buckets of slots not listed are not touched.  d_slots = NULL means
+ * all of them, slot j = j, and needs n_slots = n_outputs.  Row u of d_old /
+ * d_new (n_rows rows per stripe) holds the old / new contents of data row
+ * d_ids[s * n_rows + u].
+ *
+ * In place: d_out == d_coded with equal strides is allowed and is the
+ * expected use (every column is read before it is written, by the lane that
+ * writes it); any other overlap between the tensors of a call is undefined.
+ * The two bucket sets must be distinct.  Clear the out counts of the listed
+ * slots first (qi_gpu_oor_clear); NULL out counts skip the recording (65536
+ * is still stored as 0).  After an in-place update the out buckets are the
+ * rows' marks: swap the two bucket sets for the next call.
+ *
+ * Marks: an input symbol listed in its slot's in-bucket is 65536 (stored as
+ * 0), as qi_gpu_encode records it; an updated symbol equal to 65536 is stored
+ * as 0 and recorded, the count going on past out_cap as in the encode.  Data
+ * rows carry no marks.  No mark is refused: a bucket with count <= in_cap is
+ * restored in full however dense; a count above in_cap raises bit 1 of
+ * qi_gpu_take_error.  NULL in counts: no marks.
+ *
+ * Bad ids -- an id not below k, a repeated id, a slot not below n_outputs, a
+ * repeated slot -- raise bit 2 of qi_gpu_take_error when the context is
+ * built; the update of such a stripe is then unspecified, but stays inside
+ * the caller's rows.
+ *
+ * The context holds, per stripe, the n_slots x n_rows coefficients, the slots
+ * and the ids (it does not depend on the width).  For a systematic plan the
+ * first qi_gpu_update_ctx builds two per-plan tables on the host (O(k + m)
+ * field operations, under a lock) and uploads them with a blocking copy;
+ * everything else is asynchronous on `stream`.  Any positive strides with a
+ * unit inner stride, per tensor, at any alignment (rows and strides that are
+ * all multiples of 16 bytes move as 16-byte pieces per lane). */
+#define QI_UPDATE_MAX_ROWS 8
+size_t qi_gpu_update_ctx_bytes(const qi_plan* plan, int n_rows, int n_slots, int n_stripes);
+int qi_gpu_update_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][U] data row ids, < k*/,
+                      const uint16_t* d_slots /*[S][R] coded-row slots, or NULL*/,
+                      int n_rows, int n_slots, int n_stripes, void* d_ctx, void* stream);
+int qi_gpu_update(qi_plan* plan, const void* d_ctx, int n_rows, int n_slots,
+                  const uint16_t* d_old, long long old_ss, long long old_rs,
+                  const uint16_t* d_new, long long new_ss, long long new_rs,
+                  const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                  uint16_t* d_out, long long oss, long long ors,
+                  uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                  long long words, int n_stripes, void* stream);
+/* Names of the kernels such an update launches (rows and strides at
+ * multiples of 16 bytes), as "update=<context kernel> + <kernel>"; "" for
+ * counts out of range.  Per calling thread, valid until its next call. */
+const char* qi_gpu_update_kernels(const qi_plan* plan, int n_rows, int n_slots, long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -351,6 +426,20 @@ int qi_fec_verify_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
                          const uint32_t* oor, const uint32_t* oor_count,
                          uint32_t oor_cap, const int* missing, long long* result,
                          size_t block_bytes);
+
+/* Delta update of the held coded fragments (RsFnt::update_blocks_vertical,
+ * include/qi_fec.hpp): data rows ids[0 .. n_rows) go from old_rows[u] to
+ * new_rows[u] (block_bytes each); parities[j] != NULL are the coded fragments
+ * held here, updated in place, their marks (oor / oor_count, oor_cap entries
+ * per fragment, as qi_fec_encode_blocks returned them) replaced by the new
+ * ones, ascending, with exact counts (a count above oor_cap: only oor_cap
+ * entries were written).  Returns 1 updated, -1 error (an id out of range or
+ * repeated, no fragment held), -2 shape not supported (n_rows outside 1 ..
+ * min(8, k), or 2 n_rows + held rows wider than the single-chunk staging):
+ * encode again instead. */
+int qi_fec_update_blocks(qi_fec* f, const int* ids, int n_rows, uint8_t** old_rows,
+                         uint8_t** new_rows, uint8_t** parities, uint32_t* oor,
+                         uint32_t* oor_count, uint32_t oor_cap, size_t block_bytes);
 
 /* Stream API (encode_streams_vertical / decode_streams_vertical,
  * src/fec_base.h:463-542, 898-1048) over caller memory: each fragment is a

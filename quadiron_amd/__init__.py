@@ -64,6 +64,11 @@ def _declare(lib):
         "qi_gpu_verify": (I, [V, V, I, V, V, LL, LL, V, LL, LL, V, V, I, V, I,
                               V, V, V, LL, I, V]),
         "qi_gpu_verify_kernels": (C.c_char_p, [V, I, LL]),
+        "qi_gpu_update_ctx_bytes": (SZ, [V, I, I, I]),
+        "qi_gpu_update_ctx": (I, [V, V, V, I, I, I, V, V]),
+        "qi_gpu_update": (I, [V, V, I, I, V, LL, LL, V, LL, LL, V, LL, LL, V, V, I,
+                              V, LL, LL, V, V, I, LL, I, V]),
+        "qi_gpu_update_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -75,6 +80,7 @@ def _declare(lib):
         "qi_fec_repair_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, c_u8pp, V,
                                      V, U32, SZ]),
         "qi_fec_verify_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
+        "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
                                       c_u8pp]),
@@ -444,6 +450,83 @@ class Plan:
             raise RuntimeError(f"qi_gpu_verify failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    UPDATE_MAX_ROWS = 8  # QI_UPDATE_MAX_ROWS
+
+    def update_kernels(self, n_rows, n_slots, words):
+        """'update=<context kernel> + <kernel>' an update of n_rows data rows
+        and n_slots coded rows launches (qi_gpu_update_kernels); '' for
+        counts out of range."""
+        return lib().qi_gpu_update_kernels(self.h, n_rows, n_slots, words).decode()
+
+    def update_ctx_bytes(self, n_rows, n_slots, n_stripes):
+        """0 when n_rows is outside 1 .. min(8, k) or n_slots outside
+        1 .. n_outputs."""
+        return lib().qi_gpu_update_ctx_bytes(self.h, n_rows, n_slots, n_stripes)
+
+    def update_ctx(self, ids, slots, ctx, stream=None):
+        """ids: int16 tensor [S, U] (the changed data rows); slots: int16
+        tensor [S, R] (the coded rows to update, by encode output index) or
+        None for all n_outputs of them."""
+        import torch
+        if ids.dim() != 2 or (slots is not None and (
+                slots.dim() != 2 or slots.shape[0] != ids.shape[0])):
+            raise ValueError("ids: expected [S, U], slots: [S, R] or None")
+        S, U = ids.shape
+        R = slots.shape[1] if slots is not None else self.n_outputs
+        need = self.update_ctx_bytes(U, R, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"update of {U} rows into {R} slots is not supported "
+                             f"(1 <= U <= min(8, k), 1 <= R <= n_outputs)")
+        _flat(ids, "ids", S * U, (torch.int16, torch.uint16))
+        _flat(slots, "slots", S * R, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        rc = lib().qi_gpu_update_ctx(
+            self.h, ids.data_ptr(), slots.data_ptr() if slots is not None else None,
+            U, R, S, ctx.data_ptr(), self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_update_ctx failed: {rc}")
+
+    def update(self, ctx, n_slots, old, new, coded, out=None, counts=None,
+               entries=None, cap=0, out_counts=None, out_entries=None,
+               out_cap=0, stream=None, check=True):
+        """old, new: [S, U, P], row u the old / new contents of data row
+        ids[s][u] of the context; coded: [S, n_out, P] (rows by slot, with
+        their OOR buckets counts / entries); out: the same shape, None for
+        in place; the updated rows' marks go to out_counts / out_entries
+        (slots = n_outputs, cleared by the caller, distinct from counts /
+        entries).  n_slots: the R the context was built with.  Returns the
+        sticky error flags when check."""
+        import torch
+        _rows(old, "old")
+        S, U, P = old.shape
+        _rows(new, "new", U, S)
+        _rows(coded, "coded", self.n_outputs, S)
+        out = coded if out is None else out
+        _rows(out, "out", self.n_outputs, S)
+        if not new.shape[2] == coded.shape[2] == out.shape[2] == P:
+            raise ValueError("old, new, coded and out differ in width")
+        need = self.update_ctx_bytes(U, n_slots, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"update of {U} rows into {n_slots} slots is not supported "
+                             f"(1 <= U <= min(8, k), 1 <= R <= n_outputs)")
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, self.n_outputs)
+        _oor(out_counts, out_entries, out_cap, S, self.n_outputs)
+        rc = lib().qi_gpu_update(
+            self.h, ctx.data_ptr(), U, n_slots,
+            old.data_ptr(), old.stride(0), old.stride(1),
+            new.data_ptr(), new.stride(0), new.stride(1),
+            coded.data_ptr(), coded.stride(0), coded.stride(1),
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            out.data_ptr(), out.stride(0), out.stride(1),
+            out_counts.data_ptr() if out_counts is not None else None,
+            out_entries.data_ptr() if out_entries is not None else None,
+            int(out_cap), P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_update failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -521,6 +604,29 @@ class Fec:
         if rc < 0:
             raise RuntimeError(f"qi_fec_verify_blocks failed: {rc}")
         return res if rc == 1 else None
+
+    def update_blocks(self, ids, old_rows, new_rows, parities, oor, counts):
+        """Delta update (qi_fec_update_blocks): data rows `ids` go from
+        old_rows[u] to new_rows[u] (uint8 rows); parities: n_outputs uint8
+        rows, None where the fragment is not held -- the held ones are updated
+        in place.  oor (n_outputs, cap) uint32 and counts (n_outputs,) uint32
+        hold their marks and are replaced, for the held rows, by the new marks
+        (ascending, counts exact).  Raises ValueError for an unsupported shape
+        (more than min(8, k) rows, a block wider than one staging chunk)."""
+        import numpy as np
+        idv = np.ascontiguousarray(ids, np.int32)
+        if oor.dtype != np.uint32 or counts.dtype != np.uint32 or not (
+                oor.flags.c_contiguous and counts.flags.c_contiguous):
+            raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        rc = lib().qi_fec_update_blocks(
+            self.h, idv.ctypes.data_as(C.c_void_p), len(idv),
+            ptr_array(list(old_rows)), ptr_array(list(new_rows)),
+            ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p), oor.shape[1], len(old_rows[0]))
+        if rc == -2:
+            raise ValueError("update_blocks: shape not supported")
+        if rc != 1:
+            raise RuntimeError(f"qi_fec_update_blocks failed: {rc}")
 
     def close(self):
         if self.h:

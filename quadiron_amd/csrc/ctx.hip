@@ -1679,4 +1679,110 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// ---------------------------------------------------------------------------
+// Delta-update contexts (qi_gpu_update_ctx; the coefficients of
+// update_coef.h on the device).  Per stripe, update_ctx_words(U, R) words:
+//   R x UP balanced coefficients c(slot_j, id_u) in [-32768, 32768] (UP = U
+//   rounded up to 1, 2, 4, 8; the pad columns 0), the R slots, the UP ids
+//   (pad 0), as dwords -- every word written.
+// non-systematic: c = r^(slot id mod n), one rpow chain; systematic: c =
+// A(y_j) / ((y_j - x_i) A'(x_i)) from the plan's tables `tab` (A(y_j), j < m,
+// then 1 / A'(x_i), i < k) with one inversion per (slot, id) (inv_lz).
+// A block takes kUpdCtxThreads slots of one stripe, a thread one slot and its
+// UP coefficients.  Every block checks the whole stripe: ids below k and
+// distinct (at most 8: compared pairwise), slots below n_out and distinct (a
+// 65536-bit map in LDS); a bad one raises kErrBadIds and goes into the context
+// as 0, so that the update stays inside the caller's rows.
+// ---------------------------------------------------------------------------
+constexpr int kUpdCtxThreads = 256;
+
+__global__ __launch_bounds__(kUpdCtxThreads) void update_ctx_kernel(
+    int k, int n_out, int sys, RPow2 rp, int lgn, int U, int UP, int R,
+    const uint16_t* __restrict__ ids, const uint16_t* __restrict__ slots,
+    const uint32_t* __restrict__ tab, int32_t* __restrict__ ctx, long long ctx_stride, int bps,
+    uint32_t* err)
+{
+    __shared__ uint32_t seen[65536 / 32];
+    __shared__ uint32_t s_id[8];
+    const int s = static_cast<int>(blockIdx.x) / bps;
+    const int cb = static_cast<int>(blockIdx.x) - s * bps;
+    const int tid = static_cast<int>(threadIdx.x);
+    int32_t* c = ctx + static_cast<long long>(s) * ctx_stride;
+    const uint16_t* sl_s = slots ? slots + static_cast<long long>(s) * R : nullptr;
+    bool bad = false;
+    if (sl_s) {
+        for (int i = tid; i < 65536 / 32; i += kUpdCtxThreads)
+            seen[i] = 0;
+        __syncthreads();
+        for (int j = tid; j < R; j += kUpdCtxThreads) {
+            const uint32_t sl = sl_s[j];
+            const uint32_t bit = 1u << (sl & 31u);
+            if (sl >= static_cast<uint32_t>(n_out) || (atomicOr(&seen[sl >> 5], bit) & bit))
+                bad = true;
+        }
+    }
+    if (tid < 8) {
+        uint32_t id = 0;
+        if (tid < U) {
+            const uint16_t* id_s = ids + static_cast<long long>(s) * U;
+            id = id_s[tid];
+            for (int u = 0; u < tid; u++)
+                bad |= id_s[u] == id;
+            if (id >= static_cast<uint32_t>(k)) {
+                bad = true;
+                id = 0;
+            }
+        }
+        s_id[tid] = id;
+    }
+    if (bad)
+        atomicOr(err, kErrBadIds);
+    __syncthreads();
+    const long long slots_off = static_cast<long long>(R) * UP;
+    const int j = cb * kUpdCtxThreads + tid;
+    if (j < R) {
+        uint32_t sl = sl_s ? sl_s[j] : static_cast<uint32_t>(j);
+        if (sl >= static_cast<uint32_t>(n_out))
+            sl = 0;
+        c[slots_off + j] = static_cast<int32_t>(sl);
+        const uint32_t y = sys ? canon_lz(rpow_lz(rp, static_cast<uint32_t>(k) + sl, lgn)) : 0;
+        const uint32_t ay = sys ? tab[sl] : 0;
+        for (int u = 0; u < UP; u++) {
+            uint32_t co = 0;
+            if (u < U) {
+                const uint32_t id = s_id[u];
+                if (!sys) {
+                    // sl < 2^16, id < 2^15: the product fits 32 bits; n = 2^lgn
+                    co = canon_lz(rpow_lz(rp, (sl * id) & ((1u << lgn) - 1u), lgn));
+                } else {
+                    // k + sl < n and id < k: y != x, the divisor is not 0
+                    const uint32_t x = canon_lz(rpow_lz(rp, id, lgn));
+                    co = mulm(mulm(ay, inv_lz(subm(y, x))), tab[n_out + id]);
+                }
+            }
+            c[static_cast<long long>(j) * UP + u] = balanced(co);
+        }
+    }
+    if (cb == 0 && tid < UP)
+        c[slots_off + R + tid] = static_cast<int32_t>(s_id[tid]);
+}
+
+int launch_update_ctx(int k, int n, int n_out, uint32_t r, int sys, const uint32_t* d_tab,
+                      const uint16_t* d_ids, const uint16_t* d_slots, int U, int UP, int R, int S,
+                      int32_t* d_ctx, long long ctx_stride, uint32_t* err, hipStream_t st)
+{
+    if (U < 1 || U > UP || UP > 8 || R < 1 || R > n_out || S <= 0 || (sys && !d_tab))
+        return -3;
+    int lgn = 0;
+    const RPow2 rp = make_rpow2(r, n, &lgn);
+    const int bps = (R + kUpdCtxThreads - 1) / kUpdCtxThreads;
+    const long long blocks = static_cast<long long>(bps) * S;
+    if (blocks > 0x7fffffffLL)
+        return -3;
+    hipLaunchKernelGGL(update_ctx_kernel, dim3(static_cast<unsigned>(blocks)),
+                       dim3(kUpdCtxThreads), 0, st, k, n_out, sys, rp, lgn, U, UP, R, d_ids,
+                       d_slots, d_tab, d_ctx, ctx_stride, bps, err);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace qi

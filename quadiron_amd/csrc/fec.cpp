@@ -644,6 +644,118 @@ bool RsFnt::verify_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     return true;
 }
 
+// ---- delta update (single chunk; qi_gpu_update_ctx, then the update in
+// place on the staged rows) ----
+bool RsFnt::update_supported(size_t n_rows, size_t n_held, size_t block_size_bytes) const
+{
+    const size_t words = block_size_bytes / word_size;
+    if (n_rows < 1 || n_rows > std::min<size_t>(QI_UPDATE_MAX_ROWS, n_data) || n_held < 1 ||
+        n_held > n_outputs)
+        return false;
+    if (words == 0 || words > chunk_bytes(buf_size) / 2)
+        return false;
+    // the old and the new rows and the held coded rows, back to back
+    return (2 * n_rows + n_held) * pad_words(words) * 2 <= (size_t{256} << 20);
+}
+
+void RsFnt::update_blocks_vertical(const std::vector<int>& ids, std::vector<uint8_t*>& old_bufs,
+                                   std::vector<uint8_t*>& new_bufs,
+                                   std::vector<uint8_t*>& parities_bufs,
+                                   std::vector<Properties>& parities_props,
+                                   size_t block_size_bytes)
+{
+    // validate
+    const size_t U = ids.size();
+    std::vector<uint16_t> held;  // the slots held here, ascending
+    for (size_t j = 0; j < n_outputs && j < parities_bufs.size(); j++)
+        if (parities_bufs[j])
+            held.push_back(static_cast<uint16_t>(j));
+    const size_t R = held.size();
+    if (!update_supported(U, R, block_size_bytes))
+        throw std::invalid_argument("RsFnt::update_blocks_vertical: unsupported shape");
+    if (old_bufs.size() < U || new_bufs.size() < U || parities_props.size() < n_outputs)
+        throw std::invalid_argument("RsFnt::update_blocks_vertical: buffers");
+    for (size_t u = 0; u < U; u++) {
+        if (ids[u] < 0 || ids[u] >= static_cast<int>(n_data) || !old_bufs[u] || !new_bufs[u])
+            throw std::invalid_argument("RsFnt::update_blocks_vertical: id out of range");
+        for (size_t v = 0; v < u; v++)
+            if (ids[v] == ids[u])
+                throw std::invalid_argument("RsFnt::update_blocks_vertical: id repeated");
+    }
+    const size_t words = block_size_bytes / word_size;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // stage: U old rows, U new rows, the R held rows (row j = held[j]: the
+    // compact addressing of update_rows), their buckets, the output counts
+    std::vector<const Properties*> marked(R);
+    for (size_t j = 0; j < R; j++) {
+        parities_props[held[j]].sort();
+        marked[j] = &parities_props[held[j]];
+    }
+    const stage::PackedMarks pm = stage::pack_marks(marked, 0, words);
+    const size_t P = pad_words(words);
+    const auto off = stage::layout({R * 4, pm.entries.size() * 4, R * 4});
+    const size_t ctx_bytes =
+        qi_gpu_update_ctx_bytes(pl, static_cast<int>(U), static_cast<int>(R), 1);
+    reserve(h.in, (2 * U + R) * P * 2);
+    reserve(h.counts, off[3]);
+    reserve(h.ids, (U + R) * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint16_t* dold = static_cast<uint16_t*>(h.in.p);
+    uint16_t* dnew = dold + U * P;
+    uint16_t* dcoded = dnew + U * P;
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
+    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
+    const auto upload_coded = [&] {
+        for (size_t j = 0; j < R; j++)
+            h2d(dcoded + j * P, parities_bufs[held[j]], words * 2, s);
+    };
+    for (size_t u = 0; u < U; u++) {
+        h2d(dold + u * P, old_bufs[u], words * 2, s);
+        h2d(dnew + u * P, new_bufs[u], words * 2, s);
+    }
+    upload_coded();
+    upload_marks(pm, dcnt, dent, s);
+    std::vector<uint16_t> hids(ids.begin(), ids.end());
+    hids.insert(hids.end(), held.begin(), held.end());
+    h2d(h.ids.p, hids.data(), (U + R) * 2, s);
+    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
+    check_rc(qi_gpu_update_ctx(pl, dids, dids + U, static_cast<int>(U), static_cast<int>(R), 1,
+                               h.ctx.p, s),
+             "update context");
+    // launch in place; a second attempt starts from the rows as they were
+    const long long Pl = static_cast<long long>(P);
+    std::vector<uint32_t> ocnt(R);
+    const size_t ocap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, R * c * 4);
+            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+            check_rc(update_rows(pl, h.ctx.p, static_cast<int>(U), static_cast<int>(R), 1, dold,
+                                 0, Pl, dnew, 0, Pl, dcoded, 0, Pl, dcnt, dent,
+                                 static_cast<int>(pm.cap), dcoded, 0, Pl, docnt,
+                                 static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                 static_cast<long long>(words), 1, s),
+                     "update");
+        },
+        [&] { return read_max(ocnt, docnt, s); }, upload_coded);
+    // collect
+    std::vector<uint32_t> ent(R * ocap);
+    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
+    for (size_t j = 0; j < R; j++)
+        d2h(parities_bufs[held[j]], dcoded + j * P, words * 2, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: update failed (bad ids or OOR bucket capacity)");
+    for (size_t j = 0; j < R; j++) {
+        parities_props[held[j]] = Properties();
+        stage::add_sorted(parities_props[held[j]], ent.data() + j * ocap, ocnt[j], 0);
+    }
+}
+
 namespace {
 
 // One stage of the pipelined stream API: pinned host staging, device
@@ -1502,6 +1614,47 @@ int qi_fec_verify_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const ui
             result[3 * i + 2] = res[i].first;
         }
         return ok ? 1 : 0;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_update_blocks(qi_fec* h, const int* ids, int n_rows, uint8_t** old_rows,
+                         uint8_t** new_rows, uint8_t** parities, uint32_t* oor,
+                         uint32_t* oor_count, uint32_t cap, size_t block_bytes)
+{
+    try {
+        if (!h || !ids || !old_rows || !new_rows || !parities || n_rows < 0)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        size_t held = 0;
+        for (unsigned j = 0; j < f.n_outputs; j++)
+            held += parities[j] != nullptr;
+        if (held == 0)
+            return -1;
+        if (!f.update_supported(static_cast<size_t>(n_rows), held, block_bytes))
+            return -2;
+        std::vector<int> iv(ids, ids + n_rows);
+        std::vector<uint8_t*> ov(old_rows, old_rows + n_rows), nv(new_rows, new_rows + n_rows);
+        std::vector<uint8_t*> pv(parities, parities + f.n_outputs);
+        // the held fragments' marks only (oor_count null: none)
+        std::vector<qi::Properties> props(f.n_outputs);
+        for (unsigned j = 0; j < f.n_outputs; j++)
+            for (uint32_t e = 0; pv[j] && oor_count && e < std::min(oor_count[j], cap); e++)
+                props[j].add(oor[static_cast<size_t>(j) * cap + e], qi::OOR_MARK);
+        f.update_blocks_vertical(iv, ov, nv, pv, props, block_bytes);
+        for (unsigned j = 0; j < f.n_outputs; j++) {
+            if (!pv[j] || !oor_count)
+                continue;
+            uint32_t c = 0;
+            for (auto const& it : props[j].get_map()) {
+                if (c < cap)
+                    oor[static_cast<size_t>(j) * cap + c] = static_cast<uint32_t>(it.first);
+                c++;
+            }
+            oor_count[j] = c;
+        }
+        return 1;
     } catch (...) {
         return -1;
     }

@@ -316,6 +316,8 @@ void qi_plan_destroy(qi_plan* p)
         (void)hipFree(p->d_rowid);
     if (p->d_err)
         (void)hipFree(p->d_err);
+    if (p->d_upd_tab)
+        (void)hipFree(p->d_upd_tab);
     ntt_plan_free(p);
     p->host.release();
     delete p;

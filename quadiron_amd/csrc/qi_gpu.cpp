@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -10,6 +11,7 @@
 #include "gf65537.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
+#include "update_coef.h"
 
 using namespace qi;
 
@@ -146,6 +148,38 @@ int build_ctx(qi_plan* p, const uint16_t* d_ids, int n_stripes, const Oor* in,
     return launch_decode_ctx(p->k, p->n, p->r, p->sys ? 1 : 0, L, d_ids, n_stripes,
                              static_cast<int32_t*>(d_ctx), cs, in, slot_base, by_pos,
                              words, dot2, p->d_err, s);
+}
+
+static bool update_ok(const qi_plan* p, int U, int R)
+{
+    return U >= 1 && U <= std::min(QI_UPDATE_MAX_ROWS, p->k) && R >= 1 && R <= p->n_outputs;
+}
+
+// qi_gpu_update; by_pos: the coded / output row and both buckets of the j-th
+// listed slot are found by its position j (rows and slots = R: the compact
+// staging of the block API) instead of by the slot
+int update_rows(qi_plan* p, const void* d_ctx, int U, int R, int by_pos, const uint16_t* d_old,
+                long long old_ss, long long old_rs, const uint16_t* d_new, long long new_ss,
+                long long new_rs, const uint16_t* d_coded, long long css, long long crs,
+                const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                uint16_t* d_out, long long oss, long long ors, uint32_t* d_out_counts,
+                uint32_t* d_out_entries, int out_cap, long long words, int n_stripes,
+                hipStream_t s)
+{
+    if (!d_ctx || !d_old || !d_new || !d_coded || !d_out || n_stripes < 0 || words < 0)
+        return -1;
+    if (!update_ok(p, U, R))
+        return -1;
+    if (n_stripes == 0 || words == 0)
+        return 0;
+    const int slots = by_pos ? R : p->n_outputs;
+    const Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries), slots,
+                 in_cap};
+    const Oor outm{d_out_counts, d_out_entries, slots, out_cap};
+    return launch_update(static_cast<const int32_t*>(d_ctx), update_ctx_words(U, R), U,
+                         update_up(U), R, by_pos, d_old, old_ss, old_rs, d_new, new_ss, new_rs,
+                         d_coded, css, crs, in, d_out, oss, ors, outm, words, n_stripes, p->d_err,
+                         s);
 }
 
 }  // namespace qi
@@ -394,6 +428,83 @@ const char* qi_gpu_verify_kernels(const qi_plan* p, int R, long long words)
     names = "verify=" + repair_ctx_kernel_name(p->k, R) + " + " +
             matrix_kernel_names(repair_layout(p, R), words, true, p->sys != 0, false, true) +
             " + " + verify_marks_kernel_name();
+    return names.c_str();
+}
+
+// ---- delta update (any k): update_ctx_kernel leaves the R x UP coefficients
+// c(slot, id) per stripe, update_kernel streams the R coded rows past the U
+// row differences ----
+// the systematic plan's coefficient tables, built on the host and uploaded
+// once (the copy is complete when hipMemcpy returns, so every stream sees it)
+static int update_tables_ready(qi_plan* p)
+{
+    if (!p->sys)
+        return 0;
+    std::lock_guard<std::mutex> lock(p->upd_mu);
+    if (p->d_upd_tab)
+        return 0;
+    UpdateTables t;
+    if (!update_tables(p->k, p->m, p->r, t))
+        return -3;
+    t.ay.insert(t.ay.end(), t.iap.begin(), t.iap.end());
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, t.ay.size() * 4) != hipSuccess)
+        return -2;
+    if (hipMemcpy(d, t.ay.data(), t.ay.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return -2;
+    }
+    p->d_upd_tab = d;
+    return 0;
+}
+
+size_t qi_gpu_update_ctx_bytes(const qi_plan* p, int U, int R, int n_stripes)
+{
+    if (!p || n_stripes < 0 || !update_ok(p, U, R))
+        return 0;
+    return static_cast<size_t>(update_ctx_words(U, R)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_update_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_slots, int U, int R,
+                      int n_stripes, void* d_ctx, void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0)
+        return -1;
+    if (!update_ok(p, U, R) || (!d_slots && R != p->n_outputs))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids)
+        return -1;
+    if (int rc = update_tables_ready(p))
+        return rc;
+    return launch_update_ctx(p->k, p->n, p->n_outputs, p->r, p->sys, p->d_upd_tab, d_ids, d_slots,
+                             U, update_up(U), R, n_stripes, static_cast<int32_t*>(d_ctx),
+                             update_ctx_words(U, R), p->d_err, st(stream));
+}
+
+int qi_gpu_update(qi_plan* p, const void* d_ctx, int U, int R, const uint16_t* d_old,
+                  long long old_ss, long long old_rs, const uint16_t* d_new, long long new_ss,
+                  long long new_rs, const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                  uint16_t* d_out, long long oss, long long ors, uint32_t* d_out_counts,
+                  uint32_t* d_out_entries, int out_cap, long long words, int n_stripes,
+                  void* stream)
+{
+    if (!p)
+        return -1;
+    return qi::update_rows(p, d_ctx, U, R, 0, d_old, old_ss, old_rs, d_new, new_ss, new_rs,
+                           d_coded, css, crs, d_in_counts, d_in_entries, in_cap, d_out, oss, ors,
+                           d_out_counts, d_out_entries, out_cap, words, n_stripes, st(stream));
+}
+
+const char* qi_gpu_update_kernels(const qi_plan* p, int U, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || words <= 0 || !update_ok(p, U, R))
+        return "";
+    names = "update=" + update_ctx_kernel_name() + " + " + update_kernel_name(update_up(U), true);
     return names.c_str();
 }
 

@@ -265,6 +265,34 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
 int fill_dot2_sections(const MatLayout& L, int32_t* d_ctx, long long ctx_stride, long long words,
                        int n_stripes, hipStream_t stream);
 
+// per-stripe delta-update contexts (ctx.hip; S x U data row ids, S x R coded
+// slots, d_slots null: slot j = j): update_ctx_words(U, R) words each, the
+// R x UP balanced coefficients c(slot, id) of update_coef.h, the slots and the
+// ids as dwords.  d_tab: the systematic plan's tables, A(y_j) for j < n_out
+// then 1 / A'(x_i) for i < k (null for a non-systematic plan).  Ids not below
+// k or repeated and slots not below n_out or repeated raise kErrBadIds and
+// enter the context as 0
+int launch_update_ctx(int k, int n, int n_out, uint32_t r, int sys, const uint32_t* d_tab,
+                      const uint16_t* d_ids, const uint16_t* d_slots, int U, int UP, int R, int S,
+                      int32_t* d_ctx, long long ctx_stride, uint32_t* err, hipStream_t st);
+// the update itself (update.hip): out[slot] = coded[slot] + sum_u c (new_u -
+// old_u) for the R slots of each context; in / outm: the coded rows' buckets
+// and the updated rows', by slot (counts null: none); by_pos: rows and
+// buckets by the slot's position in the list instead
+int launch_update(const int32_t* d_ctx, long long ctx_stride, int U, int UP, int R, int by_pos,
+                  const uint16_t* d_old, long long old_ss, long long old_rs,
+                  const uint16_t* d_new, long long new_ss, long long new_rs,
+                  const uint16_t* d_coded, long long css, long long crs, const Oor& in,
+                  uint16_t* d_out, long long oss, long long ors, const Oor& outm, long long words,
+                  int n_stripes, uint32_t* d_err, hipStream_t st);
+// its kernel, by row count and by whether every base and stride is a
+// multiple of 16 bytes
+std::string update_kernel_name(int UP, bool vec);
+inline std::string update_ctx_kernel_name()
+{
+    return "update_ctx_kernel";
+}
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <string>
 
 #include "qi_internal.h"
@@ -66,6 +67,15 @@ namespace qi {
 long long ctx_stride(const qi_plan* p, long long words);
 int build_ctx(qi_plan* p, const uint16_t* d_ids, int n_stripes, const Oor* in,
               int slot_base, int by_pos, long long words, void* d_ctx, hipStream_t s);
+// qi_gpu_update, with the compact row addressing of the block API (by_pos:
+// row and bucket of the j-th listed slot at position j, R of each)
+int update_rows(qi_plan* p, const void* d_ctx, int U, int R, int by_pos, const uint16_t* d_old,
+                long long old_ss, long long old_rs, const uint16_t* d_new, long long new_ss,
+                long long new_rs, const uint16_t* d_coded, long long css, long long crs,
+                const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                uint16_t* d_out, long long oss, long long ors, uint32_t* d_out_counts,
+                uint32_t* d_out_entries, int out_cap, long long words, int n_stripes,
+                hipStream_t s);
 }  // namespace qi
 
 struct qi_plan {
@@ -94,6 +104,11 @@ struct qi_plan {
     int32_t* d_ldstw = nullptr;  // per-pass twiddle tables of the LDS engine
     int32_t* d_sysctx = nullptr;
     uint32_t* d_err = nullptr;
+    // systematic delta update: A(y_j), j < m, then 1 / A'(x_i), i < k
+    // (update_coef.h), built and uploaded under upd_mu by the first
+    // qi_gpu_update_ctx
+    uint32_t* d_upd_tab = nullptr;
+    std::mutex upd_mu;
     qi::HostState host;
 };
 
