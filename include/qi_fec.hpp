@@ -102,6 +102,22 @@ struct VerifyResult {
     long long value_mismatch, mark_mismatch, first;
 };
 
+// What RsFnt::locate_blocks_vertical reports: per fragment id the number of
+// columns in which that fragment alone was wrong (-1 for a fragment that is
+// missing or was not listed), the number of bad columns that could not be
+// attributed, and per located column the fragment and the symbol (0 .. 65536)
+// it should hold there
+struct LocateFix {
+    uint32_t column;
+    int fragment;
+    uint32_t symbol;
+};
+struct LocateResult {
+    std::vector<long long> located;
+    long long unlocated = 0;
+    std::vector<LocateFix> fixes;
+};
+
 class RsFnt {
   public:
     // throws std::invalid_argument (bad parameters / word_size != 2) or
@@ -195,6 +211,33 @@ class RsFnt {
                                 std::vector<Properties>& parities_props,
                                 std::vector<int>& missing_idxs,
                                 std::vector<VerifyResult>& result, size_t block_size_bytes);
+
+    // Fragment locate (scrubbing, after a verify flagged the stripe): which
+    // fragment is wrong in which column, and what it should hold there
+    // (qi_gpu_locate).  The first min(present, n_data + 8) present fragments
+    // are listed, chosen as decode_blocks_vertical chooses them; R = listed -
+    // n_data syndromes tell a single bad fragment of a column and its
+    // correction.  With R >= 3 a column with 2 .. R - 1 bad fragments is
+    // counted as unlocated, never attributed; with R = 2 (exactly n_data + 2
+    // present) two bad fragments of a column may be attributed to a third.
+    // Returns 0 with fewer than n_data + 2 fragments present (nothing to
+    // locate with), 1 when the result was filled, and with `correct`, when
+    // there are fixes and no column is unlocated, 2 after the fixes were
+    // written into the caller's buffers and parities_props (a mark inserted
+    // where the symbol becomes 65536, removed where it stops being one; lists
+    // ascending).  A fix list longer than the first attempt's capacity is run
+    // again with the exact one.  Throws std::invalid_argument where
+    // locate_supported() is false, std::length_error (nothing patched) when a
+    // patched mark list would grow beyond max_marks.
+    int locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                               std::vector<uint8_t*>& parities_bufs,
+                               std::vector<Properties>& parities_props,
+                               std::vector<int>& missing_idxs, LocateResult& result,
+                               bool correct, size_t block_size_bytes,
+                               size_t max_marks = static_cast<size_t>(-1));
+    // n_data <= 256, at least 2 parities, and a block within the single-chunk
+    // staging of repair_supported
+    bool locate_supported(size_t block_size_bytes) const;
 
     void encode_streams_vertical(
         const std::vector<std::istream*>& input_data_bufs,

@@ -275,9 +275,8 @@ const char* qi_gpu_repair_kernels(const qi_plan* plan, int n_targets, long long 
  *   d_first:          the smallest column with either kind, or 0xFFFFFFFF.
  * It initialises all three itself.  A corrupt *basis* fragment shows up as a
  * mismatch in every check row at that column (each recomputed symbol depends
- * on every basis symbol of its column); telling which fragment of a stripe
- * is the corrupt one is the caller's business (e.g. by checking again with
- * another basis).
+ * on every basis symbol of its column); which fragment of a stripe is the
+ * corrupt one, and what it should hold, is qi_gpu_locate's answer (below).
  *
  * d_work: qi_gpu_verify_work_bytes bytes of scratch for the recomputed rows'
  * 65536 positions, work_cap per (stripe, check) -- about words / 65537 are
@@ -375,6 +374,75 @@ int qi_gpu_update(qi_plan* plan, const void* d_ctx, int n_rows, int n_slots,
  * counts out of range.  Per calling thread, valid until its next call. */
 const char* qi_gpu_update_kernels(const qi_plan* plan, int n_rows, int n_slots, long long words);
 
+/* ---- Fragment locate: qi_gpu_verify says that the fragments of a stripe
+ * disagree; this call says which one is wrong and what it should hold, in one
+ * pass over the rows and without writing one.  Fragment f of a column is
+ * P(r^f), deg P < k, in both code types.  List N = k + n_checks distinct
+ * present fragments f_0 .. f_(N-1) of a stripe (ids in the decode's id space,
+ * as for qi_gpu_repair), let x_i = r^(f_i) and w_i = prod_{l != i} (x_i - x_l).
+ * For the received column y (y_i the restored symbol: 65536 where the column
+ * is in the row's OOR bucket, the stored u16 otherwise) the syndromes are
+ *   S_j = sum_i y_i x_i^j / w_i   (mod 65537),  j < n_checks = R,
+ * all 0 for a codeword.  One fragment p off by e != 0 gives S_j = (e / w_p)
+ * x_p^j, and a column is
+ *   clean      every S_j = 0;
+ *   located    at position p of the list: S_0 != 0, S_1 / S_0 = x_p, S_j = x_p
+ *              S_(j-1) for 2 <= j < R, and the corrected symbol v = y_p - S_0
+ *              w_p can be stored: v in [0, 65536], and v != 65536 when p is a
+ *              systematic data row (data rows carry no marks);
+ *   unlocated  anything else.
+ * The code over the listed points has minimum distance R + 1: a column with
+ * 2 .. R - 1 bad fragments is always unlocated, never attributed to a wrong
+ * fragment.  R = 2 has no guard equation: there a column with two bad
+ * fragments MAY be attributed to a third one, with a wrong correction.  Use
+ * R >= 3 where more than one fragment of a column can be bad.
+ *
+ * Supported for k <= 256 (as qi_gpu_verify) and 2 <= n_checks <= min(
+ * QI_LOCATE_MAX_CHECKS, m): a larger k returns QI_ERR_UNSUPPORTED (the bytes
+ * call 0, the kernels call ""), an n_checks out of range -1 (0, ""), and
+ * nothing is launched.
+ *
+ * Rows and buckets are addressed by fragment id exactly as qi_gpu_decode
+ * addresses received rows (d_data for f < k of a systematic plan, d_coded by
+ * slot otherwise; d_data may be NULL for a non-systematic plan), with any
+ * positive strides and a unit inner stride at any alignment (rows and strides
+ * that are all multiples of 16 bytes move as 16-byte pieces per lane).
+ * d_stripes = NULL: list position s is stripe s.  Otherwise list position s
+ * takes the rows and buckets of stripe d_stripes[s], so that only the stripes
+ * a verify flagged need be listed; the context, the ids and all four outputs
+ * are indexed by list position.
+ *
+ * Outputs, all initialised by the call: d_located[s * N + i] counts the
+ * columns attributed to listed fragment i, d_unlocated[s] the unlocated
+ * columns.  Each located column appends {column, position i, corrected
+ * symbol v in [0, 65536]} to the stripe's fix list d_fixes[s][fix_cap][3], in
+ * no particular order; d_fix_counts[s] goes on past fix_cap and entries past
+ * it are dropped (the OOR bucket protocol).  fix_cap = 0: counts only (d_fixes
+ * may be NULL).  No row and no bucket is written.
+ *
+ * Ids repeated or not below k + m raise bit 2 of qi_gpu_take_error when the
+ * context is built; the result of such a stripe is unspecified, but the call
+ * stays inside the caller's buffers.  A bucket over oor_cap raises bit 1.
+ * NULL d_oor_counts: no marks.  A bucket with count <= oor_cap is restored in
+ * full however dense.  The context holds, per stripe, the ids, x_i, w_i and
+ * the R x N coefficients (it does not depend on the width). */
+#define QI_LOCATE_MAX_CHECKS 8
+size_t qi_gpu_locate_ctx_bytes(const qi_plan* plan, int n_checks, int n_stripes);
+int qi_gpu_locate_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][k+R]*/, int n_checks,
+                      int n_stripes, void* d_ctx, void* stream);
+int qi_gpu_locate(qi_plan* plan, const void* d_ctx, int n_checks,
+                  const uint32_t* d_stripes /*[S] or NULL*/,
+                  const uint16_t* d_data, long long dss, long long drs,
+                  const uint16_t* d_coded, long long css, long long crs,
+                  const uint32_t* d_oor_counts, const uint32_t* d_oor_entries, int oor_cap,
+                  uint32_t* d_located /*[S][k+R]*/, uint32_t* d_unlocated /*[S]*/,
+                  uint32_t* d_fix_counts /*[S]*/, uint32_t* d_fixes /*[S][fix_cap][3]*/,
+                  int fix_cap, long long words, int n_stripes, void* stream);
+/* Names of the kernels a locate launches (rows and strides at multiples of
+ * 16 bytes), as "locate=<context kernel> + <kernel>"; "" when unsupported.
+ * Per calling thread, valid until its next call. */
+const char* qi_gpu_locate_kernels(const qi_plan* plan, int n_checks, long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -426,6 +494,28 @@ int qi_fec_verify_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
                          const uint32_t* oor, const uint32_t* oor_count,
                          uint32_t oor_cap, const int* missing, long long* result,
                          size_t block_bytes);
+
+/* Fragment locate over the present fragments (RsFnt::locate_blocks_vertical,
+ * include/qi_fec.hpp): the first min(present, k + 8) present fragments are
+ * listed, as qi_fec_decode_blocks chooses them, and each bad column is
+ * attributed to the one listed fragment that is wrong there.  result: k + m + 1
+ * values, per fragment id the number of columns located in it (-1 for a
+ * fragment that is missing or not listed), then the number of bad columns
+ * that could not be attributed.  With exactly k + 2 present (two syndromes)
+ * two bad fragments of a column may be attributed to a third; from k + 3 on
+ * such a column is counted as unlocated.
+ * correct != 0: when there are located columns and none is unlocated, the
+ * corrected symbols are written into the caller's buffers and the ascending
+ * mark lists (oor / oor_count, oor_cap entries per coded fragment) follow: a
+ * mark is inserted where the symbol becomes 65536 and removed where it stops
+ * being one.  If a list would grow beyond oor_cap (oor_count NULL: beyond 0)
+ * nothing is patched and -1 returned.
+ * Returns 1 located (result filled), 2 located and patched, 0 fewer than k + 2
+ * fragments present, -1 error, -2 shape not supported (k > 256, m < 2, or a
+ * block wider than the single-chunk staging). */
+int qi_fec_locate_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                         uint32_t* oor_count, uint32_t oor_cap, const int* missing,
+                         long long* result, int correct, size_t block_bytes);
 
 /* Delta update of the held coded fragments (RsFnt::update_blocks_vertical,
  * include/qi_fec.hpp): data rows ids[0 .. n_rows) go from old_rows[u] to

@@ -69,6 +69,11 @@ def _declare(lib):
         "qi_gpu_update": (I, [V, V, I, I, V, LL, LL, V, LL, LL, V, LL, LL, V, V, I,
                               V, LL, LL, V, V, I, LL, I, V]),
         "qi_gpu_update_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_locate_ctx_bytes": (SZ, [V, I, I]),
+        "qi_gpu_locate_ctx": (I, [V, V, I, I, V, V]),
+        "qi_gpu_locate": (I, [V, V, I, V, V, LL, LL, V, LL, LL, V, V, I, V, V, V, V, I,
+                              LL, I, V]),
+        "qi_gpu_locate_kernels": (C.c_char_p, [V, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -80,6 +85,7 @@ def _declare(lib):
         "qi_fec_repair_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, c_u8pp, V,
                                      V, U32, SZ]),
         "qi_fec_verify_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
+        "qi_fec_locate_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, SZ]),
         "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
@@ -527,6 +533,98 @@ class Plan:
             raise RuntimeError(f"qi_gpu_update failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    LOCATE_MAX_CHECKS = 8  # QI_LOCATE_MAX_CHECKS
+
+    def locate_kernels(self, n_checks, words):
+        """'locate=<context kernel> + <kernel>' a locate with n_checks
+        syndromes launches (qi_gpu_locate_kernels); '' when unsupported."""
+        return lib().qi_gpu_locate_kernels(self.h, n_checks, words).decode()
+
+    def locate_ctx_bytes(self, n_checks, n_stripes):
+        """0 when k > 256 or n_checks is outside 2 .. min(8, m)."""
+        return lib().qi_gpu_locate_ctx_bytes(self.h, n_checks, n_stripes)
+
+    def locate_ctx(self, ids, ctx, stream=None):
+        """ids: int16 tensor [S, k + R], the listed present fragments of each
+        list position (decode id space); R = n_checks follows from the
+        shape."""
+        import torch
+        if ids.dim() != 2:
+            raise ValueError("ids: expected [S, k + R]")
+        S, N = ids.shape
+        R = N - self.k
+        need = self.locate_ctx_bytes(R, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"locate with {R} checks is not supported on this "
+                             f"plan (k <= 256, 2 <= R <= min(8, m))")
+        _flat(ids, "ids", S * N, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        rc = lib().qi_gpu_locate_ctx(self.h, ids.data_ptr(), R, S, ctx.data_ptr(),
+                                     self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_locate_ctx failed: {rc}")
+
+    def locate(self, ctx, n_checks, coded, located, unlocated, fix_counts,
+               fixes=None, fix_cap=0, data=None, counts=None, entries=None,
+               cap=0, stripes=None, stream=None, check=True):
+        """Fragment locate (qi_gpu_locate).  ctx: built by locate_ctx; coded:
+        [S_all, n_out, P] (fragment slot rows, with their OOR buckets counts /
+        entries), data: [S_all, k, P] for systematic codes.  stripes: int32
+        tensor of the stripes to look at (list position -> stripe), None for
+        all S_all in order.  Outputs by list position, int32, initialised by
+        the call: located [S, k + R], unlocated [S], fix_counts [S], fixes
+        [S, fix_cap, 3] of {column, position, corrected symbol}.  Returns the
+        sticky error flags when check."""
+        import torch
+        _rows(coded, "coded", self.n_outputs)
+        S_all, _, P = coded.shape
+        if data is not None:
+            _rows(data, "data", self.k, S_all)
+            if data.shape[2] != P:
+                raise ValueError("data and coded differ in width")
+        elif self.sys:
+            raise ValueError("a systematic plan needs the data rows")
+        if stripes is not None:
+            _flat(stripes, "stripes", 0, (torch.int32,))
+            S = stripes.numel()
+            # every listed stripe must exist (checked here unless check=False:
+            # reading the values back waits for the device)
+            if check and S > 0 and not (0 <= int(stripes.min()) and
+                                        int(stripes.max()) < S_all):
+                raise ValueError(f"stripes: values must lie in [0, {S_all})")
+        else:
+            S = S_all
+        need = self.locate_ctx_bytes(n_checks, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"locate with {n_checks} checks is not supported on "
+                             f"this plan (k <= 256, 2 <= R <= min(8, m))")
+        N = self.k + n_checks
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S_all, self.n_outputs)
+        for t, name, n in ((located, "located", S * N), (unlocated, "unlocated", S),
+                           (fix_counts, "fix_counts", S)):
+            if t is None:
+                raise ValueError(f"{name}: required")
+            _flat(t, name, n, (torch.int32,))
+        if fix_cap < 0 or (fix_cap > 0 and fixes is None):
+            raise ValueError("fix_cap > 0 needs fixes")
+        _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        rc = lib().qi_gpu_locate(
+            self.h, ctx.data_ptr(), n_checks,
+            stripes.data_ptr() if stripes is not None else None,
+            data.data_ptr() if data is not None else None,
+            data.stride(0) if data is not None else 0,
+            data.stride(1) if data is not None else 0,
+            coded.data_ptr(), coded.stride(0), coded.stride(1),
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            located.data_ptr(), unlocated.data_ptr(), fix_counts.data_ptr(),
+            fixes.data_ptr() if fixes is not None else None, int(fix_cap),
+            P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_locate failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -604,6 +702,41 @@ class Fec:
         if rc < 0:
             raise RuntimeError(f"qi_fec_verify_blocks failed: {rc}")
         return res if rc == 1 else None
+
+    def locate_blocks(self, data, parities, oor, counts, missing, correct=False):
+        """Which fragment is wrong in which columns (qi_fec_locate_blocks):
+        the first min(present, k + 8) present fragments are listed.  Arguments
+        as verify_blocks; oor (n_outputs, cap) and counts (n_outputs,) must be
+        contiguous uint32 arrays (counts None: no marks).  Returns an int64
+        array of k + m + 1 values: per fragment id the number of columns
+        located in it (-1: missing or not listed), then the number of bad
+        columns that could not be attributed; None when fewer than k + 2
+        fragments are present.  correct=True returns (that array, patched):
+        when there are located columns and none is unlocated, the rows (uint8
+        numpy arrays, written in place), oor and counts are corrected and
+        patched is True.  Raises ValueError for an unsupported shape (k > 256,
+        m < 2, a block wider than one staging chunk)."""
+        import numpy as np
+        rows = [r for r in list(data or []) + list(parities) if r is not None]
+        B = len(rows[0])
+        miss = np.ascontiguousarray(missing, np.int32)
+        for a in (oor, counts):
+            if a is not None and (a.dtype != np.uint32 or not a.flags.c_contiguous):
+                raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        res = np.full(self.k + self.m + 1, -1, np.int64)
+        rc = lib().qi_fec_locate_blocks(
+            self.h, ptr_array(list(data)) if data is not None else None,
+            ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p) if counts is not None else None,
+            oor.shape[1], miss.ctypes.data_as(C.c_void_p),
+            res.ctypes.data_as(C.c_void_p), int(bool(correct)), B)
+        if rc == -2:
+            raise ValueError("locate_blocks: shape not supported")
+        if rc < 0:
+            raise RuntimeError(f"qi_fec_locate_blocks failed: {rc}")
+        if rc == 0:
+            return None
+        return (res, rc == 2) if correct else res
 
     def update_blocks(self, ids, old_rows, new_rows, parities, oor, counts):
         """Delta update (qi_fec_update_blocks): data rows `ids` go from

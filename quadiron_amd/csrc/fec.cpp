@@ -644,6 +644,95 @@ bool RsFnt::verify_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     return true;
 }
 
+// ---- fragment locate (single chunk; qi_gpu_locate_ctx, then qi_gpu_locate
+// over the staged rows) ----
+bool RsFnt::locate_supported(size_t block_size_bytes) const
+{
+    return code_len - n_data >= 2 && repair_supported(1, block_size_bytes);
+}
+
+int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                  std::vector<uint8_t*>& parities_bufs,
+                                  std::vector<Properties>& parities_props,
+                                  std::vector<int>& missing_idxs, LocateResult& result,
+                                  bool correct, size_t block_size_bytes, size_t max_marks)
+{
+    // validate
+    const stage::FragMap map = frag_map(*this);
+    if (!locate_supported(block_size_bytes))
+        throw std::invalid_argument("RsFnt::locate_blocks_vertical: unsupported shape");
+    const std::vector<int> present = map.present(missing_idxs);
+    result.located.assign(code_len, -1);
+    result.unlocated = 0;
+    result.fixes.clear();
+    const std::vector<int> ids = map.select_upto(present, n_data + QI_LOCATE_MAX_CHECKS);
+    if (ids.size() < n_data + 2)
+        return 0;
+    const size_t N = ids.size();
+    const int R = static_cast<int>(N - n_data);
+    for (auto& p : parities_props)
+        p.sort();
+    const size_t words = block_size_bytes / word_size;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    const size_t ctx_bytes = qi_gpu_locate_ctx_bytes(pl, R, 1);
+    if (ctx_bytes == 0)
+        throw std::invalid_argument("RsFnt::locate_blocks_vertical: unsupported shape");
+    // stage: the listed rows, their buckets, then located[N], unlocated, the
+    // fix count
+    const Staged st = stage_fragments(pl, map, ids, data_bufs, parities_bufs, parities_props,
+                                      words, (N + 2) * 4, N, ctx_bytes);
+    const long long P = static_cast<long long>(st.P);
+    const int cap = static_cast<int>(st.pm.cap);
+    uint32_t* dres = st.dtail;
+    const std::vector<uint16_t> hids(ids.begin(), ids.end());
+    h2d(h.ids.p, hids.data(), N * 2, s);
+    check_rc(qi_gpu_locate_ctx(pl, static_cast<uint16_t*>(h.ids.p), R, 1, h.ctx.p, s),
+             "locate context");
+    // launch: a fix list longer than the capacity is run again with the exact
+    // one (no error drain between the attempts: an overflowing fix list
+    // raises none)
+    std::vector<uint32_t> res(N + 2);
+    const size_t fcap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, c * 3 * 4);
+            check_rc(qi_gpu_locate(pl, h.ctx.p, R, nullptr, st.din, 0, P, st.dcoded, 0, P,
+                                   st.dcnt, st.dent, cap, dres, dres + N, dres + N + 1,
+                                   static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                   static_cast<long long>(words), 1, s),
+                     "locate");
+        },
+        [&] {
+            d2h(res.data(), dres, (N + 2) * 4, s);
+            check(hipStreamSynchronize(s), "sync");
+            return static_cast<size_t>(res[N + 1]);
+        },
+        [] {});
+    // collect
+    const size_t nfix = res[N + 1];
+    if (nfix > fcap)
+        throw std::runtime_error("RsFnt: locate fix list overflowed twice");
+    std::vector<uint32_t> fx(nfix * 3);
+    if (nfix)
+        d2h(fx.data(), h.entries.p, nfix * 3 * 4, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: locate failed (bad ids or OOR bucket capacity)");
+    for (size_t i = 0; i < N; i++)
+        result.located[ids[i]] = static_cast<long long>(res[i]);
+    result.unlocated = static_cast<long long>(res[N]);
+    for (size_t e = 0; e < nfix; e++)
+        result.fixes.push_back(LocateFix{fx[3 * e], ids[fx[3 * e + 1]], fx[3 * e + 2]});
+    if (!correct || result.fixes.empty() || result.unlocated != 0)
+        return 1;
+    if (!stage::apply_fixes(map, result.fixes, data_bufs, parities_bufs, parities_props,
+                            max_marks))
+        throw std::length_error("RsFnt::locate_blocks_vertical: mark list capacity");
+    return 2;
+}
+
 // ---- delta update (single chunk; qi_gpu_update_ctx, then the update in
 // place on the staged rows) ----
 bool RsFnt::update_supported(size_t n_rows, size_t n_held, size_t block_size_bytes) const
@@ -1614,6 +1703,33 @@ int qi_fec_verify_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const ui
             result[3 * i + 2] = res[i].first;
         }
         return ok ? 1 : 0;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_locate_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                         uint32_t* oor_count, uint32_t cap, const int* missing,
+                         long long* result, int correct, size_t block_bytes)
+{
+    try {
+        if (!h || !parities || !missing || !result)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.locate_supported(block_bytes))
+            return -2;
+        // (oor_count null: no marks, and none can be written)
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
+        qi::fec::LocateResult res;
+        const int rc = f.locate_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res,
+                                                correct != 0, block_bytes,
+                                                oor_count ? cap : 0);
+        for (unsigned i = 0; i < f.code_len; i++)
+            result[i] = res.located[i];
+        result[f.code_len] = res.unlocated;
+        if (rc == 2 && oor_count)
+            stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
+        return rc;
     } catch (...) {
         return -1;
     }

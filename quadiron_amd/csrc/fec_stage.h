@@ -87,6 +87,19 @@ struct FragMap {
                 ids.push_back(static_cast<int>(coded_id(i)));
         return ids.size() == k;
     }
+    // the first min(present, limit) present fragments in the same order (data
+    // before parities): what a locate lists
+    std::vector<int> select_upto(const std::vector<int>& present, size_t limit) const
+    {
+        std::vector<int> ids;
+        for (unsigned i = 0; i < data_rows() && ids.size() < limit; i++)
+            if (present[i])
+                ids.push_back(static_cast<int>(i));
+        for (unsigned i = 0; i < n_outputs && ids.size() < limit; i++)
+            if (present[coded_id(i)])
+                ids.push_back(static_cast<int>(coded_id(i)));
+        return ids;
+    }
 };
 
 // ---- mark packing -------------------------------------------------------
@@ -183,6 +196,60 @@ inline void add_sorted(Properties& p, uint32_t* bucket, uint32_t count, size_t o
     std::sort(bucket, bucket + count);
     for (uint32_t e = 0; e < count; e++)
         p.add(offset + bucket[e], OOR_MARK);
+}
+
+// ---- locate fixes -> the caller's buffers -----------------------------------
+// Writes the corrected symbols into the rows (u16 words; 65536 is stored as 0)
+// and keeps the coded fragments' ascending mark lists in step: a mark is
+// inserted where the symbol becomes 65536 and removed where it stops being
+// one.  Nothing is touched, and false returned, when a list would grow past
+// max_marks or a data row would need a mark.
+inline bool apply_fixes(const FragMap& map, const std::vector<LocateFix>& fixes,
+                        const std::vector<uint8_t*>& data_bufs,
+                        const std::vector<uint8_t*>& coded_bufs, std::vector<Properties>& props,
+                        size_t max_marks)
+{
+    std::vector<std::vector<size_t>> marks(map.n_outputs);
+    std::vector<char> touched(map.n_outputs, 0);
+    for (auto const& f : fixes) {
+        const auto fs = map.slot(static_cast<unsigned>(f.fragment));
+        if (fs.is_data) {
+            if (f.symbol > 65535u)
+                return false;
+            continue;
+        }
+        auto& mk = marks[fs.slot];
+        if (!touched[fs.slot]) {
+            touched[fs.slot] = 1;
+            for (auto const& it : props[fs.slot].get_map())
+                mk.push_back(it.first);
+            std::sort(mk.begin(), mk.end());
+        }
+        const auto at = std::lower_bound(mk.begin(), mk.end(), static_cast<size_t>(f.column));
+        const bool has = at != mk.end() && *at == f.column;
+        if (f.symbol == 65536u && !has)
+            mk.insert(at, f.column);
+        else if (f.symbol != 65536u && has)
+            mk.erase(at);
+    }
+    for (unsigned j = 0; j < map.n_outputs; j++)
+        if (touched[j] && marks[j].size() > max_marks &&
+            marks[j].size() > props[j].get_map().size())
+            return false;
+    for (auto const& f : fixes) {
+        uint8_t* row = map.pick(static_cast<unsigned>(f.fragment), data_bufs, coded_bufs);
+        const uint16_t w = static_cast<uint16_t>(f.symbol & 0xffffu);
+        row[2 * static_cast<size_t>(f.column)] = static_cast<uint8_t>(w & 0xff);
+        row[2 * static_cast<size_t>(f.column) + 1] = static_cast<uint8_t>(w >> 8);
+    }
+    for (unsigned j = 0; j < map.n_outputs; j++) {
+        if (!touched[j])
+            continue;
+        props[j].clear();
+        for (size_t c : marks[j])
+            props[j].add(c, OOR_MARK);
+    }
+    return true;
 }
 
 // ---- flat C arrays <-> Properties ---------------------------------------

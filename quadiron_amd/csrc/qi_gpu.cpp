@@ -9,6 +9,7 @@
 
 #include "../../include/qi_gpu.h"
 #include "gf65537.h"
+#include "locate_math.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
 #include "update_coef.h"
@@ -505,6 +506,75 @@ const char* qi_gpu_update_kernels(const qi_plan* p, int U, int R, long long word
     if (!p || words <= 0 || !update_ok(p, U, R))
         return "";
     names = "update=" + update_ctx_kernel_name() + " + " + update_kernel_name(update_up(U), true);
+    return names.c_str();
+}
+
+// ---- fragment locate (k <= 256): locate_ctx_kernel leaves the points, the
+// dual weights and the syndrome coefficients of the k + R listed fragments
+// per stripe, locate_kernel streams their rows once and classifies the
+// columns whose R syndromes are not all 0 (locate.hip, locate_math.h) ----
+static bool locate_ok(const qi_plan* p, int R)
+{
+    return R >= 2 && R <= std::min(QI_LOCATE_MAX_CHECKS, p->code_len - p->k);
+}
+
+size_t qi_gpu_locate_ctx_bytes(const qi_plan* p, int R, int n_stripes)
+{
+    if (!p || p->k > kLocMaxK || n_stripes < 0 || !locate_ok(p, R))
+        return 0;
+    return static_cast<size_t>(locate_ctx_words(p->k, R)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_locate_ctx(qi_plan* p, const uint16_t* d_ids, int R, int n_stripes, void* d_ctx,
+                      void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0)
+        return -1;
+    if (p->k > kLocMaxK)
+        return QI_ERR_UNSUPPORTED;
+    if (!locate_ok(p, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids)
+        return -1;
+    return launch_locate_ctx(p->k, R, p->code_len, p->r, d_ids, n_stripes,
+                             static_cast<int32_t*>(d_ctx), p->d_err, st(stream));
+}
+
+int qi_gpu_locate(qi_plan* p, const void* d_ctx, int R, const uint32_t* d_stripes,
+                  const uint16_t* d_data, long long dss, long long drs, const uint16_t* d_coded,
+                  long long css, long long crs, const uint32_t* d_counts,
+                  const uint32_t* d_entries, int cap, uint32_t* d_located, uint32_t* d_unlocated,
+                  uint32_t* d_fix_counts, uint32_t* d_fixes, int fix_cap, long long words,
+                  int n_stripes, void* stream)
+{
+    if (!p || !d_ctx || !d_coded || !d_located || !d_unlocated || !d_fix_counts ||
+        n_stripes < 0 || words < 0 || fix_cap < 0 || (fix_cap > 0 && !d_fixes) ||
+        (d_counts && cap > 0 && !d_entries))
+        return -1;
+    if (p->k > kLocMaxK)
+        return QI_ERR_UNSUPPORTED;
+    if (!locate_ok(p, R) || (p->sys && !d_data))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    const Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs,
+                 cap};
+    return launch_locate(static_cast<const int32_t*>(d_ctx), p->k, R, p->sys ? p->k : 0,
+                         d_stripes, d_data, dss, drs, d_coded, css, crs, in, d_located,
+                         d_unlocated, d_fix_counts, d_fixes, fix_cap, words, n_stripes, p->d_err,
+                         st(stream));
+}
+
+const char* qi_gpu_locate_kernels(const qi_plan* p, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || p->k > kLocMaxK || words <= 0 || !locate_ok(p, R))
+        return "";
+    names = "locate=" + locate_ctx_kernel_name(locate_rp(R)) + " + " +
+            locate_kernel_name(locate_rp(R), true);
     return names.c_str();
 }
 

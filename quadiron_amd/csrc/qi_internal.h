@@ -293,6 +293,25 @@ inline std::string update_ctx_kernel_name()
     return "update_ctx_kernel";
 }
 
+// per-stripe locate contexts (locate.hip; S x (k + R) listed fragment ids):
+// locate_ctx_words(k, R) words each (locate_math.h).  Ids not below code_len
+// or repeated raise kErrBadIds; an id out of range enters the context as 0
+int launch_locate_ctx(int k, int R, int code_len, uint32_t r, const uint16_t* d_ids, int S,
+                      int32_t* d_ctx, uint32_t* err, hipStream_t st);
+// the locate itself: fragments below `split` are rows of d_data, the others
+// rows of d_coded by slot id - split with the buckets `in` (counts null: no
+// marks); d_stripes: list position -> stripe of the rows and buckets (null:
+// the identity).  Clears the four outputs first
+int launch_locate(const int32_t* d_ctx, int k, int R, int split, const uint32_t* d_stripes,
+                  const uint16_t* d_data, long long dss, long long drs, const uint16_t* d_coded,
+                  long long css, long long crs, const Oor& in, uint32_t* d_located,
+                  uint32_t* d_unlocated, uint32_t* d_fix_counts, uint32_t* d_fixes, int fix_cap,
+                  long long words, int n_stripes, uint32_t* d_err, hipStream_t st);
+// their kernels, by the syndrome count rounded up (locate_rp) and by whether
+// every base and stride is a multiple of 16 bytes
+std::string locate_ctx_kernel_name(int RP);
+std::string locate_kernel_name(int RP, bool vec);
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.

@@ -1,0 +1,35 @@
+"""CPU: the compiler's resource report of the fragment locate's kernels
+(build/obj/locate.res, written by quadiron_amd/csrc/Makefile): every form of
+locate_kernel and locate_ctx_kernel is there, none uses scratch memory or
+spills a VGPR."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RES = os.path.join(ROOT, "build", "obj", "locate.res")
+
+
+def _report(path):
+    out, cur = {}, None
+    for line in open(path):
+        m = re.search(r"remark: (?:\S+:\d+:\d+: )?Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+            out[cur] = {}
+            continue
+        m = re.search(r"remark: (?:\S+:\d+:\d+: )?\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and cur:
+            out[cur][m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def test_locate_kernels_use_no_scratch():
+    ks = _report(RES)
+    # locate_kernel<RP, VEC> and locate_ctx_kernel<RP>, RP in 2, 4, 8
+    want = {f"locate_kernelILi{rp}ELb{v}E" for rp in (2, 4, 8) for v in (0, 1)}
+    want |= {f"locate_ctx_kernelILi{rp}E" for rp in (2, 4, 8)}
+    assert {w for w in want if any(w in k for k in ks)} == want, sorted(ks)
+    assert len(ks) == len(want), sorted(ks)
+    for k, v in ks.items():
+        assert v["ScratchSize"] == 0, (k, v)
+        assert v["VGPRs Spill"] == 0, (k, v)
