@@ -116,6 +116,9 @@ struct LocateResult {
     std::vector<long long> located;
     long long unlocated = 0;
     std::vector<LocateFix> fixes;
+    // locate_multi_blocks_vertical only: weights[nu - 1] is the number of
+    // columns located with nu fragments, nu = 1 .. max_errors
+    std::vector<long long> weights;
 };
 
 class RsFnt {
@@ -239,6 +242,22 @@ class RsFnt {
     // staging of repair_supported
     bool locate_supported(size_t block_size_bytes) const;
 
+    // The same with up to max_errors bad fragments per column
+    // (qi_gpu_locate_multi): a column is located when 1 .. max_errors listed
+    // fragments explain all R syndromes, and then counts in each of them; its
+    // fixes are adjacent in result.fixes, result.weights[nu - 1] counts the
+    // columns located with nu fragments.  A column with more than max_errors
+    // and at most R - max_errors bad fragments is always unlocated.  Listing,
+    // return values, `correct`, max_marks and the exceptions are
+    // locate_blocks_vertical's; 0 is also returned when R < 2 max_errors.
+    // Throws std::invalid_argument for max_errors outside 1 .. 4.
+    int locate_multi_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                     std::vector<uint8_t*>& parities_bufs,
+                                     std::vector<Properties>& parities_props,
+                                     std::vector<int>& missing_idxs, LocateResult& result,
+                                     int max_errors, bool correct, size_t block_size_bytes,
+                                     size_t max_marks = static_cast<size_t>(-1));
+
     void encode_streams_vertical(
         const std::vector<std::istream*>& input_data_bufs,
         std::vector<std::ostream*>& output_parities_bufs,
@@ -286,6 +305,11 @@ class RsFnt {
     qi_plan* plan() const { return plan_; }
 
   private:
+    // both locates: max_errors 0 is qi_gpu_locate, 1 .. 4 qi_gpu_locate_multi
+    int locate_run(std::vector<uint8_t*>& data_bufs, std::vector<uint8_t*>& parities_bufs,
+                   std::vector<Properties>& parities_props, std::vector<int>& missing_idxs,
+                   LocateResult& result, int max_errors, bool correct, size_t block_size_bytes,
+                   size_t max_marks);
     // device encode of `words` columns on plan pl; outputs[i] NULL = not
     // wanted (pl's n_outputs of them)
     void encode_columns(qi_plan* pl, const uint8_t* const* data, uint8_t* const* outputs,

@@ -443,6 +443,59 @@ int qi_gpu_locate(qi_plan* plan, const void* d_ctx, int n_checks,
  * Per calling thread, valid until its next call. */
 const char* qi_gpu_locate_kernels(const qi_plan* plan, int n_checks, long long words);
 
+/* ---- Multi-fragment locate: qi_gpu_locate solves with two of its R
+ * syndromes and keeps the others as guards, so a column with two bad
+ * fragments is always unlocated.  This call decodes up to max_errors = t bad
+ * fragments per column, 1 <= t <= floor(R / 2) <= QI_LOCATE_MAX_ERRORS, from
+ * the same context (qi_gpu_locate_ctx) and the same single pass over the rows.
+ * With the notation above a column is
+ *   clean      every S_j = 0;
+ *   located    with nu fragments, 1 <= nu <= t: there are distinct list
+ *              positions p_1 .. p_nu and non-zero E_1 .. E_nu with S_j = sum_a
+ *              E_a x_(p_a)^j for ALL j < R, and every corrected symbol v_a =
+ *              y_(p_a) - E_a w_(p_a) can be stored (v_a in [0, 65536], and not
+ *              65536 on a systematic data row).  As 2 nu <= R such a set is
+ *              unique when it exists;
+ *   unlocated  anything else.  One v_a that cannot be stored makes the whole
+ *              column unlocated: no partial fix is emitted.
+ * With b bad listed fragments in a column:
+ *   b <= t          located exactly, each fix is the original symbol;
+ *   t < b <= R - t  always unlocated, never attributed;
+ *   b > R - t       may be miscorrected.
+ * With t = 1 every output equals qi_gpu_locate's on the same input (R = 2
+ * included).  A t below floor(R / 2) buys a wider guard zone.
+ *
+ * Rows, buckets, d_stripes, limits and errors are exactly qi_gpu_locate's:
+ * k > 256 returns QI_ERR_UNSUPPORTED (the kernels call ""); n_checks outside
+ * 2 .. min(QI_LOCATE_MAX_CHECKS, m) or max_errors outside 1 .. n_checks / 2
+ * returns -1 and launches nothing; a bucket over oor_cap raises bit 1; bad
+ * ids are the context's business (bit 2).
+ *
+ * Outputs, all initialised by the call: a located column adds 1 to each of
+ * its nu d_located[s * N + p_a] and 1 to d_weights[s * QI_LOCATE_MAX_ERRORS +
+ * nu - 1], an unlocated one 1 to d_unlocated[s].  A located column reserves
+ * its nu fix entries {column, position, v} with one addition of nu to
+ * d_fix_counts[s], so they are adjacent in d_fixes[s][fix_cap][3]; entries at
+ * or past fix_cap are dropped one by one and the count goes on (the OOR bucket
+ * protocol).  fix_cap = 0: counts only (d_fixes may be NULL).  No row and no
+ * bucket is written. */
+#define QI_LOCATE_MAX_ERRORS 4
+int qi_gpu_locate_multi(qi_plan* plan, const void* d_ctx, int n_checks, int max_errors,
+                        const uint32_t* d_stripes /*[S] or NULL*/,
+                        const uint16_t* d_data, long long dss, long long drs,
+                        const uint16_t* d_coded, long long css, long long crs,
+                        const uint32_t* d_oor_counts, const uint32_t* d_oor_entries,
+                        int oor_cap, uint32_t* d_located /*[S][k+R]*/,
+                        uint32_t* d_unlocated /*[S]*/,
+                        uint32_t* d_weights /*[S][QI_LOCATE_MAX_ERRORS]*/,
+                        uint32_t* d_fix_counts /*[S]*/, uint32_t* d_fixes /*[S][fix_cap][3]*/,
+                        int fix_cap, long long words, int n_stripes, void* stream);
+/* "locate_multi=<context kernel> + <kernel>" (rows and strides at multiples
+ * of 16 bytes); "" when unsupported or max_errors is out of range.  Per
+ * calling thread, valid until its next call. */
+const char* qi_gpu_locate_multi_kernels(const qi_plan* plan, int n_checks, int max_errors,
+                                        long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -516,6 +569,19 @@ int qi_fec_verify_blocks(qi_fec* f, uint8_t** data, uint8_t** parities,
 int qi_fec_locate_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, uint32_t* oor,
                          uint32_t* oor_count, uint32_t oor_cap, const int* missing,
                          long long* result, int correct, size_t block_bytes);
+
+/* The same with up to max_errors bad fragments per column
+ * (RsFnt::locate_multi_blocks_vertical, qi_gpu_locate_multi), 1 <= max_errors
+ * <= QI_LOCATE_MAX_ERRORS (else -1).  Listing as above, R = listed - k; 0 is
+ * also returned when R < 2 max_errors.  result: the k + m + 1 values of
+ * qi_fec_locate_blocks (a located column counts in each of its fragments),
+ * then max_errors values: the columns located with 1 .. max_errors fragments.
+ * `correct` patches all fixes of all columns or, with a column unlocated or a
+ * mark list past oor_cap, nothing.  Return values as qi_fec_locate_blocks. */
+int qi_fec_locate_multi_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                               uint32_t* oor_count, uint32_t oor_cap, const int* missing,
+                               int max_errors, long long* result, int correct,
+                               size_t block_bytes);
 
 /* Delta update of the held coded fragments (RsFnt::update_blocks_vertical,
  * include/qi_fec.hpp): data rows ids[0 .. n_rows) go from old_rows[u] to

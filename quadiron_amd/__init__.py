@@ -74,6 +74,9 @@ def _declare(lib):
         "qi_gpu_locate": (I, [V, V, I, V, V, LL, LL, V, LL, LL, V, V, I, V, V, V, V, I,
                               LL, I, V]),
         "qi_gpu_locate_kernels": (C.c_char_p, [V, I, LL]),
+        "qi_gpu_locate_multi": (I, [V, V, I, I, V, V, LL, LL, V, LL, LL, V, V, I, V, V, V,
+                                    V, V, I, LL, I, V]),
+        "qi_gpu_locate_multi_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -86,6 +89,7 @@ def _declare(lib):
                                      V, U32, SZ]),
         "qi_fec_verify_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
         "qi_fec_locate_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, SZ]),
+        "qi_fec_locate_multi_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, I, V, I, SZ]),
         "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
@@ -625,6 +629,75 @@ class Plan:
             raise RuntimeError(f"qi_gpu_locate failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    LOCATE_MAX_ERRORS = 4  # QI_LOCATE_MAX_ERRORS
+
+    def locate_multi_kernels(self, n_checks, max_errors, words):
+        """'locate_multi=<context kernel> + <kernel>' a multi-fragment locate
+        launches (qi_gpu_locate_multi_kernels); '' when unsupported or
+        max_errors is outside 1 .. n_checks // 2."""
+        return lib().qi_gpu_locate_multi_kernels(self.h, n_checks, max_errors,
+                                                 words).decode()
+
+    def locate_multi(self, ctx, n_checks, max_errors, coded, located, unlocated,
+                     weights, fix_counts, fixes=None, fix_cap=0, data=None,
+                     counts=None, entries=None, cap=0, stripes=None, stream=None,
+                     check=True):
+        """Multi-fragment locate (qi_gpu_locate_multi): up to max_errors bad
+        fragments per column, 1 <= max_errors <= n_checks // 2.  Arguments as
+        locate, and weights: int32 [S, 4], weights[s, nu - 1] the columns of
+        list position s located with nu fragments.  A located column adds 1
+        to each of its fragments' located counters and its nu fix entries are
+        adjacent.  Returns the sticky error flags when check."""
+        import torch
+        _rows(coded, "coded", self.n_outputs)
+        S_all, _, P = coded.shape
+        if data is not None:
+            _rows(data, "data", self.k, S_all)
+            if data.shape[2] != P:
+                raise ValueError("data and coded differ in width")
+        elif self.sys:
+            raise ValueError("a systematic plan needs the data rows")
+        if stripes is not None:
+            _flat(stripes, "stripes", 0, (torch.int32,))
+            S = stripes.numel()
+            if check and S > 0 and not (0 <= int(stripes.min()) and
+                                        int(stripes.max()) < S_all):
+                raise ValueError(f"stripes: values must lie in [0, {S_all})")
+        else:
+            S = S_all
+        need = self.locate_ctx_bytes(n_checks, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"locate with {n_checks} checks is not supported on "
+                             f"this plan (k <= 256, 2 <= R <= min(8, m))")
+        N = self.k + n_checks
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S_all, self.n_outputs)
+        for t, name, n in ((located, "located", S * N), (unlocated, "unlocated", S),
+                           (weights, "weights", S * self.LOCATE_MAX_ERRORS),
+                           (fix_counts, "fix_counts", S)):
+            if t is None:
+                raise ValueError(f"{name}: required")
+            _flat(t, name, n, (torch.int32,))
+        if fix_cap < 0 or (fix_cap > 0 and fixes is None):
+            raise ValueError("fix_cap > 0 needs fixes")
+        _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        rc = lib().qi_gpu_locate_multi(
+            self.h, ctx.data_ptr(), n_checks, int(max_errors),
+            stripes.data_ptr() if stripes is not None else None,
+            data.data_ptr() if data is not None else None,
+            data.stride(0) if data is not None else 0,
+            data.stride(1) if data is not None else 0,
+            coded.data_ptr(), coded.stride(0), coded.stride(1),
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            located.data_ptr(), unlocated.data_ptr(), weights.data_ptr(),
+            fix_counts.data_ptr(),
+            fixes.data_ptr() if fixes is not None else None, int(fix_cap),
+            P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_locate_multi failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -703,7 +776,8 @@ class Fec:
             raise RuntimeError(f"qi_fec_verify_blocks failed: {rc}")
         return res if rc == 1 else None
 
-    def locate_blocks(self, data, parities, oor, counts, missing, correct=False):
+    def locate_blocks(self, data, parities, oor, counts, missing, correct=False,
+                      max_errors=None):
         """Which fragment is wrong in which columns (qi_fec_locate_blocks):
         the first min(present, k + 8) present fragments are listed.  Arguments
         as verify_blocks; oor (n_outputs, cap) and counts (n_outputs,) must be
@@ -715,7 +789,12 @@ class Fec:
         when there are located columns and none is unlocated, the rows (uint8
         numpy arrays, written in place), oor and counts are corrected and
         patched is True.  Raises ValueError for an unsupported shape (k > 256,
-        m < 2, a block wider than one staging chunk)."""
+        m < 2, a block wider than one staging chunk).
+        max_errors=t (1 .. 4) decodes up to t bad fragments per column
+        (qi_fec_locate_multi_blocks): a located column counts in each of its
+        fragments, the array has t more values, the columns located with
+        1 .. t fragments, and None is also returned when fewer than k + 2 t
+        fragments are listed.  None keeps the single-fragment call."""
         import numpy as np
         rows = [r for r in list(data or []) + list(parities) if r is not None]
         B = len(rows[0])
@@ -723,6 +802,24 @@ class Fec:
         for a in (oor, counts):
             if a is not None and (a.dtype != np.uint32 or not a.flags.c_contiguous):
                 raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        if max_errors is not None:
+            t = int(max_errors)
+            if not 1 <= t <= Plan.LOCATE_MAX_ERRORS:
+                raise ValueError("locate_blocks: max_errors must be 1 .. 4")
+            res = np.full(self.k + self.m + 1 + t, -1, np.int64)
+            rc = lib().qi_fec_locate_multi_blocks(
+                self.h, ptr_array(list(data)) if data is not None else None,
+                ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+                counts.ctypes.data_as(C.c_void_p) if counts is not None else None,
+                oor.shape[1], miss.ctypes.data_as(C.c_void_p), t,
+                res.ctypes.data_as(C.c_void_p), int(bool(correct)), B)
+            if rc == -2:
+                raise ValueError("locate_blocks: shape not supported")
+            if rc < 0:
+                raise RuntimeError(f"qi_fec_locate_multi_blocks failed: {rc}")
+            if rc == 0:
+                return None
+            return (res, rc == 2) if correct else res
         res = np.full(self.k + self.m + 1, -1, np.int64)
         rc = lib().qi_fec_locate_blocks(
             self.h, ptr_array(list(data)) if data is not None else None,

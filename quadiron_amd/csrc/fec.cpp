@@ -657,6 +657,30 @@ int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
                                   std::vector<int>& missing_idxs, LocateResult& result,
                                   bool correct, size_t block_size_bytes, size_t max_marks)
 {
+    return locate_run(data_bufs, parities_bufs, parities_props, missing_idxs, result, 0, correct,
+                      block_size_bytes, max_marks);
+}
+
+int RsFnt::locate_multi_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                        std::vector<uint8_t*>& parities_bufs,
+                                        std::vector<Properties>& parities_props,
+                                        std::vector<int>& missing_idxs, LocateResult& result,
+                                        int max_errors, bool correct, size_t block_size_bytes,
+                                        size_t max_marks)
+{
+    if (max_errors < 1 || max_errors > QI_LOCATE_MAX_ERRORS)
+        throw std::invalid_argument("RsFnt::locate_multi_blocks_vertical: max_errors");
+    return locate_run(data_bufs, parities_bufs, parities_props, missing_idxs, result, max_errors,
+                      correct, block_size_bytes, max_marks);
+}
+
+// max_errors = t: 0 runs qi_gpu_locate, 1 .. 4 qi_gpu_locate_multi, whose
+// weights follow the fix count in the tail
+int RsFnt::locate_run(std::vector<uint8_t*>& data_bufs, std::vector<uint8_t*>& parities_bufs,
+                      std::vector<Properties>& parities_props, std::vector<int>& missing_idxs,
+                      LocateResult& result, int t, bool correct, size_t block_size_bytes,
+                      size_t max_marks)
+{
     // validate
     const stage::FragMap map = frag_map(*this);
     if (!locate_supported(block_size_bytes))
@@ -665,11 +689,14 @@ int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     result.located.assign(code_len, -1);
     result.unlocated = 0;
     result.fixes.clear();
+    result.weights.assign(t, 0);
     const std::vector<int> ids = map.select_upto(present, n_data + QI_LOCATE_MAX_CHECKS);
     if (ids.size() < n_data + 2)
         return 0;
     const size_t N = ids.size();
     const int R = static_cast<int>(N - n_data);
+    if (R < 2 * t)
+        return 0;
     for (auto& p : parities_props)
         p.sort();
     const size_t words = block_size_bytes / word_size;
@@ -680,9 +707,10 @@ int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     if (ctx_bytes == 0)
         throw std::invalid_argument("RsFnt::locate_blocks_vertical: unsupported shape");
     // stage: the listed rows, their buckets, then located[N], unlocated, the
-    // fix count
+    // fix count and the weights
+    const size_t T = N + 2 + QI_LOCATE_MAX_ERRORS;
     const Staged st = stage_fragments(pl, map, ids, data_bufs, parities_bufs, parities_props,
-                                      words, (N + 2) * 4, N, ctx_bytes);
+                                      words, T * 4, N, ctx_bytes);
     const long long P = static_cast<long long>(st.P);
     const int cap = static_cast<int>(st.pm.cap);
     uint32_t* dres = st.dtail;
@@ -693,19 +721,28 @@ int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     // launch: a fix list longer than the capacity is run again with the exact
     // one (no error drain between the attempts: an overflowing fix list
     // raises none)
-    std::vector<uint32_t> res(N + 2);
+    std::vector<uint32_t> res(T);
     const size_t fcap = stage::run_with_retry(
         64 + words / 512,
         [&](size_t c) {
             reserve(h.entries, c * 3 * 4);
-            check_rc(qi_gpu_locate(pl, h.ctx.p, R, nullptr, st.din, 0, P, st.dcoded, 0, P,
-                                   st.dcnt, st.dent, cap, dres, dres + N, dres + N + 1,
-                                   static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
-                                   static_cast<long long>(words), 1, s),
-                     "locate");
+            if (t == 0)
+                check_rc(qi_gpu_locate(pl, h.ctx.p, R, nullptr, st.din, 0, P, st.dcoded, 0, P,
+                                       st.dcnt, st.dent, cap, dres, dres + N, dres + N + 1,
+                                       static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                       static_cast<long long>(words), 1, s),
+                         "locate");
+            else
+                check_rc(qi_gpu_locate_multi(pl, h.ctx.p, R, t, nullptr, st.din, 0, P, st.dcoded,
+                                             0, P, st.dcnt, st.dent, cap, dres, dres + N,
+                                             dres + N + 2, dres + N + 1,
+                                             static_cast<uint32_t*>(h.entries.p),
+                                             static_cast<int>(c), static_cast<long long>(words),
+                                             1, s),
+                         "locate");
         },
         [&] {
-            d2h(res.data(), dres, (N + 2) * 4, s);
+            d2h(res.data(), dres, (t ? T : N + 2) * 4, s);
             check(hipStreamSynchronize(s), "sync");
             return static_cast<size_t>(res[N + 1]);
         },
@@ -723,6 +760,8 @@ int RsFnt::locate_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     for (size_t i = 0; i < N; i++)
         result.located[ids[i]] = static_cast<long long>(res[i]);
     result.unlocated = static_cast<long long>(res[N]);
+    for (int nu = 0; nu < t; nu++)
+        result.weights[nu] = static_cast<long long>(res[N + 2 + nu]);
     for (size_t e = 0; e < nfix; e++)
         result.fixes.push_back(LocateFix{fx[3 * e], ids[fx[3 * e + 1]], fx[3 * e + 2]});
     if (!correct || result.fixes.empty() || result.unlocated != 0)
@@ -1727,6 +1766,37 @@ int qi_fec_locate_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t
         for (unsigned i = 0; i < f.code_len; i++)
             result[i] = res.located[i];
         result[f.code_len] = res.unlocated;
+        if (rc == 2 && oor_count)
+            stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
+        return rc;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_locate_multi_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                               uint32_t* oor_count, uint32_t cap, const int* missing,
+                               int max_errors, long long* result, int correct,
+                               size_t block_bytes)
+{
+    try {
+        if (!h || !parities || !missing || !result || max_errors < 1 ||
+            max_errors > QI_LOCATE_MAX_ERRORS)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.locate_supported(block_bytes))
+            return -2;
+        // (oor_count null: no marks, and none can be written)
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
+        qi::fec::LocateResult res;
+        const int rc = f.locate_multi_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res,
+                                                      max_errors, correct != 0, block_bytes,
+                                                      oor_count ? cap : 0);
+        for (unsigned i = 0; i < f.code_len; i++)
+            result[i] = res.located[i];
+        result[f.code_len] = res.unlocated;
+        for (int nu = 0; nu < max_errors; nu++)
+            result[f.code_len + 1 + nu] = res.weights[nu];
         if (rc == 2 && oor_count)
             stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
         return rc;

@@ -10,6 +10,7 @@
 #include "../../include/qi_gpu.h"
 #include "gf65537.h"
 #include "locate_math.h"
+#include "locate_multi_math.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
 #include "update_coef.h"
@@ -575,6 +576,46 @@ const char* qi_gpu_locate_kernels(const qi_plan* p, int R, long long words)
         return "";
     names = "locate=" + locate_ctx_kernel_name(locate_rp(R)) + " + " +
             locate_kernel_name(locate_rp(R), true);
+    return names.c_str();
+}
+
+// ---- multi-fragment locate: the same contexts and row pass, a bounded-
+// distance decoder behind them (locate_multi.hip, locate_multi_math.h) ----
+static_assert(QI_LOCATE_MAX_ERRORS == kLocMaxErrors, "qi_gpu.h and locate_multi_math.h differ");
+
+int qi_gpu_locate_multi(qi_plan* p, const void* d_ctx, int R, int t, const uint32_t* d_stripes,
+                        const uint16_t* d_data, long long dss, long long drs,
+                        const uint16_t* d_coded, long long css, long long crs,
+                        const uint32_t* d_counts, const uint32_t* d_entries, int cap,
+                        uint32_t* d_located, uint32_t* d_unlocated, uint32_t* d_weights,
+                        uint32_t* d_fix_counts, uint32_t* d_fixes, int fix_cap, long long words,
+                        int n_stripes, void* stream)
+{
+    if (!p || !d_ctx || !d_coded || !d_located || !d_unlocated || !d_weights || !d_fix_counts ||
+        n_stripes < 0 || words < 0 || fix_cap < 0 || (fix_cap > 0 && !d_fixes) ||
+        (d_counts && cap > 0 && !d_entries))
+        return -1;
+    if (p->k > kLocMaxK)
+        return QI_ERR_UNSUPPORTED;
+    if (!locate_ok(p, R) || t < 1 || 2 * t > R || (p->sys && !d_data))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    const Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs,
+                 cap};
+    return launch_locate_multi(static_cast<const int32_t*>(d_ctx), p->k, R, t, p->sys ? p->k : 0,
+                               d_stripes, d_data, dss, drs, d_coded, css, crs, in, d_located,
+                               d_unlocated, d_weights, d_fix_counts, d_fixes, fix_cap, words,
+                               n_stripes, p->d_err, st(stream));
+}
+
+const char* qi_gpu_locate_multi_kernels(const qi_plan* p, int R, int t, long long words)
+{
+    static thread_local std::string names;
+    if (!p || p->k > kLocMaxK || words <= 0 || !locate_ok(p, R) || t < 1 || 2 * t > R)
+        return "";
+    names = "locate_multi=" + locate_ctx_kernel_name(locate_rp(R)) + " + " +
+            locate_multi_kernel_name(locate_rp(R), true);
     return names.c_str();
 }
 

@@ -311,6 +311,17 @@ int launch_locate(const int32_t* d_ctx, int k, int R, int split, const uint32_t*
 // every base and stride is a multiple of 16 bytes
 std::string locate_ctx_kernel_name(int RP);
 std::string locate_kernel_name(int RP, bool vec);
+// the multi-fragment locate (locate_multi.hip) over the same contexts: up to t
+// bad fragments per column, 1 <= t <= R / 2; launch_locate's arguments and
+// d_weights [n_stripes][kLocMaxErrors].  Clears the five outputs first
+int launch_locate_multi(const int32_t* d_ctx, int k, int R, int t, int split,
+                        const uint32_t* d_stripes, const uint16_t* d_data, long long dss,
+                        long long drs, const uint16_t* d_coded, long long css, long long crs,
+                        const Oor& in, uint32_t* d_located, uint32_t* d_unlocated,
+                        uint32_t* d_weights, uint32_t* d_fix_counts, uint32_t* d_fixes,
+                        int fix_cap, long long words, int n_stripes, uint32_t* d_err,
+                        hipStream_t st);
+std::string locate_multi_kernel_name(int RP, bool vec);
 
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
