@@ -258,6 +258,22 @@ class RsFnt {
                                      int max_errors, bool correct, size_t block_size_bytes,
                                      size_t max_marks = static_cast<size_t>(-1));
 
+    // Fragment fingerprints (qi_gpu_fingerprint, include/qi_gpu.h): keys holds
+    // n_keys triples (a, b, d), each component in 1 .. 65536, 1 <= n_keys <=
+    // 8.  result gets code_len * n_keys values: per fragment id its n_keys
+    // fingerprints in [0, 65536], or -1 for a missing fragment.  Every present
+    // fragment is covered, at any n_data; a block wider than the device
+    // staging goes through in column chunks (first_col) whose results are
+    // added modulo 65537 here.  QI_FINGERPRINT_CHUNK_WORDS in the environment,
+    // read at call time, caps the chunk width (a test switch).  Throws
+    // std::invalid_argument for keys out of range.
+    void fingerprint_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                     std::vector<uint8_t*>& parities_bufs,
+                                     std::vector<Properties>& parities_props,
+                                     std::vector<int>& missing_idxs, const uint32_t* keys,
+                                     int n_keys, std::vector<long long>& result,
+                                     size_t block_size_bytes);
+
     void encode_streams_vertical(
         const std::vector<std::istream*>& input_data_bufs,
         std::vector<std::ostream*>& output_parities_bufs,

@@ -496,6 +496,83 @@ int qi_gpu_locate_multi(qi_plan* plan, const void* d_ctx, int n_checks, int max_
 const char* qi_gpu_locate_multi_kernels(const qi_plan* plan, int n_checks, int max_errors,
                                         long long words);
 
+/* ---- Fragment fingerprints: keyed digests of the rows that are homomorphic
+ * under the code, so that a stripe can be scrubbed from a few symbols per
+ * fragment instead of the fragments themselves.
+ *
+ * Symbols.  y_c in [0, 65536] is the restored symbol of a row: 65536 where
+ * column c is listed in the row's OOR bucket, the stored u16 otherwise (a
+ * systematic data row has no bucket) -- exactly how qi_gpu_locate reads rows.
+ *
+ * Keys and weights.  A key is a triple (a, b, d), each in [1, 65536]; F keys
+ * per call, 1 <= F <= QI_FINGERPRINT_MAX_KEYS, passed from the host as
+ * h_keys[F][3].  They travel as kernel arguments: no upload, no blocking copy.
+ * For the absolute column C = first_col + c take the base-256 digits C0 = C &
+ * 255, C1 = (C >> 8) & 255, C2 = C >> 16.  Then
+ *   w_j(C) = a_j^C0 b_j^C1 d_j^C2                      (mod 65537)
+ *   fp_j   = sum_{c < words} y_c w_j(first_col + c)    (mod 65537),
+ * canonical in [0, 65536].  Weights are never 0: one changed symbol changes
+ * every fp_j.  Every column of a stripe is a codeword P_c(r^f), so the
+ * fingerprints of a stripe's fragments are a codeword again, h_f = P_h(r^f)
+ * with P_h = sum_c w(c) P_c, in both code types: qi_gpu_verify, qi_gpu_locate
+ * and qi_gpu_locate_multi run unchanged on a stripe of F columns whose rows
+ * are the fragments' fingerprints (65536 as a mark), and the encode of the k
+ * data rows' fingerprints gives the fingerprints of all n outputs.
+ *
+ * Collision bound.  Three variables because the field has 65537 elements and
+ * rows are longer: a single power z^C would alias columns 65536 apart.  With
+ * base-256 digits two different rows of total width W collide under one
+ * uniformly random key with probability at most (510 + floor((W - 1) / 65536))
+ * / 65536 (Schwartz-Zippel: the difference is a non-zero polynomial of total
+ * degree at most 255 + 255 + floor((W - 1) / 65536)), under 0.8 % per key at
+ * 32768 words; keys are independent.  This is an error-detection digest, not
+ * a cryptographic one: keys must be random and kept from whoever may tamper
+ * with the data.
+ *
+ * first_col (chunking).  Bucket columns and `words` are relative to the row
+ * pointers given; only the weights see first_col, so the fingerprints of
+ * adjacent column slices of a row add modulo 65537 to the fingerprint of the
+ * whole row.  first_col >= 0 and first_col + words <= 2^32.
+ *
+ * The call.  Any plan qi_plan_create accepts, at any k, both code types; no
+ * context.  d_ids[s * N + i] are fragment ids in the decode's id space, 1 <=
+ * N <= k + m, and an id may repeat within a stripe.  Rows and buckets are
+ * addressed exactly as qi_gpu_decode addresses received rows (d_data for f <
+ * k of a systematic plan, d_coded by slot otherwise), with any positive
+ * strides and a unit inner stride at any 2-byte alignment (rows and strides
+ * that are all multiples of 16 bytes, with first_col a multiple of 8, move as
+ * 16-byte pieces per lane).  d_data may be NULL for a non-systematic plan; a
+ * systematic plan may pass NULL for the region it holds no row of, not both.
+ * NULL d_oor_counts: no marks.  A bucket with count <= oor_cap is restored in
+ * full however dense; a count above oor_cap raises bit 1 of
+ * qi_gpu_take_error, and bucket entries >= words are no columns.  An id not
+ * below k + m, or one in a region passed as NULL, raises bit 2: its F outputs
+ * are 0xFFFFFFFF and nothing is read for it.
+ * Arguments out of range -- NULL plan; n_keys, n_rows, words (1 .. 2^32) or
+ * first_col out of range; a key component outside 1 .. 65536 -- return -1
+ * (the kernels call "", the bytes call 0) and launch nothing.  For valid
+ * arguments the bytes call returns at least 4.
+ * d_fp[s][i][j] is written in full by the call (no clearing needed).  Results
+ * are exact and deterministic: the same bits whatever the grid.  d_work holds
+ * the call's power tables and, for rows longer than one block's share, the
+ * blocks' partial sums: one call at a time per work buffer.  Everything runs
+ * on `stream`. */
+#define QI_FINGERPRINT_MAX_KEYS 8
+size_t qi_gpu_fingerprint_work_bytes(const qi_plan* plan, int n_rows, int n_keys,
+                                     int n_stripes, long long words);
+int qi_gpu_fingerprint(qi_plan* plan, const uint16_t* d_ids /*[S][N] fragment ids*/, int n_rows,
+                       const uint32_t* h_keys /*[F][3], host*/, int n_keys, long long first_col,
+                       const uint16_t* d_data, long long dss, long long drs,
+                       const uint16_t* d_coded, long long css, long long crs,
+                       const uint32_t* d_oor_counts, const uint32_t* d_oor_entries, int oor_cap,
+                       void* d_work, uint32_t* d_fp /*[S][N][F]*/,
+                       long long words, int n_stripes, void* stream);
+/* "fingerprint=<table kernel> + <kernel>[ + <finish kernel>]" (rows and
+ * strides at multiples of 16 bytes, first_col 0); "" for arguments out of
+ * range.  Per calling thread, valid until its next call. */
+const char* qi_gpu_fingerprint_kernels(const qi_plan* plan, int n_rows, int n_keys,
+                                       long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -582,6 +659,20 @@ int qi_fec_locate_multi_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, ui
                                uint32_t* oor_count, uint32_t oor_cap, const int* missing,
                                int max_errors, long long* result, int correct,
                                size_t block_bytes);
+
+/* Fingerprints of every present fragment (RsFnt::fingerprint_blocks_vertical,
+ * qi_gpu_fingerprint): keys[n_keys][3], each component in 1 .. 65536, 1 <=
+ * n_keys <= QI_FINGERPRINT_MAX_KEYS.  result: (k + m) * n_keys values, per
+ * fragment id its n_keys fingerprints in [0, 65536], or -1 for a missing
+ * fragment.  Any k and any block width: blocks wider than the staging go
+ * through in column chunks and the chunk results are added modulo 65537.
+ * `data` may be NULL for non-systematic codes, oor_count NULL when no row has
+ * marks.  Returns 1 done, -1 error (a key or n_keys out of range, a NULL
+ * handle; nothing is staged). */
+int qi_fec_fingerprint_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, const uint32_t* oor,
+                              const uint32_t* oor_count, uint32_t oor_cap, const int* missing,
+                              const uint32_t* keys, int n_keys, long long* result,
+                              size_t block_bytes);
 
 /* Delta update of the held coded fragments (RsFnt::update_blocks_vertical,
  * include/qi_fec.hpp): data rows ids[0 .. n_rows) go from old_rows[u] to

@@ -77,6 +77,10 @@ def _declare(lib):
         "qi_gpu_locate_multi": (I, [V, V, I, I, V, V, LL, LL, V, LL, LL, V, V, I, V, V, V,
                                     V, V, I, LL, I, V]),
         "qi_gpu_locate_multi_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_fingerprint_work_bytes": (SZ, [V, I, I, I, LL]),
+        "qi_gpu_fingerprint": (I, [V, V, I, V, I, LL, V, LL, LL, V, LL, LL, V, V, I, V, V,
+                                   LL, I, V]),
+        "qi_gpu_fingerprint_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -90,6 +94,7 @@ def _declare(lib):
         "qi_fec_verify_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, SZ]),
         "qi_fec_locate_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, SZ]),
         "qi_fec_locate_multi_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, I, V, I, SZ]),
+        "qi_fec_fingerprint_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, V, SZ]),
         "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
@@ -698,6 +703,84 @@ class Plan:
             raise RuntimeError(f"qi_gpu_locate_multi failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    FINGERPRINT_MAX_KEYS = 8  # QI_FINGERPRINT_MAX_KEYS
+
+    def fingerprint_kernels(self, n_rows, n_keys, words):
+        """'fingerprint=<table kernel> + <kernel>[ + <finish kernel>]' a
+        fingerprint of n_rows rows under n_keys keys launches
+        (qi_gpu_fingerprint_kernels); '' for arguments out of range."""
+        return lib().qi_gpu_fingerprint_kernels(self.h, n_rows, n_keys, words).decode()
+
+    def fingerprint_work_bytes(self, n_rows, n_keys, n_stripes, words):
+        """Bytes of the work buffer of such a call (0: arguments out of
+        range)."""
+        return lib().qi_gpu_fingerprint_work_bytes(self.h, n_rows, n_keys, n_stripes,
+                                                   words)
+
+    @staticmethod
+    def _keys(keys):
+        import numpy as np
+        kk = np.ascontiguousarray(keys, np.int64)
+        if kk.ndim != 2 or kk.shape[1] != 3 or not 1 <= kk.shape[0] <= Plan.FINGERPRINT_MAX_KEYS:
+            raise ValueError("keys: expected 1 .. 8 triples (a, b, d)")
+        if kk.min() < 1 or kk.max() > 65536:
+            raise ValueError("keys: every component must lie in 1 .. 65536")
+        return np.ascontiguousarray(kk, np.uint32)
+
+    def fingerprint(self, ids, keys, fp, work, coded=None, data=None, counts=None,
+                    entries=None, cap=0, first_col=0, words=None, stream=None, check=True):
+        """Fragment fingerprints (qi_gpu_fingerprint).  ids: int16 tensor
+        [S, N] of fragment ids (decode id space; an id may repeat); keys: F
+        host triples (a, b, d), each in 1 .. 65536; coded: [S, n_out, P] with
+        its OOR buckets counts / entries, data: [S, k, P] for systematic codes
+        (either may be None when no listed row lives there); fp: int32 [S, N,
+        F], written in full; work: uint8 tensor of fingerprint_work_bytes(N,
+        F, S, words).  words: the columns to digest (default P); first_col:
+        the absolute column of column 0, for slices of a wider row.  Returns
+        the sticky error flags when check."""
+        import torch
+        if ids.dim() != 2:
+            raise ValueError("ids: expected [S, N]")
+        S, N = ids.shape
+        kk = self._keys(keys)
+        F = kk.shape[0]
+        P = None
+        for t, name, rows in ((coded, "coded", self.n_outputs), (data, "data", self.k)):
+            if t is None:
+                continue
+            _rows(t, name, rows, S)
+            if P is not None and t.shape[2] != P:
+                raise ValueError("data and coded differ in width")
+            P = t.shape[2]
+        if P is None or (coded is None and not self.sys):
+            raise ValueError("no rows given")
+        if data is not None and not self.sys:
+            data = None
+        words = P if words is None else int(words)
+        if not 1 <= words <= P:
+            raise ValueError("words: expected 1 .. P")
+        need = self.fingerprint_work_bytes(N, F, S, words)
+        if need == 0:
+            raise ValueError("fingerprint: n_rows out of range (1 .. k + m)")
+        _flat(ids, "ids", S * N, (torch.int16, torch.uint16))
+        _flat(work, "work", need, (torch.uint8,))
+        _flat(fp, "fp", S * N * F, (torch.int32,))
+        _oor(counts, entries, cap, S, self.n_outputs)
+        rc = lib().qi_gpu_fingerprint(
+            self.h, ids.data_ptr(), N, kk.ctypes.data_as(C.c_void_p), F, int(first_col),
+            data.data_ptr() if data is not None else None,
+            data.stride(0) if data is not None else 0,
+            data.stride(1) if data is not None else 0,
+            coded.data_ptr() if coded is not None else None,
+            coded.stride(0) if coded is not None else 0,
+            coded.stride(1) if coded is not None else 0,
+            counts.data_ptr() if counts is not None else None,
+            entries.data_ptr() if entries is not None else None, int(cap),
+            work.data_ptr(), fp.data_ptr(), words, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_fingerprint failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     def take_error(self):
         return lib().qi_gpu_take_error(self.h)
 
@@ -834,6 +917,78 @@ class Fec:
         if rc == 0:
             return None
         return (res, rc == 2) if correct else res
+
+    def fingerprint_blocks(self, data, parities, oor, counts, missing, keys):
+        """Fingerprints of every present fragment (qi_fec_fingerprint_blocks):
+        arguments as verify_blocks (counts None: no marks), keys: F triples
+        (a, b, d), each in 1 .. 65536.  Returns an int64 array (k + m, F): per
+        fragment id its F fingerprints in [0, 65536], -1 for a missing
+        fragment.  Any k and any block width."""
+        import numpy as np
+        kk = Plan._keys(keys)
+        rows = [r for r in list(data or []) + list(parities) if r is not None]
+        B = len(rows[0])
+        miss = np.ascontiguousarray(missing, np.int32)
+        for a in (oor, counts):
+            if a is not None and (a.dtype != np.uint32 or not a.flags.c_contiguous):
+                raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        res = np.full((self.k + self.m, kk.shape[0]), -1, np.int64)
+        rc = lib().qi_fec_fingerprint_blocks(
+            self.h, ptr_array(list(data)) if data is not None else None,
+            ptr_array(list(parities)),
+            oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+            counts.ctypes.data_as(C.c_void_p) if counts is not None else None,
+            oor.shape[1] if oor is not None else 0, miss.ctypes.data_as(C.c_void_p),
+            kk.ctypes.data_as(C.c_void_p), kk.shape[0], res.ctypes.data_as(C.c_void_p), B)
+        if rc != 1:
+            raise RuntimeError(f"qi_fec_fingerprint_blocks failed: {rc}")
+        return res
+
+    def check_fingerprints(self, fp, missing, max_errors=1):
+        """The coordinator's half of a scrub by fingerprints: fp is the
+        (k + m, F) table of the fragments' fingerprints under the same F keys
+        (fingerprint_blocks, or gathered from the nodes; rows of missing
+        fragments are ignored).  The fingerprints of a stripe's fragments are
+        a codeword in each of the F columns, so the present ones are laid out
+        as blocks of F words, a value of 65536 as a mark, and handed to
+        locate_blocks (max_errors 1: the single-fragment locate, 2 .. 4: up to
+        that many bad fragments).  Returns that call's array: per fragment id
+        the number of the F columns located in it (-1: missing or not
+        listed), then the unlocated columns (then, max_errors > 1, the columns
+        located with 1 .. max_errors fragments); None when too few fragments
+        are present.  Locate's limits hold: k <= 256 and at least k + 2
+        fragments present (ValueError otherwise).  A systematic data
+        fragment's fingerprint equal to 65536 cannot be stored in a data row:
+        ValueError -- draw another key (probability 1 / 65537 per data
+        fragment and key)."""
+        import numpy as np
+        fp = np.asarray(fp, np.int64)
+        n = self.k + self.m
+        if fp.ndim != 2 or fp.shape[0] != n or fp.shape[1] < 1:
+            raise ValueError("fp: expected a (k + m, F) table")
+        F = fp.shape[1]
+        miss = np.ascontiguousarray(missing, np.int32)
+        first = self.k if self.sys else 0
+        rows = [None] * n
+        oor = np.zeros((self.n_outputs, F), np.uint32)
+        counts = np.zeros(self.n_outputs, np.uint32)
+        for f in range(n):
+            if miss[f]:
+                continue
+            v = fp[f]
+            if v.min() < 0 or v.max() > 65536:
+                raise ValueError(f"fp: fragment {f} holds no fingerprints")
+            marks = np.flatnonzero(v == 65536)
+            if len(marks) and f < first:
+                raise ValueError(f"data fragment {f} has a fingerprint of 65536: "
+                                 "draw another key")
+            if f >= first:
+                counts[f - first] = len(marks)
+                oor[f - first, :len(marks)] = marks
+            rows[f] = np.ascontiguousarray((v & 0xffff).astype(np.uint16)).view(np.uint8)
+        return self.locate_blocks(rows[:first] if self.sys else None, rows[first:], oor,
+                                  counts, miss,
+                                  max_errors=None if max_errors == 1 else max_errors)
 
     def update_blocks(self, ids, old_rows, new_rows, parities, oor, counts):
         """Delta update (qi_fec_update_blocks): data rows `ids` go from

@@ -10,6 +10,7 @@
 #include <arpa/inet.h>
 #include <chrono>
 #include <memory>
+#include <cstdlib>
 #include <cstring>
 #include <sstream>
 #include <stdexcept>
@@ -426,7 +427,7 @@ namespace {
 // row slots of h.in (row = fragment id: the data rows first when systematic,
 // then the coded rows), the coded ones' OOR buckets by slot at the head of
 // h.counts, followed by `tail_bytes` for the caller's own results; h.ids and
-// h.ctx reserved.
+// h.ctx reserved.  offset: the first column staged (marks relative to it).
 struct Staged {
     size_t P;
     uint16_t *din, *dcoded;
@@ -438,7 +439,7 @@ Staged stage_fragments(qi_plan* pl, const stage::FragMap& map, const std::vector
                        const std::vector<uint8_t*>& data_bufs,
                        const std::vector<uint8_t*>& parities_bufs,
                        const std::vector<Properties>& parities_props, size_t words,
-                       size_t tail_bytes, size_t n_ids, size_t ctx_bytes)
+                       size_t tail_bytes, size_t n_ids, size_t ctx_bytes, size_t offset = 0)
 {
     HostState& h = pl->host;
     hipStream_t s = h.stream;
@@ -450,7 +451,7 @@ Staged stage_fragments(qi_plan* pl, const stage::FragMap& map, const std::vector
         if (!fs.is_data)
             marked[fs.slot] = &parities_props[fs.slot];
     }
-    st.pm = stage::pack_marks(marked, 0, words);
+    st.pm = stage::pack_marks(marked, offset, words);
     const auto off = stage::layout({no * 4, st.pm.entries.size() * 4, tail_bytes});
     reserve(h.in, (map.data_rows() + no) * P * 2);
     reserve(h.counts, off[3]);
@@ -463,7 +464,7 @@ Staged stage_fragments(qi_plan* pl, const stage::FragMap& map, const std::vector
     st.dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
     st.dtail = reinterpret_cast<uint32_t*>(dcb + off[2]);
     for (int id : upload)
-        h2d(st.din + id * P, map.pick(id, data_bufs, parities_bufs), words * 2, s);
+        h2d(st.din + id * P, map.pick(id, data_bufs, parities_bufs) + offset * 2, words * 2, s);
     upload_marks(st.pm, st.dcnt, st.dent, s);
     return st;
 }
@@ -770,6 +771,85 @@ int RsFnt::locate_run(std::vector<uint8_t*>& data_bufs, std::vector<uint8_t*>& p
                             max_marks))
         throw std::length_error("RsFnt::locate_blocks_vertical: mark list capacity");
     return 2;
+}
+
+// ---- fragment fingerprints (qi_gpu_fingerprint over the staged rows, in
+// column chunks that fit the staging) ----
+void RsFnt::fingerprint_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                        std::vector<uint8_t*>& parities_bufs,
+                                        std::vector<Properties>& parities_props,
+                                        std::vector<int>& missing_idxs, const uint32_t* keys,
+                                        int n_keys, std::vector<long long>& result,
+                                        size_t block_size_bytes)
+{
+    // validate
+    if (!keys || n_keys < 1 || n_keys > QI_FINGERPRINT_MAX_KEYS)
+        throw std::invalid_argument("RsFnt::fingerprint_blocks_vertical: n_keys");
+    for (int e = 0; e < 3 * n_keys; e++)
+        if (keys[e] < 1 || keys[e] > 65536)
+            throw std::invalid_argument("RsFnt::fingerprint_blocks_vertical: key out of range");
+    const size_t F = static_cast<size_t>(n_keys);
+    const size_t words = block_size_bytes / word_size;
+    if (words == 0 || words > (size_t{1} << 32))
+        throw std::invalid_argument("RsFnt::fingerprint_blocks_vertical: block size");
+    const stage::FragMap map = frag_map(*this);
+    const std::vector<int> present = map.present(missing_idxs);
+    result.assign(code_len * F, -1);
+    std::vector<int> held;
+    for (unsigned f = 0; f < code_len; f++)
+        if (present[f])
+            held.push_back(static_cast<int>(f));
+    if (held.empty())
+        return;
+    const size_t N = held.size();
+    for (auto& p : parities_props)
+        p.sort();
+    // the chunk: every fragment of the code has a row slot on the device (at
+    // most 256 MiB of rows), rows of whole kAlign granules
+    const size_t slots = map.data_rows() + map.n_outputs;
+    size_t chunk = std::max<size_t>(kAlign, (size_t{256} << 20) / (2 * slots) / kAlign * kAlign);
+    chunk = std::min(chunk, chunk_bytes(buf_size) / 2);
+    if (const char* env = std::getenv("QI_FINGERPRINT_CHUNK_WORDS")) {
+        const long long v = std::atoll(env);
+        if (v > 0)
+            chunk = std::min(chunk, static_cast<size_t>(v));
+    }
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    const std::vector<uint16_t> hids(held.begin(), held.end());
+    std::vector<uint32_t> sum(N * F, 0), res(N * F);
+    for (size_t c0 = 0; c0 < words; c0 += chunk) {
+        const size_t w = std::min(chunk, words - c0);
+        // stage: the present rows' columns [c0, c0 + w), their buckets, then
+        // the fingerprints
+        const Staged st = stage_fragments(pl, map, held, data_bufs, parities_bufs, parities_props,
+                                          w, N * F * 4, N, 0, c0);
+        const size_t wb = qi_gpu_fingerprint_work_bytes(pl, static_cast<int>(N), n_keys, 1,
+                                                        static_cast<long long>(w));
+        if (!wb)
+            throw std::runtime_error("RsFnt: fingerprint work size");
+        reserve(h.entries, wb);
+        h2d(h.ids.p, hids.data(), N * 2, s);
+        const long long P = static_cast<long long>(st.P);
+        // launch
+        check_rc(qi_gpu_fingerprint(pl, static_cast<uint16_t*>(h.ids.p), static_cast<int>(N),
+                                    keys, n_keys, static_cast<long long>(c0), st.din, 0, P,
+                                    st.dcoded, 0, P, st.dcnt, st.dent,
+                                    static_cast<int>(st.pm.cap), h.entries.p, st.dtail,
+                                    static_cast<long long>(w), 1, s),
+                 "fingerprint");
+        // collect
+        d2h(res.data(), st.dtail, N * F * 4, s);
+        check(hipStreamSynchronize(s), "sync");
+        if (qi_gpu_take_error(pl))
+            throw std::runtime_error("RsFnt: fingerprint failed (bad ids or OOR bucket capacity)");
+        for (size_t e = 0; e < N * F; e++)
+            sum[e] = (sum[e] + res[e]) % 65537u;
+    }
+    for (size_t i = 0; i < N; i++)
+        for (size_t j = 0; j < F; j++)
+            result[held[i] * F + j] = static_cast<long long>(sum[i * F + j]);
 }
 
 // ---- delta update (single chunk; qi_gpu_update_ctx, then the update in
@@ -1800,6 +1880,32 @@ int qi_fec_locate_multi_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, ui
         if (rc == 2 && oor_count)
             stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
         return rc;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_fingerprint_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, const uint32_t* oor,
+                              const uint32_t* oor_count, uint32_t cap, const int* missing,
+                              const uint32_t* keys, int n_keys, long long* result,
+                              size_t block_bytes)
+{
+    try {
+        if (!keys || n_keys < 1 || n_keys > QI_FINGERPRINT_MAX_KEYS)
+            return -1;
+        for (int e = 0; e < 3 * n_keys; e++)
+            if (keys[e] < 1 || keys[e] > 65536)
+                return -1;
+        if (!h || !parities || !missing || !result)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        // (oor_count null: no marks)
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
+        std::vector<long long> res;
+        f.fingerprint_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, keys, n_keys, res,
+                                      block_bytes);
+        std::copy(res.begin(), res.end(), result);
+        return 1;
     } catch (...) {
         return -1;
     }

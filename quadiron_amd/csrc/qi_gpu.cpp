@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/qi_gpu.h"
+#include "fingerprint_math.h"
 #include "gf65537.h"
 #include "locate_math.h"
 #include "locate_multi_math.h"
@@ -616,6 +617,62 @@ const char* qi_gpu_locate_multi_kernels(const qi_plan* p, int R, int t, long lon
         return "";
     names = "locate_multi=" + locate_ctx_kernel_name(locate_rp(R)) + " + " +
             locate_multi_kernel_name(locate_rp(R), true);
+    return names.c_str();
+}
+
+// ---- fragment fingerprints: F keyed digests of each listed row, homomorphic
+// under the code (fingerprint.hip, fingerprint_math.h).  Any plan: no context
+// is built ----
+static_assert(QI_FINGERPRINT_MAX_KEYS == kFpMaxKeys, "qi_gpu.h and fingerprint_math.h differ");
+
+static bool fingerprint_ok(const qi_plan* p, int N, int F, long long words)
+{
+    return p && F >= 1 && F <= kFpMaxKeys && N >= 1 && N <= p->code_len && words >= 1 &&
+           words <= (1LL << 32);
+}
+
+size_t qi_gpu_fingerprint_work_bytes(const qi_plan* p, int N, int F, int n_stripes,
+                                     long long words)
+{
+    if (!fingerprint_ok(p, N, F, words) || n_stripes < 0)
+        return 0;
+    return static_cast<size_t>(fp_work_words(static_cast<long long>(n_stripes) * N, fp_pad(F),
+                                             words)) *
+           sizeof(uint32_t);
+}
+
+int qi_gpu_fingerprint(qi_plan* p, const uint16_t* d_ids, int N, const uint32_t* h_keys, int F,
+                       long long first_col, const uint16_t* d_data, long long dss, long long drs,
+                       const uint16_t* d_coded, long long css, long long crs,
+                       const uint32_t* d_counts, const uint32_t* d_entries, int cap, void* d_work,
+                       uint32_t* d_fp, long long words, int n_stripes, void* stream)
+{
+    if (!fingerprint_ok(p, N, F, words) || !h_keys || first_col < 0 ||
+        first_col > (1LL << 32) - words || n_stripes < 0 || cap < 0 ||
+        (d_counts && cap > 0 && !d_entries))
+        return -1;
+    for (int e = 0; e < 3 * F; e++)
+        if (h_keys[e] < 1u || h_keys[e] > 65536u)
+            return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids || !d_work || !d_fp || (!d_data && !d_coded) || (!p->sys && !d_coded) ||
+        (d_data && (dss < 0 || drs < 0)) || (d_coded && (css < 0 || crs < 0)))
+        return -1;
+    const Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), p->n_outputs,
+                 cap};
+    return launch_fingerprint(d_ids, N, h_keys, F, first_col, p->sys ? p->k : 0, p->code_len,
+                              p->sys ? d_data : nullptr, dss, drs, d_coded, css, crs, in,
+                              static_cast<uint32_t*>(d_work), d_fp, words, n_stripes, p->d_err,
+                              st(stream));
+}
+
+const char* qi_gpu_fingerprint_kernels(const qi_plan* p, int N, int F, long long words)
+{
+    static thread_local std::string names;
+    if (!fingerprint_ok(p, N, F, words))
+        return "";
+    names = "fingerprint=" + fingerprint_kernel_names(F, true, words);
     return names.c_str();
 }
 

@@ -323,6 +323,19 @@ int launch_locate_multi(const int32_t* d_ctx, int k, int R, int t, int split,
                         hipStream_t st);
 std::string locate_multi_kernel_name(int RP, bool vec);
 
+// fragment fingerprints (fingerprint.hip, fingerprint_math.h): F digests of
+// each of the N listed rows per stripe; keys: F host triples (they travel as
+// kernel arguments), d_work: fp_work_words(S * N, fp_pad(F), words) u32.  An
+// id not below code_len, or in a region that is not held (null), raises
+// kErrBadIds and gives 0xFFFFFFFF.  The caller checks the ranges
+int launch_fingerprint(const uint16_t* d_ids, int N, const uint32_t* keys, int F,
+                       long long first_col, int split, int code_len, const uint16_t* d_data,
+                       long long dss, long long drs, const uint16_t* d_coded, long long css,
+                       long long crs, const Oor& in, uint32_t* d_work, uint32_t* d_fp,
+                       long long words, int n_stripes, uint32_t* d_err, hipStream_t st);
+// its kernels (rows and strides at multiples of 16 bytes when vec)
+std::string fingerprint_kernel_names(int F, bool vec, long long words);
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.
