@@ -176,6 +176,16 @@ def _oor(counts, entries, cap, S, slots):
     _flat(entries, "entries", S * slots * cap, (torch.int32,))
 
 
+def _ptr(t):
+    """The device pointer of an optional tensor (None -> NULL)."""
+    return t.data_ptr() if t is not None else None
+
+
+def _row_args(t):
+    """(pointer, stripe stride, row stride) of an optional row tensor."""
+    return (t.data_ptr(), t.stride(0), t.stride(1)) if t is not None else (None, 0, 0)
+
+
 def require_device():
     n = lib().qi_gpu_device_count()
     if n < 1:
@@ -241,8 +251,7 @@ class Plan:
         rc = lib().qi_gpu_encode(
             self.h, data.data_ptr(), data.stride(0), data.stride(1),
             out.data_ptr(), out.stride(0), out.stride(1), P, S,
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_encode failed: {rc}")
@@ -263,8 +272,7 @@ class Plan:
             self.h, ids.data_ptr(),
             h_ids.ctypes.data_as(C.c_void_p) if h_ids is not None else None,
             ids.shape[0],
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             words, ctx.data_ptr(), self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_decode_ctx failed: {rc}")
@@ -288,8 +296,7 @@ class Plan:
         rc = lib().qi_gpu_decode(
             self.h, ctx.data_ptr(), ids.data_ptr(), d.data_ptr(), d.stride(0),
             d.stride(1), coded.data_ptr(), coded.stride(0), coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             out.data_ptr(), out.stride(0), out.stride(1), P, S,
             self._stream(stream))
         if rc:
@@ -309,8 +316,7 @@ class Plan:
             self.h, ids.data_ptr(),
             h_ids.ctypes.data_as(C.c_void_p) if h_ids is not None else None,
             ids.shape[0],
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             words, ctx.data_ptr(), self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_decode_ctx_packed failed: {rc}")
@@ -327,8 +333,7 @@ class Plan:
         rc = lib().qi_gpu_decode_packed(
             self.h, ctx.data_ptr(), recv.data_ptr(), recv.stride(0),
             recv.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             out.data_ptr(), out.stride(0), out.stride(1), P, S,
             self._stream(stream))
         if rc:
@@ -347,6 +352,16 @@ class Plan:
         return lib().qi_gpu_repair_ctx_bytes(self.h, n_targets, n_stripes,
                                              words)
 
+    def _repair_need(self, what, R, S, words):
+        """repair_ctx_bytes, or the error of a "repair" / "check" of R
+        fragments that the plan does not support."""
+        need = self.repair_ctx_bytes(R, S, words)
+        if need == 0 and S > 0:
+            noun = "targets" if what == "repair" else "fragments"
+            raise ValueError(f"{what} of {R} {noun} is not supported on "
+                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        return need
+
     def repair_ctx(self, ids, targets, ctx, words, counts=None, entries=None,
                    cap=0, stream=None):
         """ids: int16 tensor [S, k] (received fragment ids); targets: int16
@@ -356,18 +371,14 @@ class Plan:
         if ids.dim() != 2 or targets.dim() != 2 or ids.shape[0] != targets.shape[0]:
             raise ValueError("ids: expected [S, k], targets: [S, R]")
         S, R = targets.shape
-        need = self.repair_ctx_bytes(R, S, words)
-        if need == 0 and S > 0:
-            raise ValueError(f"repair of {R} targets is not supported on "
-                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        need = self._repair_need("repair", R, S, words)
         _flat(ids, "ids", S * self.k, (torch.int16, torch.uint16))
         _flat(targets, "targets", S * R, (torch.int16, torch.uint16))
         _flat(ctx, "ctx", need, (torch.uint8,))
         _oor(counts, entries, cap, S, self.n_outputs)
         rc = lib().qi_gpu_repair_ctx(
             self.h, ids.data_ptr(), targets.data_ptr(), R, S,
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             words, ctx.data_ptr(), self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_repair_ctx failed: {rc}")
@@ -384,10 +395,7 @@ class Plan:
         _rows(coded, "coded", self.n_outputs, S)
         if data is not None:
             _rows(data, "data", self.k, S)
-        need = self.repair_ctx_bytes(R, S, P)
-        if need == 0 and S > 0:
-            raise ValueError(f"repair of {R} targets is not supported on "
-                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        need = self._repair_need("repair", R, S, P)
         import torch
         _flat(ctx, "ctx", need, (torch.uint8,))
         _oor(counts, entries, cap, S, self.n_outputs)
@@ -396,12 +404,9 @@ class Plan:
         rc = lib().qi_gpu_repair(
             self.h, ctx.data_ptr(), R, d.data_ptr(), d.stride(0), d.stride(1),
             coded.data_ptr(), coded.stride(0), coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             out.data_ptr(), out.stride(0), out.stride(1),
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_entries.data_ptr() if out_entries is not None else None,
-            int(out_cap), P, S, self._stream(stream))
+            _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_repair failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
@@ -438,10 +443,7 @@ class Plan:
             _rows(data, "data", self.k, S)
             if data.shape[2] != P:
                 raise ValueError("data and coded differ in width")
-        need = self.repair_ctx_bytes(R, S, P)
-        if need == 0 and S > 0:
-            raise ValueError(f"check of {R} fragments is not supported on "
-                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
+        need = self._repair_need("check", R, S, P)
         _flat(checks, "checks", S * R, (torch.int16, torch.uint16))
         _flat(ctx, "ctx", need, (torch.uint8,))
         _flat(work, "work", self.verify_work_bytes(R, S, work_cap), (torch.uint8,))
@@ -456,8 +458,7 @@ class Plan:
             self.h, ctx.data_ptr(), R, checks.data_ptr(), d.data_ptr(),
             d.stride(0), d.stride(1), coded.data_ptr(), coded.stride(0),
             coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             work.data_ptr(), int(work_cap), value_mismatch.data_ptr(),
             mark_mismatch.data_ptr(), first.data_ptr(), P, S,
             self._stream(stream))
@@ -496,8 +497,7 @@ class Plan:
         _flat(slots, "slots", S * R, (torch.int16, torch.uint16))
         _flat(ctx, "ctx", need, (torch.uint8,))
         rc = lib().qi_gpu_update_ctx(
-            self.h, ids.data_ptr(), slots.data_ptr() if slots is not None else None,
-            U, R, S, ctx.data_ptr(), self._stream(stream))
+            self.h, ids.data_ptr(), _ptr(slots), U, R, S, ctx.data_ptr(), self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_update_ctx failed: {rc}")
 
@@ -532,12 +532,9 @@ class Plan:
             old.data_ptr(), old.stride(0), old.stride(1),
             new.data_ptr(), new.stride(0), new.stride(1),
             coded.data_ptr(), coded.stride(0), coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            _ptr(counts), _ptr(entries), int(cap),
             out.data_ptr(), out.stride(0), out.stride(1),
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_entries.data_ptr() if out_entries is not None else None,
-            int(out_cap), P, S, self._stream(stream))
+            _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_update failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
@@ -573,17 +570,12 @@ class Plan:
         if rc:
             raise RuntimeError(f"qi_gpu_locate_ctx failed: {rc}")
 
-    def locate(self, ctx, n_checks, coded, located, unlocated, fix_counts,
-               fixes=None, fix_cap=0, data=None, counts=None, entries=None,
-               cap=0, stripes=None, stream=None, check=True):
-        """Fragment locate (qi_gpu_locate).  ctx: built by locate_ctx; coded:
-        [S_all, n_out, P] (fragment slot rows, with their OOR buckets counts /
-        entries), data: [S_all, k, P] for systematic codes.  stripes: int32
-        tensor of the stripes to look at (list position -> stripe), None for
-        all S_all in order.  Outputs by list position, int32, initialised by
-        the call: located [S, k + R], unlocated [S], fix_counts [S], fixes
-        [S, fix_cap, 3] of {column, position, corrected symbol}.  Returns the
-        sticky error flags when check."""
+    def _locate_args(self, ctx, n_checks, coded, outputs, fixes, fix_cap, data,
+                     counts, entries, cap, stripes, check):
+        """The checks locate and locate_multi share.  outputs: the call's
+        required (tensor, name, elements per list position).  Returns the
+        argument runs in front of and behind the C call's outputs: (stripes,
+        data rows, coded rows, buckets) and (fixes, fix_cap, P, S)."""
         import torch
         _rows(coded, "coded", self.n_outputs)
         S_all, _, P = coded.shape
@@ -607,29 +599,38 @@ class Plan:
         if need == 0 and S > 0:
             raise ValueError(f"locate with {n_checks} checks is not supported on "
                              f"this plan (k <= 256, 2 <= R <= min(8, m))")
-        N = self.k + n_checks
         _flat(ctx, "ctx", need, (torch.uint8,))
         _oor(counts, entries, cap, S_all, self.n_outputs)
-        for t, name, n in ((located, "located", S * N), (unlocated, "unlocated", S),
-                           (fix_counts, "fix_counts", S)):
+        for t, name, n in outputs:
             if t is None:
                 raise ValueError(f"{name}: required")
-            _flat(t, name, n, (torch.int32,))
+            _flat(t, name, S * n, (torch.int32,))
         if fix_cap < 0 or (fix_cap > 0 and fixes is None):
             raise ValueError("fix_cap > 0 needs fixes")
         _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        return ((_ptr(stripes), *_row_args(data), *_row_args(coded), _ptr(counts),
+                 _ptr(entries), int(cap)),
+                (_ptr(fixes), int(fix_cap), P, S))
+
+    def locate(self, ctx, n_checks, coded, located, unlocated, fix_counts,
+               fixes=None, fix_cap=0, data=None, counts=None, entries=None,
+               cap=0, stripes=None, stream=None, check=True):
+        """Fragment locate (qi_gpu_locate).  ctx: built by locate_ctx; coded:
+        [S_all, n_out, P] (fragment slot rows, with their OOR buckets counts /
+        entries), data: [S_all, k, P] for systematic codes.  stripes: int32
+        tensor of the stripes to look at (list position -> stripe), None for
+        all S_all in order.  Outputs by list position, int32, initialised by
+        the call: located [S, k + R], unlocated [S], fix_counts [S], fixes
+        [S, fix_cap, 3] of {column, position, corrected symbol}.  Returns the
+        sticky error flags when check."""
+        rows, tail = self._locate_args(
+            ctx, n_checks, coded,
+            ((located, "located", self.k + n_checks), (unlocated, "unlocated", 1),
+             (fix_counts, "fix_counts", 1)),
+            fixes, fix_cap, data, counts, entries, cap, stripes, check)
         rc = lib().qi_gpu_locate(
-            self.h, ctx.data_ptr(), n_checks,
-            stripes.data_ptr() if stripes is not None else None,
-            data.data_ptr() if data is not None else None,
-            data.stride(0) if data is not None else 0,
-            data.stride(1) if data is not None else 0,
-            coded.data_ptr(), coded.stride(0), coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
-            located.data_ptr(), unlocated.data_ptr(), fix_counts.data_ptr(),
-            fixes.data_ptr() if fixes is not None else None, int(fix_cap),
-            P, S, self._stream(stream))
+            self.h, ctx.data_ptr(), n_checks, *rows, located.data_ptr(),
+            unlocated.data_ptr(), fix_counts.data_ptr(), *tail, self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_locate failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
@@ -653,52 +654,15 @@ class Plan:
         list position s located with nu fragments.  A located column adds 1
         to each of its fragments' located counters and its nu fix entries are
         adjacent.  Returns the sticky error flags when check."""
-        import torch
-        _rows(coded, "coded", self.n_outputs)
-        S_all, _, P = coded.shape
-        if data is not None:
-            _rows(data, "data", self.k, S_all)
-            if data.shape[2] != P:
-                raise ValueError("data and coded differ in width")
-        elif self.sys:
-            raise ValueError("a systematic plan needs the data rows")
-        if stripes is not None:
-            _flat(stripes, "stripes", 0, (torch.int32,))
-            S = stripes.numel()
-            if check and S > 0 and not (0 <= int(stripes.min()) and
-                                        int(stripes.max()) < S_all):
-                raise ValueError(f"stripes: values must lie in [0, {S_all})")
-        else:
-            S = S_all
-        need = self.locate_ctx_bytes(n_checks, S)
-        if need == 0 and S > 0:
-            raise ValueError(f"locate with {n_checks} checks is not supported on "
-                             f"this plan (k <= 256, 2 <= R <= min(8, m))")
-        N = self.k + n_checks
-        _flat(ctx, "ctx", need, (torch.uint8,))
-        _oor(counts, entries, cap, S_all, self.n_outputs)
-        for t, name, n in ((located, "located", S * N), (unlocated, "unlocated", S),
-                           (weights, "weights", S * self.LOCATE_MAX_ERRORS),
-                           (fix_counts, "fix_counts", S)):
-            if t is None:
-                raise ValueError(f"{name}: required")
-            _flat(t, name, n, (torch.int32,))
-        if fix_cap < 0 or (fix_cap > 0 and fixes is None):
-            raise ValueError("fix_cap > 0 needs fixes")
-        _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        rows, tail = self._locate_args(
+            ctx, n_checks, coded,
+            ((located, "located", self.k + n_checks), (unlocated, "unlocated", 1),
+             (weights, "weights", self.LOCATE_MAX_ERRORS), (fix_counts, "fix_counts", 1)),
+            fixes, fix_cap, data, counts, entries, cap, stripes, check)
         rc = lib().qi_gpu_locate_multi(
-            self.h, ctx.data_ptr(), n_checks, int(max_errors),
-            stripes.data_ptr() if stripes is not None else None,
-            data.data_ptr() if data is not None else None,
-            data.stride(0) if data is not None else 0,
-            data.stride(1) if data is not None else 0,
-            coded.data_ptr(), coded.stride(0), coded.stride(1),
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
-            located.data_ptr(), unlocated.data_ptr(), weights.data_ptr(),
-            fix_counts.data_ptr(),
-            fixes.data_ptr() if fixes is not None else None, int(fix_cap),
-            P, S, self._stream(stream))
+            self.h, ctx.data_ptr(), n_checks, int(max_errors), *rows, located.data_ptr(),
+            unlocated.data_ptr(), weights.data_ptr(), fix_counts.data_ptr(), *tail,
+            self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_locate_multi failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
@@ -768,14 +732,8 @@ class Plan:
         _oor(counts, entries, cap, S, self.n_outputs)
         rc = lib().qi_gpu_fingerprint(
             self.h, ids.data_ptr(), N, kk.ctypes.data_as(C.c_void_p), F, int(first_col),
-            data.data_ptr() if data is not None else None,
-            data.stride(0) if data is not None else 0,
-            data.stride(1) if data is not None else 0,
-            coded.data_ptr() if coded is not None else None,
-            coded.stride(0) if coded is not None else 0,
-            coded.stride(1) if coded is not None else 0,
-            counts.data_ptr() if counts is not None else None,
-            entries.data_ptr() if entries is not None else None, int(cap),
+            *_row_args(data), *_row_args(coded),
+            _ptr(counts), _ptr(entries), int(cap),
             work.data_ptr(), fp.data_ptr(), words, S, self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_fingerprint failed: {rc}")

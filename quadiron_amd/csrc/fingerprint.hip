@@ -23,8 +23,9 @@
 // mul24 + fold per (symbol, key), the hi step once per 8 symbols.  Otherwise
 // the lane's columns are 256 apart (scalar loads, any alignment): they share
 // C0, and each symbol is stepped with the hi weight of its own H.  Either way
-// the lane's a^C0 is one canonical product per key at the end.  Marks come
-// through locate's LDS bitmap of the tile (locate_rows.h: no density limit).
+// the lane's a^C0 is one canonical product per key at the end.  The loads and
+// the marks, through the LDS bitmap of the tile (no density limit), are
+// row_tile.h's.
 // The block sums its lanes' canonical values by wave shuffles, then LDS:
 // integer sums, so the result does not depend on the grid.  No floating point,
 // no atomics on results.
@@ -34,18 +35,14 @@
 
 #include "fingerprint_math.h"
 #include "gf65537.h"
-#include "locate_rows.h"
 #include "qi_internal.h"
+#include "row_tile.h"
 
 namespace qi {
 
-using locrows::loc_load;
-using locrows::loc_marks;
-using locrows::loc_rel;
-
-static_assert(kFpBlock == locrows::kLocBlock && kFpCols == locrows::kLocCols &&
-                  kFpTile == locrows::kLocTile,
-              "fingerprint.hip borrows locate_rows.h's loads and mark bitmap");
+// fingerprint_math.h keeps its own names for the host's index math
+static_assert(kFpBlock == kTileBlock && kFpCols == kTileCols,
+              "fingerprint_math.h's tile is row_tile.h's");
 
 constexpr int kFpAhead = 4;  // tiles in flight per lane
 
@@ -106,6 +103,8 @@ __global__ __launch_bounds__(kFpBlock) void fingerprint_kernel(FpArgs a, FpPower
             a.fp[row * a.F + tid] = 0xFFFFFFFFu;
         return;
     }
+    // row_tile.h's frag_row in this file's own text: called from here it
+    // reorders the kernel's argument loads (13 more instructions over the forms)
     const uint16_t* rp;
     long long bk = -1;
     if (id < a.split) {
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(kFpBlock) void fingerprint_kernel(FpArgs a, FpPower
         for (int q = 0; q < kFpAhead; q++) {
             if (t0 + q < nt) {
                 const long long c0 = cbeg + static_cast<long long>(t0 + q) * kFpTile;
-                loc_load<VEC>(rp, c0, tid, c0 + tid * kFpCols + kFpCols <= a.words, a.words,
+                tile_load<VEC>(rp, c0, tid, c0 + tid * kFpCols + kFpCols <= a.words, a.words,
                               w[q]);
             }
         }
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(kFpBlock) void fingerprint_kernel(FpArgs a, FpPower
             const long long c0 = cbeg + static_cast<long long>(t0 + q) * kFpTile;
             uint32_t mk = 0;
             if (cnt)
-                mk = loc_marks<VEC>(bitmap, a.in, bk, cnt, c0, a.words, tid, a.err);
+                mk = tile_marks<VEC>(bitmap, a.in, bk, cnt, c0, a.words, tid, a.err);
             int32_t y[kFpCols];
 #pragma unroll
             for (int i = 0; i < kFpCols; i++)
@@ -271,13 +270,7 @@ int launch_fingerprint(const uint16_t* d_ids, int N, const uint32_t* keys, int F
     FpArgs a{d_ids, d_data, dss, drs, d_coded, css, crs, in, d_work,
              d_work + fp_tab_words(fp_c2_max(words), FP), d_fp, words, first_col, c2s, N, F,
              split, code_len, static_cast<int>(chunks), d_err};
-    bool vec = first_col % kFpCols == 0;
-    if (d_coded)
-        vec = vec && reinterpret_cast<uintptr_t>(d_coded) % 16 == 0 && css % kFpCols == 0 &&
-              crs % kFpCols == 0;
-    if (split && d_data)
-        vec = vec && reinterpret_cast<uintptr_t>(d_data) % 16 == 0 && dss % kFpCols == 0 &&
-              drs % kFpCols == 0;
+    const bool vec = fingerprint_rows_vec(first_col, split, d_data, dss, drs, d_coded, css, crs);
     const unsigned nb = static_cast<unsigned>(rows * chunks);
     switch (FP) {
     case 1: fp_launch<1>(vec, nb, a, keys, st); break;

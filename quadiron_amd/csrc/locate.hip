@@ -5,15 +5,12 @@
 // N rows once, accumulates the R syndromes of every column and classifies the
 // columns whose syndromes are not all 0.  N rows in, no row out.
 //
-// A block owns one listed stripe and one tile of kLocTile columns, a lane 8
-// columns.  It walks the N rows kLocAhead at a time (the loads of a group are
-// issued before the first of them is used) and keeps RP x 8 syndrome
-// accumulators in registers.  Addressing is flat with 64-bit wave-uniform row
-// offsets, as in update.hip: VEC, every base and stride a multiple of 16
-// bytes, a lane moves its 8 adjacent columns as one 16-byte piece; otherwise
-// lane t takes the columns t, t + 256, ... of the tile symbol by symbol.
-// The marks of a row are restored in full through an LDS bitmap of the tile,
-// filled from the row's bucket 256 entries at a time.
+// A block owns one listed stripe and one tile of kTileElems columns, a lane 8
+// columns (row_tile.h: the addressing, its two forms VEC and symbol by
+// symbol, and the LDS bitmap that restores a row's marks in full).  It walks
+// the N rows kLocAhead at a time (the loads of a group are issued before the
+// first of them is used) and keeps RP x 8 syndrome accumulators in registers.
+// The loop is this file's own text; locate_rows.h says why.
 //
 // Ranges (gf65537.h).  A restored symbol y is in [0, 65536] and a coefficient
 // c balanced, in [-32768, 32768]: y c reaches 65536 * 32768 = 2^31, which no
@@ -36,17 +33,12 @@
 
 #include "gf65537.h"
 #include "locate_math.h"
+#include "locate_rows.h"
 #include "qi_internal.h"
 
 namespace qi {
 
-constexpr int kLocBlock = 256;
-constexpr int kLocCols = 8;  // columns per lane: one 16-byte row piece
-constexpr int kLocTile = kLocBlock * kLocCols;
-constexpr int kLocAhead = 4;  // rows in flight per lane
 constexpr int kLocCtxThreads = 256;
-
-typedef uint32_t loc_u32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------
 // The context: one block per stripe.  ids that are not below code_len or are
@@ -124,121 +116,26 @@ int launch_locate_ctx(int k, int R, int code_len, uint32_t r, const uint16_t* d_
 // ---------------------------------------------------------------------------
 // The apply kernel
 // ---------------------------------------------------------------------------
-struct LocArgs {
-    long long ctx_stride;
-    const uint32_t* stripes;  // list position -> stripe (null: the identity)
-    const uint16_t* data;     // fragments below `split` (systematic data rows)
-    long long dss, drs;
-    const uint16_t* coded;
-    long long css, crs;
-    Oor in;  // the coded rows' buckets by slot (counts null: no marks)
-    uint32_t* located;
-    uint32_t* unlocated;
-    uint32_t* fix_counts;
-    uint32_t* fixes;
-    int fix_cap;
-    long long words;
-    int N, R, split, tiles;
-    uint32_t* err;
-};
-
-// column of a lane's element i, relative to the tile
-template <bool VEC>
-__device__ __forceinline__ int loc_rel(int tid, int i)
-{
-    return VEC ? tid * kLocCols + i : i * kLocBlock + tid;
-}
-
-// a lane's 8 columns of `row` as 4 packed pairs; columns past the row's end
-// read 0.  full: the lane's 16-byte piece lies inside the row
-template <bool VEC>
-__device__ __forceinline__ void loc_load(const uint16_t* row, long long c0, int tid, bool full,
-                                         long long words, uint32_t (&w)[4])
-{
-    if (VEC && full) {
-        const loc_u32x4 v = *reinterpret_cast<const loc_u32x4*>(row + c0 + tid * kLocCols);
-        w[0] = v[0];
-        w[1] = v[1];
-        w[2] = v[2];
-        w[3] = v[3];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < kLocCols; i += 2) {
-        const long long ca = c0 + loc_rel<VEC>(tid, i), cb = c0 + loc_rel<VEC>(tid, i + 1);
-        const uint32_t lo = ca < words ? row[ca] : 0u;
-        const uint32_t hi = cb < words ? row[cb] : 0u;
-        w[i / 2] = lo | hi << 16;
-    }
-}
-
-// The marked columns of this tile in bucket bk, as a mask over the lane's 8
-// elements: the block scans the bucket's entries 256 at a time into an LDS
-// bitmap of the tile (a dense bucket costs entries / 256 steps).  Called by
-// the whole block (cnt is the same in every lane).
-template <bool VEC>
-__device__ __forceinline__ uint32_t loc_marks(uint32_t* bitmap, const Oor& in, long long bk,
-                                              uint32_t cnt, long long c0, long long words,
-                                              int tid, uint32_t* err)
-{
-    __syncthreads();  // the previous bitmap has been read
-    if (tid < kLocTile / 32)
-        bitmap[tid] = 0;
-    __syncthreads();
-    const uint32_t cap = static_cast<uint32_t>(in.cap);
-    if (cnt > cap && tid == 0)
-        atomicOr(err, kErrOorTruncated);
-    const uint32_t n = cnt < cap ? cnt : cap;
-    const uint32_t* e = in.entries + bk * in.cap;
-    for (uint32_t x = static_cast<uint32_t>(tid); x < n; x += kLocBlock) {
-        const long long col = e[x];
-        const long long rel = col - c0;
-        if (rel >= 0 && rel < kLocTile && col < words)
-            atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
-    }
-    __syncthreads();
-    uint32_t mk = 0;
-#pragma unroll
-    for (int i = 0; i < kLocCols; i++) {
-        const int rel = loc_rel<VEC>(tid, i);
-        mk |= (bitmap[rel >> 5] >> (rel & 31) & 1u) << i;
-    }
-    return mk;
-}
-
-// fragment id -> its row of stripe sr and its bucket (-1: a data row, none)
-__device__ __forceinline__ const uint16_t* loc_row(const LocArgs& a, long long sr, int id,
-                                                   long long* bk)
-{
-    if (id < a.split) {
-        *bk = -1;
-        return a.data + sr * a.dss + id * a.drs;
-    }
-    const int slot = id - a.split;
-    *bk = sr * a.in.slots + slot;
-    return a.coded + sr * a.css + slot * a.crs;
-}
-
 template <int RP, bool VEC>
-__global__ __launch_bounds__(kLocBlock) void locate_kernel(LocArgs a,
+__global__ __launch_bounds__(kTileBlock) void locate_kernel(LocArgs a,
                                                            const int32_t* __restrict__ ctx)
 {
-    __shared__ uint32_t bitmap[kLocTile / 32];
+    __shared__ uint32_t bitmap[kTileElems / 32];
     const int tid = static_cast<int>(threadIdx.x);
     const int tile = static_cast<int>(blockIdx.x) % a.tiles;  // tiles fastest
     const int s = static_cast<int>(blockIdx.x) / a.tiles;
     const long long sr = a.stripes ? a.stripes[s] : s;
-    const long long c0 = static_cast<long long>(tile) * kLocTile;
-    const bool full = c0 + tid * kLocCols + kLocCols <= a.words;
+    const long long c0 = static_cast<long long>(tile) * kTileElems;
+    const bool full = c0 + tid * kTileCols + kTileCols <= a.words;
     const int N = a.N;
     const int32_t* ids = ctx + static_cast<long long>(s) * a.ctx_stride;
     const int32_t* coef = ids + 3 * N;
 
-    int32_t acc[RP][kLocCols];
+    int32_t acc[RP][kTileCols];
 #pragma unroll
     for (int j = 0; j < RP; j++)
 #pragma unroll
-        for (int i = 0; i < kLocCols; i++)
+        for (int i = 0; i < kTileCols; i++)
             acc[j][i] = 0;
 
     for (int i0 = 0; i0 < N; i0 += kLocAhead) {
@@ -248,8 +145,8 @@ __global__ __launch_bounds__(kLocBlock) void locate_kernel(LocArgs a,
 #pragma unroll
         for (int q = 0; q < kLocAhead; q++) {
             if (i0 + q < N) {
-                const uint16_t* row = loc_row(a, sr, ids[i0 + q], &bk[q]);
-                loc_load<VEC>(row, c0, tid, full, a.words, w[q]);
+                const uint16_t* row = frag_row(a.rows(), a.in.slots, sr, ids[i0 + q], &bk[q]);
+                tile_load<VEC>(row, c0, tid, full, a.words, w[q]);
                 cnt[q] = bk[q] >= 0 && a.in.counts ? a.in.counts[bk[q]] : 0u;
             }
         }
@@ -259,10 +156,10 @@ __global__ __launch_bounds__(kLocBlock) void locate_kernel(LocArgs a,
                 break;
             uint32_t mk = 0;
             if (cnt[q])
-                mk = loc_marks<VEC>(bitmap, a.in, bk[q], cnt[q], c0, a.words, tid, a.err);
+                mk = tile_marks<VEC>(bitmap, a.in, bk[q], cnt[q], c0, a.words, tid, a.err);
             const int32_t* c = coef + (i0 + q) * RP;
 #pragma unroll
-            for (int i = 0; i < kLocCols; i++) {
+            for (int i = 0; i < kTileCols; i++) {
                 const int32_t y = static_cast<int32_t>(w[q][i / 2] >> (i % 2 * 16) & 0xffffu);
                 int32_t yb = y > 32768 ? y - kQ : y;
                 if (mk)  // a marked symbol is 65536 = -1
@@ -277,7 +174,7 @@ __global__ __launch_bounds__(kLocBlock) void locate_kernel(LocArgs a,
     // canonical syndromes; nz: the lane's columns with one that is not 0
     uint32_t nz = 0;
 #pragma unroll
-    for (int i = 0; i < kLocCols; i++) {
+    for (int i = 0; i < kTileCols; i++) {
         uint32_t any = 0;
 #pragma unroll
         for (int j = 0; j < RP; j++) {
@@ -302,18 +199,20 @@ __global__ __launch_bounds__(kLocBlock) void locate_kernel(LocArgs a,
         for (int j = 0; j < RP; j++) {
             uint32_t v = 0;
 #pragma unroll
-            for (int ii = 0; ii < kLocCols; ii++)
+            for (int ii = 0; ii < kTileCols; ii++)
                 v = i == ii ? static_cast<uint32_t>(acc[j][ii]) : v;
             S[j] = v;
         }
-        const long long col = c0 + (VEC ? tid * kLocCols + i : i * kLocBlock + tid);
+        const long long col = c0 + tile_rel<VEC>(tid, i);
         int pos = 0;
         bool found = locate_classify<RP>(S, a.R, xs, N, &pos) == kLocFound;
         uint32_t v = 0;
         if (found) {
-            // the named fragment's restored symbol at this column
+            // the named fragment's restored symbol at this column: row_tile.h's
+            // tile_symbol in this file's own text (calling it moves registers
+            // and adds 6 instructions over the six forms)
             long long bkp;
-            const uint16_t* row = loc_row(a, sr, ids[pos], &bkp);
+            const uint16_t* row = frag_row(a.rows(), a.in.slots, sr, ids[pos], &bkp);
             uint32_t y = row[col];
             if (bkp >= 0 && a.in.counts) {
                 const uint32_t cap = static_cast<uint32_t>(a.in.cap);
@@ -351,9 +250,10 @@ static void loc_launch(bool vec, unsigned blocks, const LocArgs& a, const int32_
                        hipStream_t st)
 {
     if (vec)
-        hipLaunchKernelGGL((locate_kernel<RP, true>), dim3(blocks), dim3(kLocBlock), 0, st, a, ctx);
+        hipLaunchKernelGGL((locate_kernel<RP, true>), dim3(blocks), dim3(kTileBlock), 0, st, a,
+                           ctx);
     else
-        hipLaunchKernelGGL((locate_kernel<RP, false>), dim3(blocks), dim3(kLocBlock), 0, st, a,
+        hipLaunchKernelGGL((locate_kernel<RP, false>), dim3(blocks), dim3(kTileBlock), 0, st, a,
                            ctx);
 }
 
@@ -367,30 +267,14 @@ int launch_locate(const int32_t* d_ctx, int k, int R, int split, const uint32_t*
                   uint32_t* d_unlocated, uint32_t* d_fix_counts, uint32_t* d_fixes, int fix_cap,
                   long long words, int n_stripes, uint32_t* d_err, hipStream_t st)
 {
-    if (k < 1 || k > kLocMaxK || R < 2 || R > kLocMaxChecks || n_stripes <= 0 || words < 0 ||
-        fix_cap < 0)
-        return -3;
-    const int N = k + R;
-    const size_t S = static_cast<size_t>(n_stripes);
-    if (hipMemsetAsync(d_located, 0, S * N * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(d_unlocated, 0, S * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(d_fix_counts, 0, S * sizeof(uint32_t), st) != hipSuccess)
-        return -2;
-    if (words == 0)
-        return 0;
-    const long long tiles = (words + kLocTile - 1) / kLocTile;
-    const long long blocks = tiles * n_stripes;
-    if (tiles > 0x7fffffffLL || blocks > 0x7fffffffLL)
-        return -3;
-    LocArgs a{locate_ctx_words(k, R), d_stripes, d_data, dss, drs, d_coded, css, crs, in,
-              d_located, d_unlocated, d_fix_counts, d_fixes, fix_cap, words, N, R, split,
-              static_cast<int>(tiles), d_err};
-    bool vec = reinterpret_cast<uintptr_t>(d_coded) % 16 == 0 && css % kLocCols == 0 &&
-               crs % kLocCols == 0;
-    if (split)
-        vec = vec && reinterpret_cast<uintptr_t>(d_data) % 16 == 0 && dss % kLocCols == 0 &&
-              drs % kLocCols == 0;
-    const unsigned nb = static_cast<unsigned>(blocks);
+    LocArgs a;
+    unsigned nb;
+    bool vec;
+    const int rc = loc_prepare(k, R, split, d_stripes, d_data, dss, drs, d_coded, css, crs, in,
+                               d_located, d_unlocated, d_fix_counts, d_fixes, fix_cap, words,
+                               n_stripes, d_err, st, &a, &nb, &vec);
+    if (rc <= 0)
+        return rc;
     switch (locate_rp(R)) {
     case 2: loc_launch<2>(vec, nb, a, d_ctx, st); break;
     case 4: loc_launch<4>(vec, nb, a, d_ctx, st); break;

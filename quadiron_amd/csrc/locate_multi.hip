@@ -34,32 +34,30 @@
 
 namespace qi {
 
-using namespace locrows;
-
 template <int RP, bool VEC>
-__global__ __launch_bounds__(kLocBlock) void locate_multi_kernel(LocArgs a, uint32_t* weights,
+__global__ __launch_bounds__(kTileBlock) void locate_multi_kernel(LocArgs a, uint32_t* weights,
                                                                  int t,
                                                                  const int32_t* __restrict__ ctx)
 {
     constexpr int TM = RP / 2;  // the largest t this form decodes
-    __shared__ uint32_t bitmap[kLocTile / 32];
+    __shared__ uint32_t bitmap[kTileElems / 32];
     __shared__ uint32_t sx[kLocMaxK + kLocMaxChecks];
     const int tid = static_cast<int>(threadIdx.x);
     const int tile = static_cast<int>(blockIdx.x) % a.tiles;  // tiles fastest
     const int s = static_cast<int>(blockIdx.x) / a.tiles;
     const long long sr = a.stripes ? a.stripes[s] : s;
-    const long long c0 = static_cast<long long>(tile) * kLocTile;
+    const long long c0 = static_cast<long long>(tile) * kTileElems;
     const int N = a.N;
     const int32_t* ids = ctx + static_cast<long long>(s) * a.ctx_stride;
 
-    int32_t acc[RP][kLocCols];
+    int32_t acc[RP][kTileCols];
     uint32_t nz = loc_syndromes<RP, VEC>(a, ids, sr, c0, tid, bitmap, acc);
     if (!__syncthreads_or(nz != 0))
         return;
 
     const uint32_t* xs = reinterpret_cast<const uint32_t*>(ids + N);
     const uint32_t* ws = reinterpret_cast<const uint32_t*>(ids + 2 * N);
-    for (int i = tid; i < N; i += kLocBlock)
+    for (int i = tid; i < N; i += kTileBlock)
         sx[i] = xs[i];
     __syncthreads();
 
@@ -71,11 +69,11 @@ __global__ __launch_bounds__(kLocBlock) void locate_multi_kernel(LocArgs a, uint
         for (int j = 0; j < RP; j++) {
             uint32_t v = 0;
 #pragma unroll
-            for (int ii = 0; ii < kLocCols; ii++)
+            for (int ii = 0; ii < kTileCols; ii++)
                 v = i == ii ? static_cast<uint32_t>(acc[j][ii]) : v;
             S[j] = v;
         }
-        const long long col = c0 + loc_rel<VEC>(tid, i);
+        const long long col = c0 + tile_rel<VEC>(tid, i);
         uint32_t C[TM + 1];
         const int L = lm_berlekamp_massey<RP, TM>(S, a.R, t, C);
         int pos[TM];
@@ -109,7 +107,8 @@ __global__ __launch_bounds__(kLocBlock) void locate_multi_kernel(LocArgs a, uint
                 if (e < L) {
                     const uint32_t E = lm_value<TM>(C, L, sx[pos[e]], sel);
                     bool data_row;
-                    const uint32_t y = loc_symbol(a, ids, sr, pos[e], col, &data_row);
+                    const uint32_t y =
+                        tile_symbol(a.rows(), a.in, sr, ids[pos[e]], col, &data_row);
                     found &= locate_fix(y, E, ws[pos[e]], data_row, &v[e]) && E != 0;
                 }
             }
@@ -147,10 +146,10 @@ static void locm_launch(bool vec, unsigned blocks, const LocArgs& a, uint32_t* w
                         const int32_t* ctx, hipStream_t st)
 {
     if (vec)
-        hipLaunchKernelGGL((locate_multi_kernel<RP, true>), dim3(blocks), dim3(kLocBlock), 0, st,
+        hipLaunchKernelGGL((locate_multi_kernel<RP, true>), dim3(blocks), dim3(kTileBlock), 0, st,
                            a, weights, t, ctx);
     else
-        hipLaunchKernelGGL((locate_multi_kernel<RP, false>), dim3(blocks), dim3(kLocBlock), 0, st,
+        hipLaunchKernelGGL((locate_multi_kernel<RP, false>), dim3(blocks), dim3(kTileBlock), 0, st,
                            a, weights, t, ctx);
 }
 
@@ -165,31 +164,21 @@ int launch_locate_multi(const int32_t* d_ctx, int k, int R, int t, int split,
                         int fix_cap, long long words, int n_stripes, uint32_t* d_err,
                         hipStream_t st)
 {
-    if (k < 1 || k > kLocMaxK || R < 2 || R > kLocMaxChecks || t < 1 || 2 * t > R ||
-        n_stripes <= 0 || words < 0 || fix_cap < 0)
+    if (t < 1 || 2 * t > R)
         return -3;
-    const int N = k + R;
-    const size_t S = static_cast<size_t>(n_stripes);
-    if (hipMemsetAsync(d_located, 0, S * N * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(d_unlocated, 0, S * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(d_weights, 0, S * kLocMaxErrors * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(d_fix_counts, 0, S * sizeof(uint32_t), st) != hipSuccess)
+    LocArgs a;
+    unsigned nb;
+    bool vec;
+    const int rc = loc_prepare(k, R, split, d_stripes, d_data, dss, drs, d_coded, css, crs, in,
+                               d_located, d_unlocated, d_fix_counts, d_fixes, fix_cap, words,
+                               n_stripes, d_err, st, &a, &nb, &vec);
+    if (rc < 0)
+        return rc;
+    if (hipMemsetAsync(d_weights, 0, static_cast<size_t>(n_stripes) * kLocMaxErrors *
+                                         sizeof(uint32_t), st) != hipSuccess)
         return -2;
-    if (words == 0)
+    if (rc == 0)
         return 0;
-    const long long tiles = (words + kLocTile - 1) / kLocTile;
-    const long long blocks = tiles * n_stripes;
-    if (tiles > 0x7fffffffLL || blocks > 0x7fffffffLL)
-        return -3;
-    LocArgs a{locate_ctx_words(k, R), d_stripes, d_data, dss, drs, d_coded, css, crs, in,
-              d_located, d_unlocated, d_fix_counts, d_fixes, fix_cap, words, N, R, split,
-              static_cast<int>(tiles), d_err};
-    bool vec = reinterpret_cast<uintptr_t>(d_coded) % 16 == 0 && css % kLocCols == 0 &&
-               crs % kLocCols == 0;
-    if (split)
-        vec = vec && reinterpret_cast<uintptr_t>(d_data) % 16 == 0 && dss % kLocCols == 0 &&
-              drs % kLocCols == 0;
-    const unsigned nb = static_cast<unsigned>(blocks);
     switch (locate_rp(R)) {
     case 2: locm_launch<2>(vec, nb, a, d_weights, t, d_ctx, st); break;
     case 4: locm_launch<4>(vec, nb, a, d_weights, t, d_ctx, st); break;

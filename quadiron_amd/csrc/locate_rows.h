@@ -1,11 +1,16 @@
-// locate_rows.h -- the row pass of the fragment locate as locate_multi.hip
-// (qi_gpu_locate_multi) uses it: a block owns one listed stripe and one tile
-// of kLocTile columns, walks the N listed rows kLocAhead at a time and leaves
-// the RP canonical syndromes of a lane's 8 columns in registers.  The layout,
-// the addressing, the mark bitmap and the range argument are locate.hip's and
-// are described at its top.  locate.hip keeps its own text of these steps:
-// built from this header its kernels took 4 .. 7 more VGPRs (RP 4, VEC: 7 -> 6
-// waves per SIMD), so the two copies live in namespaces of their own.
+// locate_rows.h -- what locate.hip (qi_gpu_locate) and locate_multi.hip
+// (qi_gpu_locate_multi) share beyond the tile primitives of row_tile.h: the
+// kernels' argument block LocArgs, the host side of a launch (loc_prepare),
+// and the row pass loc_syndromes, which walks the N listed rows kLocAhead at a
+// time and leaves the RP canonical syndromes of a lane's 8 columns in
+// registers.  The layout, the mark bitmap and the range argument are
+// described at the top of locate.hip.
+//
+// locate_multi_kernel calls loc_syndromes.  locate_kernel keeps its own text
+// of the same loop: built from the shared pass it takes 4 .. 7 more VGPRs
+// (gfx950: <2, true> 56 -> 60, <4, true> 71 -> 75 and 7 -> 6 waves per SIMD,
+// <8, true> 103 -> 110).  That cost belongs to the pass as a whole; the
+// primitives it is made of (row_tile.h) are shared by both at no cost.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,16 +18,11 @@
 #include "gf65537.h"
 #include "locate_math.h"
 #include "qi_internal.h"
+#include "row_tile.h"
 
 namespace qi {
-namespace locrows {
 
-constexpr int kLocBlock = 256;
-constexpr int kLocCols = 8;  // columns per lane: one 16-byte row piece
-constexpr int kLocTile = kLocBlock * kLocCols;
 constexpr int kLocAhead = 4;  // rows in flight per lane
-
-typedef uint32_t loc_u32x4 __attribute__((ext_vector_type(4)));
 
 struct LocArgs {
     long long ctx_stride;
@@ -40,83 +40,42 @@ struct LocArgs {
     long long words;
     int N, R, split, tiles;
     uint32_t* err;
+    __host__ __device__ FragRows rows() const { return {data, dss, drs, coded, css, crs, split}; }
 };
 
-// column of a lane's element i, relative to the tile
-template <bool VEC>
-__device__ __forceinline__ int loc_rel(int tid, int i)
+// The host side both launches share, launch_locate's arguments
+// (qi_internal.h): checks them, clears located, unlocated and fix_counts, and
+// fills the kernel's arguments, its block count and its form.  Returns 1 when
+// there is a kernel to launch, 0 when there is none (no columns), else the
+// launch's error
+inline int loc_prepare(int k, int R, int split, const uint32_t* d_stripes, const uint16_t* d_data,
+                       long long dss, long long drs, const uint16_t* d_coded, long long css,
+                       long long crs, const Oor& in, uint32_t* d_located, uint32_t* d_unlocated,
+                       uint32_t* d_fix_counts, uint32_t* d_fixes, int fix_cap, long long words,
+                       int n_stripes, uint32_t* d_err, hipStream_t st, LocArgs* a,
+                       unsigned* blocks, bool* vec)
 {
-    return VEC ? tid * kLocCols + i : i * kLocBlock + tid;
-}
-
-// a lane's 8 columns of `row` as 4 packed pairs; columns past the row's end
-// read 0.  full: the lane's 16-byte piece lies inside the row
-template <bool VEC>
-__device__ __forceinline__ void loc_load(const uint16_t* row, long long c0, int tid, bool full,
-                                         long long words, uint32_t (&w)[4])
-{
-    if (VEC && full) {
-        const loc_u32x4 v = *reinterpret_cast<const loc_u32x4*>(row + c0 + tid * kLocCols);
-        w[0] = v[0];
-        w[1] = v[1];
-        w[2] = v[2];
-        w[3] = v[3];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < kLocCols; i += 2) {
-        const long long ca = c0 + loc_rel<VEC>(tid, i), cb = c0 + loc_rel<VEC>(tid, i + 1);
-        const uint32_t lo = ca < words ? row[ca] : 0u;
-        const uint32_t hi = cb < words ? row[cb] : 0u;
-        w[i / 2] = lo | hi << 16;
-    }
-}
-
-// The marked columns of this tile in bucket bk, as a mask over the lane's 8
-// elements: the block scans the bucket's entries 256 at a time into an LDS
-// bitmap of the tile (a dense bucket costs entries / 256 steps).  Called by
-// the whole block (cnt is the same in every lane).
-template <bool VEC>
-__device__ __forceinline__ uint32_t loc_marks(uint32_t* bitmap, const Oor& in, long long bk,
-                                              uint32_t cnt, long long c0, long long words,
-                                              int tid, uint32_t* err)
-{
-    __syncthreads();  // the previous bitmap has been read
-    if (tid < kLocTile / 32)
-        bitmap[tid] = 0;
-    __syncthreads();
-    const uint32_t cap = static_cast<uint32_t>(in.cap);
-    if (cnt > cap && tid == 0)
-        atomicOr(err, kErrOorTruncated);
-    const uint32_t n = cnt < cap ? cnt : cap;
-    const uint32_t* e = in.entries + bk * in.cap;
-    for (uint32_t x = static_cast<uint32_t>(tid); x < n; x += kLocBlock) {
-        const long long col = e[x];
-        const long long rel = col - c0;
-        if (rel >= 0 && rel < kLocTile && col < words)
-            atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
-    }
-    __syncthreads();
-    uint32_t mk = 0;
-#pragma unroll
-    for (int i = 0; i < kLocCols; i++) {
-        const int rel = loc_rel<VEC>(tid, i);
-        mk |= (bitmap[rel >> 5] >> (rel & 31) & 1u) << i;
-    }
-    return mk;
-}
-
-// fragment id -> its row of stripe sr and its bucket (-1: a data row, none)
-__device__ __forceinline__ const uint16_t* loc_row(const LocArgs& a, long long sr, int id,
-                                                   long long* bk)
-{
-    if (id < a.split) {
-        *bk = -1;
-        return a.data + sr * a.dss + id * a.drs;
-    }
-    const int slot = id - a.split;
-    *bk = sr * a.in.slots + slot;
-    return a.coded + sr * a.css + slot * a.crs;
+    if (k < 1 || k > kLocMaxK || R < 2 || R > kLocMaxChecks || n_stripes <= 0 || words < 0 ||
+        fix_cap < 0)
+        return -3;
+    const int N = k + R;
+    const size_t S = static_cast<size_t>(n_stripes);
+    if (hipMemsetAsync(d_located, 0, S * N * sizeof(uint32_t), st) != hipSuccess ||
+        hipMemsetAsync(d_unlocated, 0, S * sizeof(uint32_t), st) != hipSuccess ||
+        hipMemsetAsync(d_fix_counts, 0, S * sizeof(uint32_t), st) != hipSuccess)
+        return -2;
+    if (words == 0)
+        return 0;
+    const long long tiles = (words + kTileElems - 1) / kTileElems;
+    const long long nb = tiles * n_stripes;
+    if (tiles > 0x7fffffffLL || nb > 0x7fffffffLL)
+        return -3;
+    *a = LocArgs{locate_ctx_words(k, R), d_stripes, d_data, dss, drs, d_coded, css, crs, in,
+                 d_located, d_unlocated, d_fix_counts, d_fixes, fix_cap, words, N, R, split,
+                 static_cast<int>(tiles), d_err};
+    *blocks = static_cast<unsigned>(nb);
+    *vec = locate_rows_vec(split, d_data, dss, drs, d_coded, css, crs);
+    return 1;
 }
 
 // The row pass: acc[j][i] becomes the canonical syndrome S_j of the lane's
@@ -126,16 +85,16 @@ template <int RP, bool VEC>
 __device__ __forceinline__ uint32_t loc_syndromes(const LocArgs& a, const int32_t* ids,
                                                   long long sr, long long c0, int tid,
                                                   uint32_t* bitmap,
-                                                  int32_t (&acc)[RP][kLocCols])
+                                                  int32_t (&acc)[RP][kTileCols])
 {
-    const bool full = c0 + tid * kLocCols + kLocCols <= a.words;
+    const bool full = c0 + tid * kTileCols + kTileCols <= a.words;
     const int N = a.N;
     const int32_t* coef = ids + 3 * N;
 
 #pragma unroll
     for (int j = 0; j < RP; j++)
 #pragma unroll
-        for (int i = 0; i < kLocCols; i++)
+        for (int i = 0; i < kTileCols; i++)
             acc[j][i] = 0;
 
     for (int i0 = 0; i0 < N; i0 += kLocAhead) {
@@ -145,8 +104,8 @@ __device__ __forceinline__ uint32_t loc_syndromes(const LocArgs& a, const int32_
 #pragma unroll
         for (int q = 0; q < kLocAhead; q++) {
             if (i0 + q < N) {
-                const uint16_t* row = loc_row(a, sr, ids[i0 + q], &bk[q]);
-                loc_load<VEC>(row, c0, tid, full, a.words, w[q]);
+                const uint16_t* row = frag_row(a.rows(), a.in.slots, sr, ids[i0 + q], &bk[q]);
+                tile_load<VEC>(row, c0, tid, full, a.words, w[q]);
                 cnt[q] = bk[q] >= 0 && a.in.counts ? a.in.counts[bk[q]] : 0u;
             }
         }
@@ -156,10 +115,10 @@ __device__ __forceinline__ uint32_t loc_syndromes(const LocArgs& a, const int32_
                 break;
             uint32_t mk = 0;
             if (cnt[q])
-                mk = loc_marks<VEC>(bitmap, a.in, bk[q], cnt[q], c0, a.words, tid, a.err);
+                mk = tile_marks<VEC>(bitmap, a.in, bk[q], cnt[q], c0, a.words, tid, a.err);
             const int32_t* c = coef + (i0 + q) * RP;
 #pragma unroll
-            for (int i = 0; i < kLocCols; i++) {
+            for (int i = 0; i < kTileCols; i++) {
                 const int32_t y = static_cast<int32_t>(w[q][i / 2] >> (i % 2 * 16) & 0xffffu);
                 int32_t yb = y > 32768 ? y - kQ : y;
                 if (mk)  // a marked symbol is 65536 = -1
@@ -174,7 +133,7 @@ __device__ __forceinline__ uint32_t loc_syndromes(const LocArgs& a, const int32_
     // canonical syndromes; nz: the lane's columns with one that is not 0
     uint32_t nz = 0;
 #pragma unroll
-    for (int i = 0; i < kLocCols; i++) {
+    for (int i = 0; i < kTileCols; i++) {
         uint32_t any = 0;
 #pragma unroll
         for (int j = 0; j < RP; j++) {
@@ -189,27 +148,4 @@ __device__ __forceinline__ uint32_t loc_syndromes(const LocArgs& a, const int32_
     return nz;
 }
 
-// the restored symbol of fragment position `pos` at column col: the stored
-// word, or 65536 when the column is in the row's bucket.  *data_row: whether
-// it is a systematic data row (no bucket)
-__device__ __forceinline__ uint32_t loc_symbol(const LocArgs& a, const int32_t* ids, long long sr,
-                                               int pos, long long col, bool* data_row)
-{
-    long long bkp;
-    const uint16_t* row = loc_row(a, sr, ids[pos], &bkp);
-    uint32_t y = row[col];
-    if (bkp >= 0 && a.in.counts) {
-        const uint32_t cap = static_cast<uint32_t>(a.in.cap);
-        const uint32_t cn = a.in.counts[bkp];
-        const uint32_t n = cn < cap ? cn : cap;
-        const uint32_t* e = a.in.entries + bkp * a.in.cap;
-        for (uint32_t t = 0; t < n; t++)
-            if (e[t] == static_cast<uint32_t>(col))
-                y = 65536u;
-    }
-    *data_row = bkp < 0;
-    return y;
-}
-
-}  // namespace locrows
 }  // namespace qi

@@ -265,6 +265,29 @@ int launch_repair_ctx(int k, int n, int code_len, uint32_t r, int sys, const Mat
 int fill_dot2_sections(const MatLayout& L, int32_t* d_ctx, long long ctx_stride, long long words,
                        int n_stripes, hipStream_t stream);
 
+// Whether rows of u16 at base + s * ss + t * rs take the streaming kernels'
+// 16-byte form (row_tile.h): the base and both strides multiples of 16 bytes.
+// The update asks it of its four regions; the locate and the fingerprint of
+// the regions a call can read:
+inline bool rows_vec(const void* base, long long ss, long long rs)
+{
+    return reinterpret_cast<uintptr_t>(base) % 16 == 0 && ss % 8 == 0 && rs % 8 == 0;
+}
+// the locate reads data rows only below a split
+inline bool locate_rows_vec(int split, const void* data, long long dss, long long drs,
+                            const void* coded, long long css, long long crs)
+{
+    return rows_vec(coded, css, crs) && (!split || rows_vec(data, dss, drs));
+}
+// the fingerprint may hold neither region (null), and its lanes' pieces start
+// at multiples of 8 absolute columns
+inline bool fingerprint_rows_vec(long long first_col, int split, const void* data, long long dss,
+                                 long long drs, const void* coded, long long css, long long crs)
+{
+    return first_col % 8 == 0 && (!coded || rows_vec(coded, css, crs)) &&
+           (!(split && data) || rows_vec(data, dss, drs));
+}
+
 // per-stripe delta-update contexts (ctx.hip; S x U data row ids, S x R coded
 // slots, d_slots null: slot j = j): update_ctx_words(U, R) words each, the
 // R x UP balanced coefficients c(slot, id) of update_coef.h, the slots and the

@@ -3,7 +3,7 @@
 // with the coefficients update_ctx_kernel (ctx.hip) left in the context.  A
 // streaming kernel: 2U + R rows in, R rows out, no matrix cores, no LDS image.
 //
-// A block owns one stripe, one tile of kUpdTile columns and a chunk of the
+// A block owns one stripe, one tile of kTileElems columns and a chunk of the
 // listed slots.  It loads the U old and U new rows of its columns once, keeps
 // d_u = balanced(new_u - old_u) in registers (8 columns per lane) and walks
 // its slots kUpdAhead coded rows at a time: the loads of a group are issued
@@ -11,13 +11,8 @@
 // is read by the lane that writes the output column, before it writes it:
 // d_out may be d_coded.
 //
-// Addressing is flat throughout, with 64-bit wave-uniform row offsets: rows
-// may lie anywhere, regions past the 31-bit buffer range and past 4 GiB
-// included.  VEC: every base and stride is a multiple of 16 bytes, a lane
-// moves its 8 adjacent columns as one 16-byte piece (the lane across the end
-// of the row, symbol by symbol).  Otherwise lane t takes the columns t, t +
-// 256, ... of the tile symbol by symbol, so that a wave's accesses stay
-// adjacent at any alignment.
+// The tile, its flat addressing in the two forms VEC (16-byte pieces) and
+// symbol by symbol, and the LDS bitmap of a row's marks are row_tile.h's.
 //
 // Ranges (gf65537.h): a data symbol is in [0, 65535], so new - old is in
 // [-65535, 65535] and its balanced representative d in [-32768, 32768]; the
@@ -34,12 +29,10 @@
 
 #include "gf65537.h"
 #include "qi_internal.h"
+#include "row_tile.h"
 
 namespace qi {
 
-constexpr int kUpdBlock = 256;
-constexpr int kUpdCols = 8;  // columns per lane: one 16-byte row piece
-constexpr int kUpdTile = kUpdBlock * kUpdCols;
 constexpr int kUpdAhead = 4;  // coded rows in flight per lane
 // Blocks wanted before the slots of a stripe tile stay in one block (4 per
 // CU of a 256-CU device), and the fewest slots a block takes per changed row
@@ -53,8 +46,6 @@ constexpr int kUpdSlotsPerRow = 4;
 #ifndef QI_UPD_NT_STORE
 #define QI_UPD_NT_STORE 0
 #endif
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct UpdArgs {
     long long ctx_stride;
@@ -73,109 +64,11 @@ struct UpdArgs {
     uint32_t* err;
 };
 
-// the protocol of qi_gpu_encode's buckets (kernels.hip record_oor): the count
-// goes on past cap, entries past it are dropped
-__device__ __forceinline__ void upd_record_oor(const Oor& o, int s, int slot, long long col)
-{
-    const long long bk = static_cast<long long>(s) * o.slots + slot;
-    const uint32_t e = atomicAdd(&o.counts[bk], 1u);
-    if (e < static_cast<uint32_t>(o.cap))
-        o.entries[bk * o.cap + e] = static_cast<uint32_t>(col);
-}
-
-// column of a lane's element i, relative to the tile
-template <bool VEC>
-__device__ __forceinline__ int upd_rel(int tid, int i)
-{
-    return VEC ? tid * kUpdCols + i : i * kUpdBlock + tid;
-}
-
-// a lane's 8 columns of the row `row` as 4 packed pairs; columns past the
-// row's end read 0.  full: the lane's 16-byte piece lies inside the row
-template <bool VEC>
-__device__ __forceinline__ void upd_load(const uint16_t* row, long long c0, int tid, bool full,
-                                         long long words, uint32_t (&w)[4])
-{
-    if (VEC && full) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(row + c0 + tid * kUpdCols);
-        w[0] = v[0];
-        w[1] = v[1];
-        w[2] = v[2];
-        w[3] = v[3];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < kUpdCols; i += 2) {
-        const long long ca = c0 + upd_rel<VEC>(tid, i), cb = c0 + upd_rel<VEC>(tid, i + 1);
-        const uint32_t lo = ca < words ? row[ca] : 0u;
-        const uint32_t hi = cb < words ? row[cb] : 0u;
-        w[i / 2] = lo | hi << 16;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void upd_store(uint16_t* row, long long c0, int tid, bool full,
-                                          long long words, const uint32_t (&y)[kUpdCols])
-{
-    if (VEC && full) {
-        u32x4 v;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            v[i] = y[2 * i] | y[2 * i + 1] << 16;
-        u32x4* p = reinterpret_cast<u32x4*>(row + c0 + tid * kUpdCols);
-        if (QI_UPD_NT_STORE)
-            __builtin_nontemporal_store(v, p);
-        else
-            *p = v;
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < kUpdCols; i++) {
-        const long long c = c0 + upd_rel<VEC>(tid, i);
-        if (c < words)
-            row[c] = static_cast<uint16_t>(y[i]);
-    }
-}
-
-// The marked columns of this tile in bucket (s, slot), as a mask over the
-// lane's 8 elements: the block scans the bucket's entries 256 at a time into
-// an LDS bitmap of the tile (a dense bucket costs entries / 256 steps, not
-// one per entry).  Called by the whole block (cnt is the same in every lane).
-template <bool VEC>
-__device__ __forceinline__ uint32_t upd_marks(uint32_t* bitmap, const Oor& in, int s, int slot,
-                                              uint32_t cnt, long long c0, long long words,
-                                              int tid, uint32_t* err)
-{
-    __syncthreads();  // the previous bitmap has been read
-    if (tid < kUpdTile / 32)
-        bitmap[tid] = 0;
-    __syncthreads();
-    const uint32_t cap = static_cast<uint32_t>(in.cap);
-    if (cnt > cap && tid == 0)
-        atomicOr(err, kErrOorTruncated);
-    const uint32_t n = cnt < cap ? cnt : cap;
-    const uint32_t* e = in.entries + (static_cast<long long>(s) * in.slots + slot) * in.cap;
-    for (uint32_t x = static_cast<uint32_t>(tid); x < n; x += kUpdBlock) {
-        const long long col = e[x];
-        const long long rel = col - c0;
-        if (rel >= 0 && rel < kUpdTile && col < words)
-            atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
-    }
-    __syncthreads();
-    uint32_t mk = 0;
-#pragma unroll
-    for (int i = 0; i < kUpdCols; i++) {
-        const int rel = upd_rel<VEC>(tid, i);
-        mk |= (bitmap[rel >> 5] >> (rel & 31) & 1u) << i;
-    }
-    return mk;
-}
-
 template <int UP, bool VEC>
-__global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
+__global__ __launch_bounds__(kTileBlock) void update_kernel(UpdArgs a,
                                                            const int32_t* __restrict__ ctx)
 {
-    __shared__ uint32_t bitmap[kUpdTile / 32];
+    __shared__ uint32_t bitmap[kTileElems / 32];
     const int tid = static_cast<int>(threadIdx.x);
     // block -> (stripe, slot chunk, tile), tiles fastest
     int b = static_cast<int>(blockIdx.x);
@@ -183,21 +76,21 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
     b /= a.tiles;
     const int ch = b % a.chunks;
     const int s = b / a.chunks;
-    const long long c0 = static_cast<long long>(tile) * kUpdTile;
-    const bool full = c0 + tid * kUpdCols + kUpdCols <= a.words;
+    const long long c0 = static_cast<long long>(tile) * kTileElems;
+    const bool full = c0 + tid * kTileCols + kTileCols <= a.words;
     const int32_t* coef = ctx + static_cast<long long>(s) * a.ctx_stride;
     const int32_t* slot_of = coef + static_cast<long long>(a.R) * UP;
 
     // d_u = balanced(new_u - old_u), in [-32768, 32768]
-    int32_t d[UP][kUpdCols];
+    int32_t d[UP][kTileCols];
 #pragma unroll
     for (int u = 0; u < UP; u++) {
         if (u < a.U) {
             uint32_t wo[4], wn[4];
-            upd_load<VEC>(a.olds + s * a.old_ss + u * a.old_rs, c0, tid, full, a.words, wo);
-            upd_load<VEC>(a.news + s * a.new_ss + u * a.new_rs, c0, tid, full, a.words, wn);
+            tile_load<VEC>(a.olds + s * a.old_ss + u * a.old_rs, c0, tid, full, a.words, wo);
+            tile_load<VEC>(a.news + s * a.new_ss + u * a.new_rs, c0, tid, full, a.words, wn);
 #pragma unroll
-            for (int i = 0; i < kUpdCols; i++) {
+            for (int i = 0; i < kTileCols; i++) {
                 const int32_t o = static_cast<int32_t>(wo[i / 2] >> (i % 2 * 16) & 0xffffu);
                 const int32_t n = static_cast<int32_t>(wn[i / 2] >> (i % 2 * 16) & 0xffffu);
                 const int32_t x = n - o;
@@ -205,7 +98,7 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < kUpdCols; i++)
+            for (int i = 0; i < kTileCols; i++)
                 d[u][i] = 0;
         }
     }
@@ -222,7 +115,7 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
         for (int q = 0; q < kUpdAhead; q++) {
             if (j + q < j1) {
                 slot[q] = a.by_pos ? j + q : slot_of[j + q];
-                upd_load<VEC>(coded + slot[q] * a.crs, c0, tid, full, a.words, w[q]);
+                tile_load<VEC>(coded + slot[q] * a.crs, c0, tid, full, a.words, w[q]);
                 cnt[q] = a.in.counts
                              ? a.in.counts[static_cast<long long>(s) * a.in.slots + slot[q]]
                              : 0u;
@@ -234,12 +127,14 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
                 break;
             uint32_t mk = 0;
             if (cnt[q])
-                mk = upd_marks<VEC>(bitmap, a.in, s, slot[q], cnt[q], c0, a.words, tid, a.err);
+                mk = tile_marks<VEC>(bitmap, a.in,
+                                     static_cast<long long>(s) * a.in.slots + slot[q], cnt[q], c0,
+                                     a.words, tid, a.err);
             const int32_t* c = coef + static_cast<long long>(j + q) * UP;
-            uint32_t y[kUpdCols];
+            uint32_t y[kTileCols];
             uint32_t bad = 0;
 #pragma unroll
-            for (int i = 0; i < kUpdCols; i++) {
+            for (int i = 0; i < kTileCols; i++) {
                 // a marked symbol is 65536 (stored as 0)
                 int32_t acc = mk >> i & 1u
                                   ? 65536
@@ -253,13 +148,14 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdArgs a,
                 bad |= static_cast<uint32_t>(v == 65536) << i;
                 y[i] = static_cast<uint32_t>(v) & 0xffffu;
             }
-            upd_store<VEC>(out + slot[q] * a.ors, c0, tid, full, a.words, y);
+            tile_store<VEC, QI_UPD_NT_STORE != 0>(out + slot[q] * a.ors, c0, tid, full, a.words,
+                                                  y);
             // (a column past the row's end computes 0: never recorded)
             if (bad && a.outm.counts) {
 #pragma unroll
-                for (int i = 0; i < kUpdCols; i++)
+                for (int i = 0; i < kTileCols; i++)
                     if (bad >> i & 1u)
-                        upd_record_oor(a.outm, s, slot[q], c0 + upd_rel<VEC>(tid, i));
+                        tile_record_oor(a.outm, s, slot[q], c0 + tile_rel<VEC>(tid, i));
             }
         }
     }
@@ -270,27 +166,15 @@ std::string update_kernel_name(int UP, bool vec)
     return "update_kernel<" + std::to_string(UP) + ", " + (vec ? "true" : "false") + ">";
 }
 
-// whether the update's rows take the 16-byte form: every base and every
-// stride a multiple of 16 bytes
-bool update_rows_vec(const void* const (&base)[4], const long long (&strides)[8])
-{
-    for (const void* p : base)
-        if (reinterpret_cast<uintptr_t>(p) % 16)
-            return false;
-    for (long long st : strides)
-        if (st % kUpdCols)
-            return false;
-    return true;
-}
-
 template <int UP>
 static void upd_launch(bool vec, unsigned blocks, const UpdArgs& a, const int32_t* ctx,
                        hipStream_t st)
 {
     if (vec)
-        hipLaunchKernelGGL((update_kernel<UP, true>), dim3(blocks), dim3(kUpdBlock), 0, st, a, ctx);
+        hipLaunchKernelGGL((update_kernel<UP, true>), dim3(blocks), dim3(kTileBlock), 0, st, a,
+                           ctx);
     else
-        hipLaunchKernelGGL((update_kernel<UP, false>), dim3(blocks), dim3(kUpdBlock), 0, st, a,
+        hipLaunchKernelGGL((update_kernel<UP, false>), dim3(blocks), dim3(kTileBlock), 0, st, a,
                            ctx);
 }
 
@@ -308,7 +192,7 @@ int launch_update(const int32_t* d_ctx, long long ctx_stride, int U, int UP, int
 {
     if (U < 1 || U > UP || R < 1 || n_stripes <= 0 || words <= 0)
         return -3;
-    const long long tiles = (words + kUpdTile - 1) / kUpdTile;
+    const long long tiles = (words + kTileElems - 1) / kTileElems;
     const long long st_tiles = tiles * n_stripes;
     // slots per block: all of them while that leaves enough blocks, else
     // halved down to kUpdSlotsPerRow per changed row (never below 4)
@@ -323,9 +207,8 @@ int launch_update(const int32_t* d_ctx, long long ctx_stride, int U, int UP, int
     UpdArgs a{ctx_stride, d_old, old_ss, old_rs, d_new, new_ss, new_rs, d_coded, css, crs,
               d_out, oss, ors, in, outm, words, R, U, static_cast<int>(tiles), chunk, chunks,
               by_pos, d_err};
-    const void* const base[4] = {d_old, d_new, d_coded, d_out};
-    const long long strides[8] = {old_ss, old_rs, new_ss, new_rs, css, crs, oss, ors};
-    const bool vec = update_rows_vec(base, strides);
+    const bool vec = rows_vec(d_old, old_ss, old_rs) && rows_vec(d_new, new_ss, new_rs) &&
+                     rows_vec(d_coded, css, crs) && rows_vec(d_out, oss, ors);
     const unsigned nb = static_cast<unsigned>(blocks);
     switch (UP) {
     case 1: upd_launch<1>(vec, nb, a, d_ctx, st); break;
