@@ -196,6 +196,35 @@ class RsFnt {
     // most 256 MiB of rows)
     bool update_supported(size_t n_rows, size_t n_held, size_t block_size_bytes) const;
 
+    // Partial repair (qi_gpu_partial): the share of a repair of `targets`
+    // from the n_data helper fragments `ids` (decode's id space, distinct)
+    // that the holder of the fragments `held_ids` (each one of `ids`,
+    // distinct) can form.  held_bufs[h] is fragment held_ids[h] and
+    // held_props[h] its marks (a systematic data row has none).  With acc:
+    // out_bufs[j] / out_props[j] hold the partial rows and marks so far and
+    // are updated in place on the device (chain and tree aggregation); else
+    // the sum starts from 0.  out_props[j] become the marks of the new
+    // partial rows (ascending, counts exact) -- a partial row of a data-row
+    // target may carry marks too; only the complete sum is free of them.
+    // Summed over any partition of `ids`, in any order, the rows and marks
+    // are those of repair_blocks_vertical, at any n_data.  Only the held and
+    // the partial rows are staged.  A bucket overflow on the device is
+    // retried once with the exact capacity, from the acc rows as they were.
+    // Throws std::invalid_argument where partial_supported() is false, or an
+    // id, a held id or a target is out of range, repeated or misplaced.
+    void partial_repair_blocks_vertical(const std::vector<int>& ids,
+                                        const std::vector<int>& held_ids,
+                                        std::vector<uint8_t*>& held_bufs,
+                                        std::vector<Properties>& held_props,
+                                        const std::vector<int>& targets, bool acc,
+                                        std::vector<uint8_t*>& out_bufs,
+                                        std::vector<Properties>& out_props,
+                                        size_t block_size_bytes);
+    // 1 <= n_held <= n_data, 1 <= n_targets <= min(8, n_parities), and a
+    // block whose n_held + n_targets rows fit the single-chunk device staging
+    // (at most 256 MiB of rows)
+    bool partial_supported(size_t n_held, size_t n_targets, size_t block_size_bytes) const;
+
     // Fused verify (scrubbing): check the present fragments against each
     // other on the device without rebuilding a row (qi_gpu_verify).  The
     // basis is the first n_data present fragments, chosen as

@@ -573,6 +573,89 @@ int qi_gpu_fingerprint(qi_plan* plan, const uint16_t* d_ids /*[S][N] fragment id
 const char* qi_gpu_fingerprint_kernels(const qi_plan* plan, int n_rows, int n_keys,
                                        long long words);
 
+/* ---- Partial repair: the share of a repair that one holder of some of the k
+ * helper fragments can form.  qi_gpu_repair rebuilds a fragment as a sum over
+ * all k helpers, which must all be in one device's memory, and is limited to
+ * k <= 256.  The sum is linear: a node can form it over just the rows it
+ * holds, and the partial sums of different nodes add modulo 65537
+ * (partial-parallel repair: a helper ships n_targets partial rows instead of
+ * its held rows, and aggregators add as they forward).  With n_held = k and
+ * no accumulator it is a one-pass streaming repair for any k.
+ *
+ * For one stripe:
+ *   ids[0 .. k)     the k helper fragments of the repair: distinct, below
+ *                   k + m, in the decode's id space;
+ *   targets[0 .. R) the fragments to rebuild: distinct, below k + m, none of
+ *                   them in ids;
+ *   held[0 .. H)    *positions* into ids (each < k, distinct): the helpers
+ *                   whose rows this call has.
+ * With x_l = r^ids[l], y_t = r^targets[t] and A(x) = prod_{l<k} (x - x_l) the
+ * coefficient is
+ *   c(t, i) = A(y_t) / ((y_t - x_i) A'(x_i)),
+ * entry (t, i) of the matrix of qi_gpu_repair.  The call computes, per column,
+ *   out_t = canon(acc_t + sum_{h<H} c(t, held[h]) y_h),   in [0, 65536],
+ * where y_h is the restored symbol of held row h -- 65536 where the column is
+ * in that row's bucket; a systematic data row (id < k) carries no marks and
+ * its bucket is not read -- and acc_t the restored symbol of accumulator row t
+ * (its bucket is always read), or 0 when d_acc is NULL.  A result of 65536 is
+ * stored as 0 and recorded in the out bucket of slot t by the encode's bucket
+ * protocol (the count goes on past out_cap).  This holds for data-row targets
+ * too: only the *complete* sum of a valid stripe is guaranteed storable there,
+ * a partial is not.  Summed over any partition of the k positions, in any
+ * order, the result is bit for bit what qi_gpu_repair writes, rows and marks
+ * both.
+ *
+ * Supported on every plan qi_plan_create accepts (any k, both code types), for
+ * 1 <= n_held <= k and 1 <= n_targets <= min(QI_PARTIAL_MAX_TARGETS, m), the
+ * same counts for every stripe of a call; ids, held and targets may differ per
+ * stripe.  Counts out of range return -1 (qi_gpu_partial_ctx_bytes: 0,
+ * qi_gpu_partial_kernels: "") and launch nothing.
+ *
+ * Rows are positional, as in qi_gpu_decode_packed: row h of stripe s is d_rows
+ * + s * rss + h * rrs, its bucket slot h of n_held; a node passes only what it
+ * holds.  Accumulator and output row t are slot t of n_targets.  Any positive
+ * strides with a unit inner stride, at any 2-byte alignment; rows and strides
+ * that are all multiples of 16 bytes move as 16-byte pieces per lane.
+ *
+ * In place: d_out == d_acc with equal strides is allowed and is the expected
+ * use (chain aggregation: every column is read before it is written, by the
+ * lane that writes it); any other overlap is undefined.  The acc and out
+ * bucket sets must be distinct.  Clear the out counts first
+ * (qi_gpu_oor_clear); NULL out counts skip the recording.
+ *
+ * Errors: an id not below k + m, a repeated id, a position not below k or
+ * repeated, a target not below k + m, a repeated target, or a target that is
+ * also a helper raise bit 2 of qi_gpu_take_error when the context is built;
+ * the offending coefficients enter as 0, and the call stays inside the
+ * caller's rows.  An in or acc bucket over its capacity raises bit 1; a bucket
+ * within its capacity is restored in full however dense.
+ *
+ * The context holds, per stripe, the n_targets x n_held balanced coefficients,
+ * the targets and the held rows' ids; it does not depend on the width.  It
+ * costs O((n_held + n_targets) k) field operations per stripe (only the held
+ * rows' Lagrange weights are needed), where the k x R matrix of
+ * qi_gpu_repair_ctx costs O(k^2).  Everything is asynchronous on `stream`: no
+ * host tables, no blocking copy. */
+#define QI_PARTIAL_MAX_TARGETS 8
+size_t qi_gpu_partial_ctx_bytes(const qi_plan* plan, int n_held, int n_targets, int n_stripes);
+int qi_gpu_partial_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][k]*/,
+                       const uint16_t* d_held /*[S][H] positions into ids*/,
+                       const uint16_t* d_targets /*[S][R]*/, int n_held, int n_targets,
+                       int n_stripes, void* d_ctx, void* stream);
+int qi_gpu_partial(qi_plan* plan, const void* d_ctx, int n_held, int n_targets,
+                   const uint16_t* d_rows, long long rss, long long rrs,
+                   const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                   const uint16_t* d_acc, long long ass, long long ars,
+                   const uint32_t* d_acc_counts, const uint32_t* d_acc_entries, int acc_cap,
+                   uint16_t* d_out, long long oss, long long ors,
+                   uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                   long long words, int n_stripes, void* stream);
+/* Names of the kernels such a partial repair launches (rows and strides at
+ * multiples of 16 bytes), as "partial=<context kernel> + <kernel>"; "" for
+ * counts out of range.  Per calling thread, valid until its next call. */
+const char* qi_gpu_partial_kernels(const qi_plan* plan, int n_held, int n_targets,
+                                   long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -687,6 +770,27 @@ int qi_fec_fingerprint_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, con
 int qi_fec_update_blocks(qi_fec* f, const int* ids, int n_rows, uint8_t** old_rows,
                          uint8_t** new_rows, uint8_t** parities, uint32_t* oor,
                          uint32_t* oor_count, uint32_t oor_cap, size_t block_bytes);
+
+/* Partial repair (RsFnt::partial_repair_blocks_vertical, qi_gpu_partial):
+ * the share of the repair of targets[0 .. n_targets) from the k helper
+ * fragments ids[0 .. k) (decode's id space) that the holder of the fragments
+ * held_ids[0 .. n_held) can form; each held id is one of ids (it is mapped to
+ * its position here).  rows[h] is fragment held_ids[h] (block_bytes), its
+ * marks oor[h * oor_cap ..] with the count oor_count[h] (oor_count NULL: no
+ * marks; a systematic data row has none).  acc != 0: out[j], out_oor and
+ * out_count hold the partial rows and marks so far and are added to; else the
+ * sum starts from 0.  out[j] receives partial row j, its marks ascending in
+ * out_oor[j * out_cap ..] with the exact count in out_count[j] (a count above
+ * out_cap: only out_cap entries were written, and the list is not a valid acc
+ * for another call).  Returns 1 done, -1 error (an id, a held id or a target
+ * out of range, repeated or misplaced), -2 shape not supported (n_held
+ * outside 1 .. k, n_targets outside 1 .. min(8, m), or n_held + n_targets
+ * rows wider than the single-chunk staging). */
+int qi_fec_partial_repair_blocks(qi_fec* f, const int* ids, const int* held_ids, int n_held,
+                                 uint8_t** rows, const uint32_t* oor, const uint32_t* oor_count,
+                                 uint32_t oor_cap, const int* targets, int n_targets, int acc,
+                                 uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
+                                 uint32_t out_cap, size_t block_bytes);
 
 /* Stream API (encode_streams_vertical / decode_streams_vertical,
  * src/fec_base.h:463-542, 898-1048) over caller memory: each fragment is a

@@ -81,6 +81,11 @@ def _declare(lib):
         "qi_gpu_fingerprint": (I, [V, V, I, V, I, LL, V, LL, LL, V, LL, LL, V, V, I, V, V,
                                    LL, I, V]),
         "qi_gpu_fingerprint_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_partial_ctx_bytes": (SZ, [V, I, I, I]),
+        "qi_gpu_partial_ctx": (I, [V, V, V, V, I, I, I, V, V]),
+        "qi_gpu_partial": (I, [V, V, I, I, V, LL, LL, V, V, I, V, LL, LL, V, V, I,
+                               V, LL, LL, V, V, I, LL, I, V]),
+        "qi_gpu_partial_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -96,6 +101,8 @@ def _declare(lib):
         "qi_fec_locate_multi_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, I, V, I, SZ]),
         "qi_fec_fingerprint_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, V, I, V, SZ]),
         "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
+        "qi_fec_partial_repair_blocks": (I, [V, V, V, I, c_u8pp, V, V, U32, V, I, I, c_u8pp,
+                                             V, V, U32, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
                                       c_u8pp]),
@@ -539,6 +546,84 @@ class Plan:
             raise RuntimeError(f"qi_gpu_update failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    PARTIAL_MAX_TARGETS = 8  # QI_PARTIAL_MAX_TARGETS
+
+    def partial_kernels(self, n_held, n_targets, words):
+        """'partial=<context kernel> + <kernel>' a partial repair of n_targets
+        fragments from n_held held rows launches (qi_gpu_partial_kernels); ''
+        for counts out of range."""
+        return lib().qi_gpu_partial_kernels(self.h, n_held, n_targets, words).decode()
+
+    def partial_ctx_bytes(self, n_held, n_targets, n_stripes):
+        """0 when n_held is outside 1 .. k or n_targets outside
+        1 .. min(8, m)."""
+        return lib().qi_gpu_partial_ctx_bytes(self.h, n_held, n_targets, n_stripes)
+
+    def _partial_need(self, H, R, S):
+        need = self.partial_ctx_bytes(H, R, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"partial repair of {R} targets from {H} held rows is not "
+                             f"supported (1 <= H <= k, 1 <= R <= min(8, m))")
+        return need
+
+    def partial_ctx(self, ids, held, targets, ctx, stream=None):
+        """ids: int16 tensor [S, k] (the k helper fragments of the repair);
+        held: int16 tensor [S, H], positions into ids (the helpers whose rows
+        the call has); targets: int16 tensor [S, R] (the fragments to
+        rebuild)."""
+        import torch
+        if (ids.dim() != 2 or held.dim() != 2 or targets.dim() != 2 or
+                not ids.shape[0] == held.shape[0] == targets.shape[0] or
+                ids.shape[1] != self.k):
+            raise ValueError("ids: expected [S, k], held: [S, H], targets: [S, R]")
+        S, H = held.shape
+        R = targets.shape[1]
+        need = self._partial_need(H, R, S)
+        for t, name, n in ((ids, "ids", S * self.k), (held, "held", S * H),
+                           (targets, "targets", S * R)):
+            _flat(t, name, n, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        rc = lib().qi_gpu_partial_ctx(
+            self.h, ids.data_ptr(), held.data_ptr(), targets.data_ptr(), H, R, S,
+            ctx.data_ptr(), self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_partial_ctx failed: {rc}")
+
+    def partial(self, ctx, rows, out, acc=None, counts=None, entries=None, cap=0,
+                acc_counts=None, acc_entries=None, acc_cap=0, out_counts=None,
+                out_entries=None, out_cap=0, stream=None, check=True):
+        """rows: [S, H, P], row h the helper at position held[s][h] of the
+        context, with its OOR bucket in slot h of counts / entries (slots =
+        H); acc: [S, R, P] partial rows to start from (None: 0) with their
+        buckets acc_counts / acc_entries (slots = R); out: [S, R, P], row t =
+        target t, may be acc itself; its marks go to out_counts / out_entries
+        (slots = R, cleared by the caller, distinct from the acc buckets).
+        Returns the sticky error flags when check."""
+        import torch
+        _rows(rows, "rows")
+        S, H, P = rows.shape
+        _rows(out, "out", None, S)
+        R = out.shape[1]
+        if acc is not None:
+            _rows(acc, "acc", R, S)
+        if out.shape[2] != P or (acc is not None and acc.shape[2] != P):
+            raise ValueError("rows, acc and out differ in width")
+        need = self._partial_need(H, R, S)
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, H)
+        _oor(acc_counts, acc_entries, acc_cap, S, R)
+        _oor(out_counts, out_entries, out_cap, S, R)
+        rc = lib().qi_gpu_partial(
+            self.h, ctx.data_ptr(), H, R,
+            rows.data_ptr(), rows.stride(0), rows.stride(1),
+            _ptr(counts), _ptr(entries), int(cap),
+            *_row_args(acc), _ptr(acc_counts), _ptr(acc_entries), int(acc_cap),
+            out.data_ptr(), out.stride(0), out.stride(1),
+            _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_partial failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     LOCATE_MAX_CHECKS = 8  # QI_LOCATE_MAX_CHECKS
 
     def locate_kernels(self, n_checks, words):
@@ -970,6 +1055,64 @@ class Fec:
             raise ValueError("update_blocks: shape not supported")
         if rc != 1:
             raise RuntimeError(f"qi_fec_update_blocks failed: {rc}")
+
+    def partial_repair_blocks(self, ids, held_ids, rows, oor, counts, targets, acc=None,
+                              out_cap=64):
+        """Partial repair (qi_fec_partial_repair_blocks): the share of the
+        repair of `targets` from the k helper fragments `ids` that the holder
+        of the fragments `held_ids` (each one of ids) can form.  rows[h]:
+        fragment held_ids[h] (uint8 rows); oor (len(held_ids), cap) uint32 and
+        counts uint32: their marks by position h (None: no marks).  acc: the
+        (rows, out_oor, out_counts) another call returned, to add to (None:
+        start from 0).  Returns (rows, out_oor, out_counts): the len(targets)
+        partial rows, their ascending marks (len(targets), cap') and exact
+        counts; summed over any partition of ids they are the rebuilt
+        fragments.  Raises ValueError for an unsupported shape (no or more
+        than k held rows, more than min(8, m) targets, a block wider than one
+        staging chunk)."""
+        import numpy as np
+        idv = np.ascontiguousarray(ids, np.int32)
+        hv = np.ascontiguousarray(held_ids, np.int32)
+        tg = np.ascontiguousarray(targets, np.int32)
+        if len(idv) != self.k or len(rows) != len(hv):
+            raise ValueError("partial_repair_blocks: k ids and one row per held id")
+        if len(hv) == 0:
+            raise ValueError("partial_repair_blocks: shape not supported")
+        B = len(rows[0])
+        if oor is not None:
+            oor = np.ascontiguousarray(oor, np.uint32).reshape(len(hv), -1)
+            counts = np.ascontiguousarray(counts, np.uint32)
+        if acc is not None:
+            a_rows, a_oor, a_cnt = acc
+            if len(a_rows) != len(tg) or int(np.max(a_cnt, initial=0)) > a_oor.shape[1]:
+                raise ValueError("partial_repair_blocks: acc needs one row per target "
+                                 "and complete mark lists")
+            out_cap = max(out_cap, a_oor.shape[1])
+        while True:
+            outs = [np.zeros(B, np.uint8) for _ in range(len(tg))]
+            o_oor = np.zeros((len(tg), out_cap), np.uint32)
+            o_cnt = np.zeros(len(tg), np.uint32)
+            if acc is not None:
+                for j in range(len(tg)):
+                    outs[j][:] = a_rows[j]
+                o_oor[:, :a_oor.shape[1]] = a_oor
+                o_cnt[:] = a_cnt
+            rc = lib().qi_fec_partial_repair_blocks(
+                self.h, idv.ctypes.data_as(C.c_void_p), hv.ctypes.data_as(C.c_void_p),
+                len(hv), ptr_array(list(rows)),
+                oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                oor.shape[1] if oor is not None else 0,
+                tg.ctypes.data_as(C.c_void_p), len(tg), int(acc is not None),
+                ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
+                o_cnt.ctypes.data_as(C.c_void_p), out_cap, B)
+            if rc == -2:
+                raise ValueError("partial_repair_blocks: shape not supported")
+            if rc != 1:
+                raise RuntimeError(f"qi_fec_partial_repair_blocks failed: {rc}")
+            if o_cnt.max(initial=0) <= out_cap:
+                return outs, o_oor, o_cnt
+            out_cap = int(o_cnt.max())   # the list did not fit: once more
 
     def close(self):
         if self.h:

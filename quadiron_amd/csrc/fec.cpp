@@ -964,6 +964,140 @@ void RsFnt::update_blocks_vertical(const std::vector<int>& ids, std::vector<uint
     }
 }
 
+// ---- partial repair (single chunk; qi_gpu_partial_ctx, then the partial in
+// place on the staged acc rows) ----
+bool RsFnt::partial_supported(size_t n_held, size_t n_targets, size_t block_size_bytes) const
+{
+    const size_t words = block_size_bytes / word_size;
+    if (n_held < 1 || n_held > n_data || n_targets < 1 ||
+        n_targets > std::min<size_t>(QI_PARTIAL_MAX_TARGETS, n_parities))
+        return false;
+    if (words == 0 || words > chunk_bytes(buf_size) / 2)
+        return false;
+    // the held rows and the partial rows, back to back
+    return (n_held + n_targets) * pad_words(words) * 2 <= (size_t{256} << 20);
+}
+
+void RsFnt::partial_repair_blocks_vertical(const std::vector<int>& ids,
+                                           const std::vector<int>& held_ids,
+                                           std::vector<uint8_t*>& held_bufs,
+                                           std::vector<Properties>& held_props,
+                                           const std::vector<int>& targets, bool acc,
+                                           std::vector<uint8_t*>& out_bufs,
+                                           std::vector<Properties>& out_props,
+                                           size_t block_size_bytes)
+{
+    // validate; held fragment ids -> positions into ids
+    const stage::FragMap map = frag_map(*this);
+    const size_t k = n_data, H = held_ids.size(), R = targets.size();
+    if (!partial_supported(H, R, block_size_bytes))
+        throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: unsupported shape");
+    if (ids.size() != k || held_bufs.size() < H || held_props.size() < H || out_bufs.size() < R ||
+        (acc && out_props.size() < R))
+        throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: buffers");
+    std::vector<int> where(code_len, -1);  // fragment id -> position in ids, -2: a target
+    for (size_t i = 0; i < k; i++) {
+        if (ids[i] < 0 || ids[i] >= static_cast<int>(code_len) || where[ids[i]] != -1)
+            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad id");
+        where[ids[i]] = static_cast<int>(i);
+    }
+    for (size_t j = 0; j < R; j++) {
+        if (targets[j] < 0 || targets[j] >= static_cast<int>(code_len) ||
+            where[targets[j]] != -1 || !out_bufs[j])
+            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad target");
+        where[targets[j]] = -2;
+    }
+    std::vector<uint16_t> hids(ids.begin(), ids.end());
+    std::vector<char> taken(k, 0);
+    for (size_t hh = 0; hh < H; hh++) {
+        const int f = held_ids[hh];
+        if (f < 0 || f >= static_cast<int>(code_len) || where[f] < 0 || taken[where[f]] ||
+            !held_bufs[hh])
+            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad held id");
+        taken[where[f]] = 1;
+        hids.push_back(static_cast<uint16_t>(where[f]));
+    }
+    hids.insert(hids.end(), targets.begin(), targets.end());
+    const size_t words = block_size_bytes / word_size;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // stage: the H held rows, the R partial rows, the buckets of both, the
+    // output counts
+    std::vector<const Properties*> hmarked(H, nullptr), amarked(R, nullptr);
+    for (size_t hh = 0; hh < H; hh++) {
+        if (map.slot(static_cast<unsigned>(held_ids[hh])).is_data)
+            continue;
+        held_props[hh].sort();
+        hmarked[hh] = &held_props[hh];
+    }
+    for (size_t j = 0; acc && j < R; j++) {
+        out_props[j].sort();
+        amarked[j] = &out_props[j];
+    }
+    const stage::PackedMarks pm = stage::pack_marks(hmarked, 0, words);
+    const stage::PackedMarks am = stage::pack_marks(amarked, 0, words);
+    const size_t P = pad_words(words);
+    const auto off = stage::layout(
+        {H * 4, pm.entries.size() * 4, R * 4, am.entries.size() * 4, R * 4});
+    const size_t ctx_bytes =
+        qi_gpu_partial_ctx_bytes(pl, static_cast<int>(H), static_cast<int>(R), 1);
+    reserve(h.in, (H + R) * P * 2);
+    reserve(h.counts, off[5]);
+    reserve(h.ids, hids.size() * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint16_t* drows = static_cast<uint16_t*>(h.in.p);
+    uint16_t* dacc = drows + H * P;
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
+    uint32_t* dacnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
+    uint32_t* daent = reinterpret_cast<uint32_t*>(dcb + off[3]);
+    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[4]);
+    const auto upload_acc = [&] {
+        for (size_t j = 0; acc && j < R; j++)
+            h2d(dacc + j * P, out_bufs[j], words * 2, s);
+    };
+    for (size_t hh = 0; hh < H; hh++)
+        h2d(drows + hh * P, held_bufs[hh], words * 2, s);
+    upload_acc();
+    upload_marks(pm, dcnt, dent, s);
+    upload_marks(am, dacnt, daent, s);
+    h2d(h.ids.p, hids.data(), hids.size() * 2, s);
+    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
+    check_rc(qi_gpu_partial_ctx(pl, dids, dids + k, dids + k + H, static_cast<int>(H),
+                                static_cast<int>(R), 1, h.ctx.p, s),
+             "partial context");
+    // launch in place; a second attempt starts from the acc rows as they were
+    const long long Pl = static_cast<long long>(P);
+    std::vector<uint32_t> ocnt(R);
+    const size_t ocap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, R * c * 4);
+            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+            check_rc(qi_gpu_partial(pl, h.ctx.p, static_cast<int>(H), static_cast<int>(R), drows,
+                                    0, Pl, dcnt, dent, static_cast<int>(pm.cap),
+                                    acc ? dacc : nullptr, 0, Pl, dacnt, daent,
+                                    static_cast<int>(am.cap), dacc, 0, Pl, docnt,
+                                    static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                    static_cast<long long>(words), 1, s),
+                     "partial");
+        },
+        [&] { return read_max(ocnt, docnt, s); }, upload_acc);
+    // collect
+    std::vector<uint32_t> ent(R * ocap);
+    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
+    for (size_t j = 0; j < R; j++)
+        d2h(out_bufs[j], dacc + j * P, words * 2, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: partial repair failed (bad ids or OOR bucket capacity)");
+    out_props.assign(R, Properties());
+    for (size_t j = 0; j < R; j++)
+        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
+}
+
 namespace {
 
 // One stage of the pipelined stream API: pinned host staging, device
@@ -1946,6 +2080,37 @@ int qi_fec_update_blocks(qi_fec* h, const int* ids, int n_rows, uint8_t** old_ro
             }
             oor_count[j] = c;
         }
+        return 1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_partial_repair_blocks(qi_fec* h, const int* ids, const int* held_ids, int n_held,
+                                 uint8_t** rows, const uint32_t* oor, const uint32_t* oor_count,
+                                 uint32_t cap, const int* targets, int n_targets, int acc,
+                                 uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
+                                 uint32_t out_cap, size_t block_bytes)
+{
+    try {
+        if (!h || !ids || !held_ids || !rows || !targets || !out || !out_count || n_held < 0 ||
+            n_targets < 0 || (out_cap > 0 && !out_oor))
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.partial_supported(static_cast<size_t>(n_held), static_cast<size_t>(n_targets),
+                                 block_bytes))
+            return -2;
+        std::vector<int> iv(ids, ids + f.n_data), hv(held_ids, held_ids + n_held),
+            tv(targets, targets + n_targets);
+        std::vector<uint8_t*> rv(rows, rows + n_held), ov(out, out + n_targets);
+        // (oor_count null: no marks)
+        std::vector<qi::Properties> hp(static_cast<size_t>(n_held)),
+            op(static_cast<size_t>(n_targets));
+        qi::fec::stage::props_from_flat(hp, oor, nullptr, oor_count, cap);
+        if (acc)
+            qi::fec::stage::props_from_flat(op, out_oor, nullptr, out_count, out_cap);
+        f.partial_repair_blocks_vertical(iv, hv, rv, hp, tv, acc != 0, ov, op, block_bytes);
+        qi::fec::stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
         return 1;
     } catch (...) {
         return -1;

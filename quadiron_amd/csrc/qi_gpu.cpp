@@ -12,6 +12,7 @@
 #include "gf65537.h"
 #include "locate_math.h"
 #include "locate_multi_math.h"
+#include "partial_math.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
 #include "update_coef.h"
@@ -673,6 +674,77 @@ const char* qi_gpu_fingerprint_kernels(const qi_plan* p, int N, int F, long long
     if (!fingerprint_ok(p, N, F, words))
         return "";
     names = "fingerprint=" + fingerprint_kernel_names(F, true, words);
+    return names.c_str();
+}
+
+// ---- partial repair (any k): partial_ctx_kernel leaves the H x RP Lagrange
+// weights of the held rows per stripe, partial_kernel streams the H rows past
+// the R accumulators (partial.hip, partial_math.h) ----
+static bool partial_ok(const qi_plan* p, int H, int R)
+{
+    return H >= 1 && H <= p->k && R >= 1 &&
+           R <= std::min(QI_PARTIAL_MAX_TARGETS, p->code_len - p->k);
+}
+
+size_t qi_gpu_partial_ctx_bytes(const qi_plan* p, int H, int R, int n_stripes)
+{
+    if (!p || n_stripes < 0 || !partial_ok(p, H, R))
+        return 0;
+    return static_cast<size_t>(partial_ctx_words(H, R)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_partial_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_held,
+                       const uint16_t* d_targets, int H, int R, int n_stripes, void* d_ctx,
+                       void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0)
+        return -1;
+    if (!partial_ok(p, H, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids || !d_held || !d_targets)
+        return -1;
+    return launch_partial_ctx(p->k, p->code_len, p->r, d_ids, d_held, d_targets, H, R, n_stripes,
+                              static_cast<int32_t*>(d_ctx), p->d_err, st(stream));
+}
+
+int qi_gpu_partial(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t* d_rows,
+                   long long rss, long long rrs, const uint32_t* d_in_counts,
+                   const uint32_t* d_in_entries, int in_cap, const uint16_t* d_acc, long long ass,
+                   long long ars, const uint32_t* d_acc_counts, const uint32_t* d_acc_entries,
+                   int acc_cap, uint16_t* d_out, long long oss, long long ors,
+                   uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap, long long words,
+                   int n_stripes, void* stream)
+{
+    if (!p || !d_ctx || !d_rows || !d_out || n_stripes < 0 || words < 0 || in_cap < 0 ||
+        acc_cap < 0 || out_cap < 0 || (d_in_counts && in_cap > 0 && !d_in_entries) ||
+        (d_acc_counts && acc_cap > 0 && !d_acc_entries) ||
+        (d_out_counts && out_cap > 0 && !d_out_entries))
+        return -1;
+    if (!partial_ok(p, H, R))
+        return -1;
+    if (n_stripes == 0 || words == 0)
+        return 0;
+    const Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries), H,
+                 in_cap};
+    // (no acc rows: no acc marks)
+    const Oor accm{d_acc ? const_cast<uint32_t*>(d_acc_counts) : nullptr,
+                   const_cast<uint32_t*>(d_acc_entries), R, acc_cap};
+    const Oor outm{d_out_counts, d_out_entries, R, out_cap};
+    return launch_partial(static_cast<const int32_t*>(d_ctx), H, R, p->sys ? p->k : 0, d_rows, rss,
+                          rrs, in, d_acc, ass, ars, accm, d_out, oss, ors, outm, words, n_stripes,
+                          p->d_err, st(stream));
+}
+
+const char* qi_gpu_partial_kernels(const qi_plan* p, int H, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || words <= 0 || !partial_ok(p, H, R))
+        return "";
+    names = "partial=" + partial_ctx_kernel_name() + " + " +
+            partial_kernel_name(partial_rp(R), true);
     return names.c_str();
 }
 

@@ -359,6 +359,29 @@ int launch_fingerprint(const uint16_t* d_ids, int N, const uint32_t* keys, int F
 // its kernels (rows and strides at multiples of 16 bytes when vec)
 std::string fingerprint_kernel_names(int F, bool vec, long long words);
 
+// per-stripe partial-repair contexts (partial.hip, partial_math.h; S x k helper
+// ids, S x H positions into them, S x R targets): partial_ctx_words(H, R) words
+// each, the H x RP balanced coefficients c(t, held[h]), the targets and the
+// held rows' ids.  An id or target not below code_len or repeated, a target
+// that is a helper, a position not below k or repeated raise kErrBadIds; the
+// offending coefficients are 0
+int launch_partial_ctx(int k, int code_len, uint32_t r, const uint16_t* d_ids,
+                       const uint16_t* d_held, const uint16_t* d_targets, int H, int R, int S,
+                       int32_t* d_ctx, uint32_t* err, hipStream_t st);
+// the partial repair itself: out_t = acc_t + sum_h c(t, held[h]) row_h, rows
+// and their buckets `in` by position h, the acc rows' and output rows' buckets
+// accm / outm by target t (counts null: none); d_acc null: start from 0.  The
+// held rows whose id is below `split` are data rows: their bucket is not read
+int launch_partial(const int32_t* d_ctx, int H, int R, int split, const uint16_t* d_rows,
+                   long long rss, long long rrs, const Oor& in, const uint16_t* d_acc,
+                   long long ass, long long ars, const Oor& accm, uint16_t* d_out, long long oss,
+                   long long ors, const Oor& outm, long long words, int n_stripes,
+                   uint32_t* d_err, hipStream_t st);
+// their kernels, by the target count rounded up (partial_rp) and by whether
+// every base and stride is a multiple of 16 bytes
+std::string partial_ctx_kernel_name();
+std::string partial_kernel_name(int RP, bool vec);
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.
