@@ -225,6 +225,64 @@ class RsFnt {
     // (at most 256 MiB of rows)
     bool partial_supported(size_t n_held, size_t n_targets, size_t block_size_bytes) const;
 
+    // Syndrome share (qi_gpu_syndrome): the share of the n_checks syndrome
+    // rows of the n_data + n_checks listed fragments `listed_ids` (decode's
+    // id space, distinct) that the holder of the fragments `held_ids` (each
+    // one of `listed_ids`, distinct) can form.  held_bufs, held_props, acc,
+    // out_bufs and out_props as in partial_repair_blocks_vertical, with
+    // n_checks rows out.  Summed over any partition of `listed_ids`, in any
+    // order, the rows and marks are the syndromes of the stripe: all 0,
+    // without marks, when every listed fragment is intact.  Any n_data.
+    // Throws std::invalid_argument where syndrome_supported() is false, or an
+    // id or a held id is out of range, repeated or not listed.
+    void syndrome_blocks_vertical(const std::vector<int>& listed_ids,
+                                  const std::vector<int>& held_ids,
+                                  std::vector<uint8_t*>& held_bufs,
+                                  std::vector<Properties>& held_props, int n_checks, bool acc,
+                                  std::vector<uint8_t*>& out_bufs,
+                                  std::vector<Properties>& out_props, size_t block_size_bytes);
+    // 1 <= n_checks <= min(8, n_parities), 1 <= n_held <= n_data + n_checks,
+    // and a block whose n_held + n_checks rows fit the single-chunk device
+    // staging (at most 256 MiB of rows)
+    bool syndrome_supported(size_t n_held, size_t n_checks, size_t block_size_bytes) const;
+
+    // The coordinator's decision (qi_gpu_syndrome_locate) over the complete
+    // sums syn_bufs[j] / syn_props[j], j < n_checks = listed_ids.size() -
+    // n_data: locate_multi_blocks_vertical's result at any n_data, from the
+    // syndrome rows alone.  0 <= max_errors <= n_checks / 2; 0 only detects
+    // (every bad column is unlocated).  result.located is by fragment id (-1:
+    // not listed); result.fixes[e].symbol is the *error* of that fragment in
+    // that column, in 1 .. 65536: the true symbol is (y - error) mod 65537
+    // (apply_deltas).  A fix list longer than the first attempt's capacity is
+    // run again with the exact one.  Throws std::invalid_argument for counts
+    // out of range or ids out of range or repeated.
+    void locate_syndromes(const std::vector<int>& listed_ids, std::vector<uint8_t*>& syn_bufs,
+                          std::vector<Properties>& syn_props, int max_errors,
+                          LocateResult& result, size_t block_size_bytes);
+
+    // The holder's step, without the device: applies the deltas of
+    // locate_syndromes that name one of `fragment_ids` to bufs[h] / props[h]
+    // (a systematic data row has no marks) and skips the others.  Returns the
+    // number applied, or -1 with nothing touched when a data row would have
+    // to hold 65536 or a mark list would grow beyond max_marks.
+    long long apply_deltas(const std::vector<int>& fragment_ids, std::vector<uint8_t*>& bufs,
+                           std::vector<Properties>& props, const std::vector<LocateFix>& deltas,
+                           size_t block_size_bytes,
+                           size_t max_marks = static_cast<size_t>(-1)) const;
+
+    // Scrub at any n_data: locate_multi_blocks_vertical's listing, result,
+    // `correct`, max_marks and return values, composed of the three calls
+    // above with every listed fragment held here.  0 <= max_errors <= 4 (0:
+    // detection only, with at least n_data + 1 fragments listed).  Returns 0
+    // when fewer than n_data + max(1, 2 max_errors) fragments are listed.
+    // Throws std::length_error (nothing patched) when apply_deltas refuses.
+    int scrub_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                              std::vector<uint8_t*>& parities_bufs,
+                              std::vector<Properties>& parities_props,
+                              std::vector<int>& missing_idxs, LocateResult& result,
+                              int max_errors, bool correct, size_t block_size_bytes,
+                              size_t max_marks = static_cast<size_t>(-1));
+
     // Fused verify (scrubbing): check the present fragments against each
     // other on the device without rebuilding a row (qi_gpu_verify).  The
     // basis is the first n_data present fragments, chosen as

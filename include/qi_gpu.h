@@ -656,6 +656,111 @@ int qi_gpu_partial(qi_plan* plan, const void* d_ctx, int n_held, int n_targets,
 const char* qi_gpu_partial_kernels(const qi_plan* plan, int n_held, int n_targets,
                                    long long words);
 
+/* ---- Syndrome shares: locate bad fragments at any k from per-node sums.
+ * For one stripe, ids[0 .. N) are the N = k + R listed fragments (decode's id
+ * space, distinct, below k + m), R = n_checks, 1 <= R <=
+ * min(QI_SYNDROME_MAX_CHECKS, m).  With x_i = r^ids[i] and the dual weights
+ * w_i = prod_{l != i, l < N} (x_i - x_l), the syndromes of the received
+ * symbols y_i of a column are S_j = sum_i y_i x_i^j / w_i, j < R: all 0 for a
+ * codeword, and linear in the rows.
+ *
+ * Helper side (qi_gpu_syndrome_ctx, qi_gpu_syndrome).  held[0 .. H) are
+ * distinct positions into ids, 1 <= H <= N: the listed fragments whose rows
+ * this call has.  Per column it computes
+ *   out_j = canon(acc_j + sum_{h<H} (x_held[h]^j / w_held[h]) y_h),  j < R,
+ * in [0, 65536].  Every other convention is qi_gpu_partial's: rows are
+ * positional (row h of stripe s at d_rows + s * rss + h * rrs, its bucket
+ * slot h of n_held), accumulator and output row j are slot j of n_checks; y_h
+ * is the restored symbol (65536 where the column is in the row's bucket; a
+ * systematic data row, id < k, carries no marks and its bucket is not read);
+ * d_acc NULL starts from 0; a result of 65536 is stored as 0 and recorded in
+ * the out bucket of slot j (the count goes on past out_cap; clear the out
+ * counts first, NULL out counts skip the recording); d_out == d_acc with equal
+ * strides is allowed and is the expected use, with distinct acc and out
+ * bucket sets.  Any positive strides at any 2-byte alignment; rows and
+ * strides that are all multiples of 16 bytes move as 16-byte pieces per lane.
+ * The shares of any partition of the N positions, added in any order, are bit
+ * for bit the result of one call with H = N, rows and marks both: the R
+ * syndrome rows.  For an intact stripe those are all 0 with empty buckets.
+ *
+ * The share context is a partial repair's (n_checks in the place of
+ * n_targets): per stripe the n_held x n_checks balanced coefficients and the
+ * held rows' ids; the row pass is the partial repair's kernel.  It costs
+ * O(n_held N) field operations per stripe, one inversion per held row.
+ * Everything is asynchronous on `stream`: no host tables, no blocking copy.
+ *
+ * Errors: an id not below k + m or repeated, a position not below N or
+ * repeated raise bit 2 of qi_gpu_take_error when the context is built; that
+ * row's coefficients are 0 and the call stays inside the caller's rows.  An in
+ * or acc bucket over its capacity raises bit 1.  n_checks outside 1 .. min(8,
+ * m) or n_held outside 1 .. N return -1 (qi_gpu_syndrome_ctx_bytes: 0,
+ * qi_gpu_syndrome_kernels: "") and launch nothing. */
+#define QI_SYNDROME_MAX_CHECKS 8
+#define QI_SYNDROME_MAX_ERRORS 4
+size_t qi_gpu_syndrome_ctx_bytes(const qi_plan* plan, int n_held, int n_checks, int n_stripes);
+int qi_gpu_syndrome_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][k + R]*/,
+                        const uint16_t* d_held /*[S][H] positions into ids*/, int n_held,
+                        int n_checks, int n_stripes, void* d_ctx, void* stream);
+int qi_gpu_syndrome(qi_plan* plan, const void* d_ctx, int n_held, int n_checks,
+                    const uint16_t* d_rows, long long rss, long long rrs,
+                    const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                    const uint16_t* d_acc, long long ass, long long ars,
+                    const uint32_t* d_acc_counts, const uint32_t* d_acc_entries, int acc_cap,
+                    uint16_t* d_out, long long oss, long long ors,
+                    uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                    long long words, int n_stripes, void* stream);
+/* "syndrome=<context kernel> + <partial kernel form>" (rows and strides at
+ * multiples of 16 bytes); "" for counts out of range.  Per calling thread,
+ * valid until its next call. */
+const char* qi_gpu_syndrome_kernels(const qi_plan* plan, int n_held, int n_checks,
+                                    long long words);
+
+/* Coordinator side (qi_gpu_syndrome_locate_ctx, qi_gpu_syndrome_locate): the
+ * decision of qi_gpu_locate_multi from the R summed syndrome rows alone, at
+ * any k.  d_syn row j of stripe s is at d_syn + s * sss + j * srs, its marks
+ * (a syndrome of 65536) in bucket slot j of n_checks (d_counts NULL: none; a
+ * bucket over its capacity raises bit 1).  max_errors = t, 0 <= t <=
+ * floor(R / 2) <= QI_SYNDROME_MAX_ERRORS.  A column whose R syndromes are all
+ * 0 is clean.  Any other column is located when 1 <= nu <= t listed fragments
+ * explain all R syndromes with errors that are not 0, else unlocated: b <= t
+ * bad fragments are located exactly, t < b <= R - t bad fragments are always
+ * unlocated, more may be miscorrected.  t = 0 is detection only: every column
+ * that is not clean counts as unlocated (a verify at any k).
+ *
+ * Outputs, initialised by the call, as qi_gpu_locate_multi's: d_located[s * N
+ * + p] the located columns fragment position p takes part in, d_unlocated[s],
+ * d_weights[s * QI_SYNDROME_MAX_ERRORS + nu - 1] the columns located with nu
+ * fragments, d_fix_counts[s] the fix entries of stripe s (the count goes on
+ * past fix_cap; entries past it are dropped), d_fixes[(s * fix_cap + e) * 3
+ * ..] = {column, list position p, error e}.  The nu entries of a column are
+ * adjacent.  No row is written.
+ *
+ * The fix is a delta: e = E w_p in [1, 65536] is what fragment p is off by,
+ * and the true symbol is (y_p - e) mod 65537 -- the coordinator does not hold
+ * y_p.  Unlike qi_gpu_locate_multi, which drops a column whose corrected
+ * symbol cannot be stored (65536 on a systematic data row), this call cannot
+ * tell: the holder decides when it applies the fix (qi_fec_apply_deltas).
+ *
+ * The context holds per stripe the N ids, points and weights, 12 N bytes; it
+ * costs O(N^2) field operations per stripe, spread over ceil(N / 256) blocks.
+ * Ids not below k + m or repeated raise bit 2 when it is built.  n_checks
+ * outside 1 .. min(8, m) or max_errors outside 0 .. n_checks / 2 return -1
+ * (qi_gpu_syndrome_locate_ctx_bytes: 0, qi_gpu_syndrome_locate_kernels: "")
+ * and launch nothing. */
+size_t qi_gpu_syndrome_locate_ctx_bytes(const qi_plan* plan, int n_checks, int n_stripes);
+int qi_gpu_syndrome_locate_ctx(qi_plan* plan, const uint16_t* d_ids /*[S][k + R]*/, int n_checks,
+                               int n_stripes, void* d_ctx, void* stream);
+int qi_gpu_syndrome_locate(qi_plan* plan, const void* d_ctx, int n_checks, int max_errors,
+                           const uint16_t* d_syn, long long sss, long long srs,
+                           const uint32_t* d_counts, const uint32_t* d_entries, int cap,
+                           uint32_t* d_located /*[S][k + R]*/, uint32_t* d_unlocated /*[S]*/,
+                           uint32_t* d_weights /*[S][QI_SYNDROME_MAX_ERRORS]*/,
+                           uint32_t* d_fix_counts /*[S]*/, uint32_t* d_fixes /*[S][fix_cap][3]*/,
+                           int fix_cap, long long words, int n_stripes, void* stream);
+/* "syndrome_locate=<context kernel> + <kernel>"; "" when out of range. */
+const char* qi_gpu_syndrome_locate_kernels(const qi_plan* plan, int n_checks, int max_errors,
+                                           long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 
@@ -791,6 +896,65 @@ int qi_fec_partial_repair_blocks(qi_fec* f, const int* ids, const int* held_ids,
                                  uint32_t oor_cap, const int* targets, int n_targets, int acc,
                                  uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
                                  uint32_t out_cap, size_t block_bytes);
+
+/* Syndrome share (RsFnt::syndrome_blocks_vertical, qi_gpu_syndrome): the
+ * share of the n_checks syndrome rows of the n_listed = k + n_checks listed
+ * fragments listed_ids (decode's id space) that the holder of the fragments
+ * held_ids[0 .. n_held) can form; each held id is one of listed_ids.  rows,
+ * oor, oor_count, oor_cap, acc, out, out_oor, out_count and out_cap as for
+ * qi_fec_partial_repair_blocks, with n_checks rows out.  Any k.  Returns 1
+ * done, -1 error (an id or a held id out of range, repeated or not listed),
+ * -2 shape not supported (n_checks outside 1 .. min(8, m), n_listed != k +
+ * n_checks, n_held outside 1 .. n_listed, or n_held + n_checks rows wider
+ * than the single-chunk staging). */
+int qi_fec_syndrome_blocks(qi_fec* f, const int* listed_ids, int n_listed, const int* held_ids,
+                           int n_held, uint8_t** rows, const uint32_t* oor,
+                           const uint32_t* oor_count, uint32_t oor_cap, int n_checks, int acc,
+                           uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
+                           uint32_t out_cap, size_t block_bytes);
+
+/* The coordinator's decision over summed syndrome rows
+ * (RsFnt::locate_syndromes, qi_gpu_syndrome_locate): rows[j], j < n_checks =
+ * n_listed - k, are the complete sums of qi_fec_syndrome_blocks over all
+ * n_listed fragments, with their marks (oor_count NULL: none).  0 <=
+ * max_errors <= n_checks / 2.  result: k + m + 1 + max_errors values, per
+ * fragment id the located columns it takes part in (-1: not listed), the
+ * unlocated columns, then the columns located with 1 .. max_errors fragments.
+ * fixes: up to fix_cap triples {column, fragment id, error e in 1 .. 65536},
+ * the fixes of a column adjacent; *n_fixes their exact number (above fix_cap:
+ * only fix_cap were written; call again with that capacity).  The true symbol
+ * is (y - e) mod 65537 (qi_fec_apply_deltas).  Returns 1 done, -1 error, -2
+ * shape not supported (n_checks outside 1 .. min(8, m), max_errors out of
+ * range, or a block wider than the single-chunk staging). */
+int qi_fec_locate_syndromes(qi_fec* f, const int* listed_ids, int n_listed, uint8_t** rows,
+                            const uint32_t* oor, const uint32_t* oor_count, uint32_t oor_cap,
+                            int max_errors, long long* result, uint32_t* fixes, uint32_t fix_cap,
+                            uint32_t* n_fixes, size_t block_bytes);
+
+/* The holder's step (RsFnt::apply_deltas; no device): for every fix {column,
+ * fragment id, e} that names one of fragment_ids[0 .. n_rows), the restored
+ * symbol y of rows[h] at that column (65536 where oor lists it) becomes (y -
+ * e) mod 65537, and the ascending mark list of the row follows (oor[h *
+ * oor_cap ..], oor_count[h]; a systematic data row has none).  Fixes for
+ * other fragments are skipped.  The whole patch is refused, and nothing
+ * touched, when a data row would have to hold 65536 or a mark list would grow
+ * beyond oor_cap (oor_count NULL: beyond 0).  Returns the number of fixes
+ * applied (0 included), -1 error, -3 refused. */
+int qi_fec_apply_deltas(qi_fec* f, const int* fragment_ids, int n_rows, uint8_t** rows,
+                        uint32_t* oor, uint32_t* oor_count, uint32_t oor_cap,
+                        const uint32_t* fixes, uint32_t n_fixes, size_t block_bytes);
+
+/* Scrub at any k (RsFnt::scrub_blocks_vertical): qi_fec_locate_multi_blocks
+ * without its k <= 256 limit, composed of the three calls above with every
+ * listed fragment held here.  The first min(present, k + 8) present fragments
+ * are listed, R = listed - k; 0 <= max_errors <= 4, max_errors = 0 only
+ * detects.  result, `correct` and the return values as
+ * qi_fec_locate_multi_blocks (0: fewer than k + max(1, 2 max_errors)
+ * fragments listed); a patch that qi_fec_apply_deltas refuses returns -1 with
+ * nothing patched.  -2: a block wider than the single-chunk staging. */
+int qi_fec_scrub_blocks(qi_fec* f, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                        uint32_t* oor_count, uint32_t oor_cap, const int* missing,
+                        int max_errors, long long* result, int correct, size_t block_bytes);
 
 /* Stream API (encode_streams_vertical / decode_streams_vertical,
  * src/fec_base.h:463-542, 898-1048) over caller memory: each fragment is a

@@ -86,6 +86,16 @@ def _declare(lib):
         "qi_gpu_partial": (I, [V, V, I, I, V, LL, LL, V, V, I, V, LL, LL, V, V, I,
                                V, LL, LL, V, V, I, LL, I, V]),
         "qi_gpu_partial_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_syndrome_ctx_bytes": (SZ, [V, I, I, I]),
+        "qi_gpu_syndrome_ctx": (I, [V, V, V, I, I, I, V, V]),
+        "qi_gpu_syndrome": (I, [V, V, I, I, V, LL, LL, V, V, I, V, LL, LL, V, V, I,
+                                V, LL, LL, V, V, I, LL, I, V]),
+        "qi_gpu_syndrome_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_syndrome_locate_ctx_bytes": (SZ, [V, I, I]),
+        "qi_gpu_syndrome_locate_ctx": (I, [V, V, I, I, V, V]),
+        "qi_gpu_syndrome_locate": (I, [V, V, I, I, V, LL, LL, V, V, I, V, V, V, V, V, I,
+                                       LL, I, V]),
+        "qi_gpu_syndrome_locate_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -103,6 +113,11 @@ def _declare(lib):
         "qi_fec_update_blocks": (I, [V, V, I, c_u8pp, c_u8pp, c_u8pp, V, V, U32, SZ]),
         "qi_fec_partial_repair_blocks": (I, [V, V, V, I, c_u8pp, V, V, U32, V, I, I, c_u8pp,
                                              V, V, U32, SZ]),
+        "qi_fec_syndrome_blocks": (I, [V, V, I, V, I, c_u8pp, V, V, U32, I, I, c_u8pp, V, V,
+                                       U32, SZ]),
+        "qi_fec_locate_syndromes": (I, [V, V, I, c_u8pp, V, V, U32, I, V, V, U32, V, SZ]),
+        "qi_fec_apply_deltas": (I, [V, V, I, c_u8pp, V, V, U32, V, U32, SZ]),
+        "qi_fec_scrub_blocks": (I, [V, c_u8pp, c_u8pp, V, V, U32, V, I, V, I, SZ]),
         "qi_fec_encode_streams": (I, [V, c_u8pp, SZ, c_u8pp, V, V, U32]),
         "qi_fec_decode_streams": (I, [V, c_u8pp, c_u8pp, SZ, V, V, U32,
                                       c_u8pp]),
@@ -624,6 +639,149 @@ class Plan:
             raise RuntimeError(f"qi_gpu_partial failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
+    SYNDROME_MAX_CHECKS = 8  # QI_SYNDROME_MAX_CHECKS
+    SYNDROME_MAX_ERRORS = 4  # QI_SYNDROME_MAX_ERRORS
+
+    def syndrome_kernels(self, n_held, n_checks, words):
+        """'syndrome=<context kernel> + <partial kernel form>' a syndrome share
+        of n_held rows with n_checks syndromes launches
+        (qi_gpu_syndrome_kernels); '' for counts out of range."""
+        return lib().qi_gpu_syndrome_kernels(self.h, n_held, n_checks, words).decode()
+
+    def syndrome_ctx_bytes(self, n_held, n_checks, n_stripes):
+        """0 when n_checks is outside 1 .. min(8, m) or n_held outside
+        1 .. k + n_checks."""
+        return lib().qi_gpu_syndrome_ctx_bytes(self.h, n_held, n_checks, n_stripes)
+
+    def _syndrome_need(self, H, R, S):
+        need = self.syndrome_ctx_bytes(H, R, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"a syndrome share of {H} held rows with {R} checks is not "
+                             f"supported (1 <= R <= min(8, m), 1 <= H <= k + R)")
+        return need
+
+    def syndrome_ctx(self, ids, held, ctx, stream=None):
+        """ids: int16 tensor [S, k + R] (the listed fragments; R = n_checks
+        follows from the shape); held: int16 tensor [S, H], positions into ids
+        (the listed fragments whose rows the call has)."""
+        import torch
+        if ids.dim() != 2 or held.dim() != 2 or ids.shape[0] != held.shape[0]:
+            raise ValueError("ids: expected [S, k + R], held: [S, H]")
+        S, H = held.shape
+        R = ids.shape[1] - self.k
+        need = self._syndrome_need(H, R, S)
+        _flat(ids, "ids", S * (self.k + R), (torch.int16, torch.uint16))
+        _flat(held, "held", S * H, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        rc = lib().qi_gpu_syndrome_ctx(self.h, ids.data_ptr(), held.data_ptr(), H, R, S,
+                                       ctx.data_ptr(), self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_syndrome_ctx failed: {rc}")
+
+    def syndrome(self, ctx, rows, out, acc=None, counts=None, entries=None, cap=0,
+                 acc_counts=None, acc_entries=None, acc_cap=0, out_counts=None,
+                 out_entries=None, out_cap=0, stream=None, check=True):
+        """Syndrome share (qi_gpu_syndrome).  Arguments as partial: rows
+        [S, H, P], row h the listed fragment at position held[s][h]; acc and
+        out [S, R, P], row j = syndrome j, out may be acc itself.  Returns the
+        sticky error flags when check."""
+        import torch
+        _rows(rows, "rows")
+        S, H, P = rows.shape
+        _rows(out, "out", None, S)
+        R = out.shape[1]
+        if acc is not None:
+            _rows(acc, "acc", R, S)
+        if out.shape[2] != P or (acc is not None and acc.shape[2] != P):
+            raise ValueError("rows, acc and out differ in width")
+        need = self._syndrome_need(H, R, S)
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, H)
+        _oor(acc_counts, acc_entries, acc_cap, S, R)
+        _oor(out_counts, out_entries, out_cap, S, R)
+        rc = lib().qi_gpu_syndrome(
+            self.h, ctx.data_ptr(), H, R,
+            rows.data_ptr(), rows.stride(0), rows.stride(1),
+            _ptr(counts), _ptr(entries), int(cap),
+            *_row_args(acc), _ptr(acc_counts), _ptr(acc_entries), int(acc_cap),
+            out.data_ptr(), out.stride(0), out.stride(1),
+            _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_syndrome failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
+    def syndrome_locate_kernels(self, n_checks, max_errors, words):
+        """'syndrome_locate=<context kernel> + <kernel>'
+        (qi_gpu_syndrome_locate_kernels); '' when n_checks is outside
+        1 .. min(8, m) or max_errors outside 0 .. n_checks // 2."""
+        return lib().qi_gpu_syndrome_locate_kernels(self.h, n_checks, max_errors,
+                                                    words).decode()
+
+    def syndrome_locate_ctx_bytes(self, n_checks, n_stripes):
+        """12 (k + n_checks) bytes per stripe; 0 when n_checks is outside
+        1 .. min(8, m)."""
+        return lib().qi_gpu_syndrome_locate_ctx_bytes(self.h, n_checks, n_stripes)
+
+    def _syndrome_locate_need(self, R, S):
+        need = self.syndrome_locate_ctx_bytes(R, S)
+        if need == 0 and S > 0:
+            raise ValueError(f"a syndrome locate with {R} checks is not supported "
+                             f"(1 <= R <= min(8, m))")
+        return need
+
+    def syndrome_locate_ctx(self, ids, ctx, stream=None):
+        """ids: int16 tensor [S, k + R], the listed fragments; R = n_checks
+        follows from the shape."""
+        import torch
+        if ids.dim() != 2:
+            raise ValueError("ids: expected [S, k + R]")
+        S, N = ids.shape
+        R = N - self.k
+        need = self._syndrome_locate_need(R, S)
+        _flat(ids, "ids", S * N, (torch.int16, torch.uint16))
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        rc = lib().qi_gpu_syndrome_locate_ctx(self.h, ids.data_ptr(), R, S, ctx.data_ptr(),
+                                              self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_syndrome_locate_ctx failed: {rc}")
+
+    def syndrome_locate(self, ctx, max_errors, syn, located, unlocated, weights, fix_counts,
+                        fixes=None, fix_cap=0, counts=None, entries=None, cap=0, stream=None,
+                        check=True):
+        """The decision over summed syndrome rows (qi_gpu_syndrome_locate).
+        syn: [S, R, P], row j = syndrome j, with its marks in slot j of counts
+        / entries (slots = R).  0 <= max_errors <= R // 2.  Outputs, int32,
+        initialised by the call: located [S, k + R], unlocated [S], weights
+        [S, 4], fix_counts [S], fixes [S, fix_cap, 3] of {column, position,
+        error e}: the true symbol is (y - e) mod 65537.  Returns the sticky
+        error flags when check."""
+        import torch
+        _rows(syn, "syn")
+        S, R, P = syn.shape
+        need = self._syndrome_locate_need(R, S)
+        t = int(max_errors)
+        if not 0 <= 2 * t <= R:
+            raise ValueError("syndrome_locate: max_errors must be 0 .. R // 2")
+        _flat(ctx, "ctx", need, (torch.uint8,))
+        _oor(counts, entries, cap, S, R)
+        for tn, name, n in ((located, "located", self.k + R), (unlocated, "unlocated", 1),
+                            (weights, "weights", self.SYNDROME_MAX_ERRORS),
+                            (fix_counts, "fix_counts", 1)):
+            if tn is None:
+                raise ValueError(f"{name}: required")
+            _flat(tn, name, S * n, (torch.int32,))
+        if fix_cap < 0 or (fix_cap > 0 and fixes is None):
+            raise ValueError("fix_cap > 0 needs fixes")
+        _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        rc = lib().qi_gpu_syndrome_locate(
+            self.h, ctx.data_ptr(), R, t, syn.data_ptr(), syn.stride(0), syn.stride(1),
+            _ptr(counts), _ptr(entries), int(cap), located.data_ptr(), unlocated.data_ptr(),
+            weights.data_ptr(), fix_counts.data_ptr(), _ptr(fixes), int(fix_cap), P, S,
+            self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_syndrome_locate failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
     LOCATE_MAX_CHECKS = 8  # QI_LOCATE_MAX_CHECKS
 
     def locate_kernels(self, n_checks, words):
@@ -1113,6 +1271,156 @@ class Fec:
             if o_cnt.max(initial=0) <= out_cap:
                 return outs, o_oor, o_cnt
             out_cap = int(o_cnt.max())   # the list did not fit: once more
+
+    def syndrome_blocks(self, listed_ids, held_ids, rows, oor, counts, n_checks, acc=None,
+                        out_cap=64):
+        """Syndrome share (qi_fec_syndrome_blocks): the share of the n_checks
+        syndrome rows of the k + n_checks listed fragments `listed_ids` that
+        the holder of the fragments `held_ids` (each one of listed_ids) can
+        form, at any k.  rows, oor, counts and acc as partial_repair_blocks.
+        Returns (rows, out_oor, out_counts): the n_checks partial syndrome
+        rows, their ascending marks and exact counts; summed over any
+        partition of listed_ids they are the stripe's syndromes (all 0 when it
+        is intact).  Raises ValueError for an unsupported shape."""
+        import numpy as np
+        idv = np.ascontiguousarray(listed_ids, np.int32)
+        hv = np.ascontiguousarray(held_ids, np.int32)
+        R = int(n_checks)
+        if len(rows) != len(hv):
+            raise ValueError("syndrome_blocks: one row per held id")
+        if len(hv) == 0 or R < 1 or len(idv) != self.k + R:
+            raise ValueError("syndrome_blocks: shape not supported")
+        B = len(rows[0])
+        if oor is not None:
+            oor = np.ascontiguousarray(oor, np.uint32).reshape(len(hv), -1)
+            counts = np.ascontiguousarray(counts, np.uint32)
+        if acc is not None:
+            a_rows, a_oor, a_cnt = acc
+            if len(a_rows) != R or int(np.max(a_cnt, initial=0)) > a_oor.shape[1]:
+                raise ValueError("syndrome_blocks: acc needs one row per check "
+                                 "and complete mark lists")
+            out_cap = max(out_cap, a_oor.shape[1])
+        while True:
+            outs = [np.zeros(B, np.uint8) for _ in range(R)]
+            o_oor = np.zeros((R, out_cap), np.uint32)
+            o_cnt = np.zeros(R, np.uint32)
+            if acc is not None:
+                for j in range(R):
+                    outs[j][:] = a_rows[j]
+                o_oor[:, :a_oor.shape[1]] = a_oor
+                o_cnt[:] = a_cnt
+            rc = lib().qi_fec_syndrome_blocks(
+                self.h, idv.ctypes.data_as(C.c_void_p), len(idv),
+                hv.ctypes.data_as(C.c_void_p), len(hv), ptr_array(list(rows)),
+                oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                oor.shape[1] if oor is not None else 0, R, int(acc is not None),
+                ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
+                o_cnt.ctypes.data_as(C.c_void_p), out_cap, B)
+            if rc == -2:
+                raise ValueError("syndrome_blocks: shape not supported")
+            if rc != 1:
+                raise RuntimeError(f"qi_fec_syndrome_blocks failed: {rc}")
+            if o_cnt.max(initial=0) <= out_cap:
+                return outs, o_oor, o_cnt
+            out_cap = int(o_cnt.max())   # the list did not fit: once more
+
+    def locate_syndromes(self, listed_ids, rows, oor, counts, max_errors=1, fix_cap=256):
+        """The coordinator's decision over the complete syndrome sums
+        (qi_fec_locate_syndromes): rows, oor, counts as syndrome_blocks
+        returned them, R = len(listed_ids) - k of them.  0 <= max_errors <=
+        R // 2.  Returns (result, fixes): result an int64 array of k + m + 1 +
+        max_errors values -- per fragment id the located columns it takes part
+        in (-1: not listed), the unlocated columns, the columns located with
+        1 .. max_errors fragments -- and fixes an int64 array (n, 3) of
+        (column, fragment id, e): that fragment is off by e there, its true
+        symbol is (y - e) mod 65537 (apply_deltas)."""
+        import numpy as np
+        idv = np.ascontiguousarray(listed_ids, np.int32)
+        t = int(max_errors)
+        B = len(rows[0])
+        if oor is not None:
+            oor = np.ascontiguousarray(oor, np.uint32).reshape(len(rows), -1)
+            counts = np.ascontiguousarray(counts, np.uint32)
+        res = np.full(self.k + self.m + 1 + max(t, 0), -1, np.int64)
+        n = C.c_uint32(0)
+        while True:
+            fx = np.zeros((max(fix_cap, 1), 3), np.uint32)
+            rc = lib().qi_fec_locate_syndromes(
+                self.h, idv.ctypes.data_as(C.c_void_p), len(idv), ptr_array(list(rows)),
+                oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                oor.shape[1] if oor is not None else 0, t,
+                res.ctypes.data_as(C.c_void_p), fx.ctypes.data_as(C.c_void_p), fix_cap,
+                C.byref(n), B)
+            if rc == -2:
+                raise ValueError("locate_syndromes: shape not supported")
+            if rc != 1:
+                raise RuntimeError(f"qi_fec_locate_syndromes failed: {rc}")
+            if n.value <= fix_cap:
+                return res, fx[:n.value].astype(np.int64)
+            fix_cap = n.value
+
+    def apply_deltas(self, fragment_ids, rows, oor, counts, fixes):
+        """The holder's step (qi_fec_apply_deltas, no device): applies the
+        fixes of locate_syndromes that name one of `fragment_ids` to rows[h]
+        (uint8 numpy arrays, written in place) and to their ascending mark
+        lists oor (len(fragment_ids), cap) / counts (contiguous uint32 arrays,
+        updated in place; None: no marks, and none can be written); fixes for
+        other fragments are skipped.  Returns the number applied, or None with
+        nothing touched when the patch is refused: a data row would have to
+        hold 65536, or a mark list would outgrow cap."""
+        import numpy as np
+        fv = np.ascontiguousarray(fragment_ids, np.int32)
+        for a in (oor, counts):
+            if a is not None and (a.dtype != np.uint32 or not a.flags.c_contiguous):
+                raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        fx = np.ascontiguousarray(fixes, np.uint32).reshape(-1, 3)
+        if len(rows) != len(fv):
+            raise ValueError("apply_deltas: one row per fragment id")
+        rc = lib().qi_fec_apply_deltas(
+            self.h, fv.ctypes.data_as(C.c_void_p), len(fv), ptr_array(list(rows)),
+            oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+            counts.ctypes.data_as(C.c_void_p) if counts is not None else None,
+            oor.shape[1] if oor is not None else 0, fx.ctypes.data_as(C.c_void_p), len(fx),
+            len(rows[0]) if len(rows) else 0)
+        if rc == -3:
+            return None
+        if rc < 0:
+            raise RuntimeError(f"qi_fec_apply_deltas failed: {rc}")
+        return rc
+
+    def scrub_blocks(self, data, parities, oor, counts, missing, max_errors=1, correct=False):
+        """locate_blocks(max_errors=...) at any k (qi_fec_scrub_blocks): the
+        first min(present, k + 8) present fragments are listed, their syndrome
+        rows formed on the device and decided from those alone.  Arguments and
+        results as locate_blocks with max_errors; max_errors = 0 only detects
+        (every bad column is unlocated).  None when fewer than k + max(1, 2
+        max_errors) fragments are listed."""
+        import numpy as np
+        rows = [r for r in list(data or []) + list(parities) if r is not None]
+        B = len(rows[0])
+        miss = np.ascontiguousarray(missing, np.int32)
+        for a in (oor, counts):
+            if a is not None and (a.dtype != np.uint32 or not a.flags.c_contiguous):
+                raise TypeError("oor, counts: expected contiguous uint32 arrays")
+        t = int(max_errors)
+        if not 0 <= t <= Plan.SYNDROME_MAX_ERRORS:
+            raise ValueError("scrub_blocks: max_errors must be 0 .. 4")
+        res = np.full(self.k + self.m + 1 + t, -1, np.int64)
+        rc = lib().qi_fec_scrub_blocks(
+            self.h, ptr_array(list(data)) if data is not None else None,
+            ptr_array(list(parities)), oor.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p) if counts is not None else None,
+            oor.shape[1], miss.ctypes.data_as(C.c_void_p), t,
+            res.ctypes.data_as(C.c_void_p), int(bool(correct)), B)
+        if rc == -2:
+            raise ValueError("scrub_blocks: shape not supported")
+        if rc < 0:
+            raise RuntimeError(f"qi_fec_scrub_blocks failed: {rc}")
+        if rc == 0:
+            return None
+        return (res, rc == 2) if correct else res
 
     def close(self):
         if self.h:

@@ -1098,6 +1098,301 @@ void RsFnt::partial_repair_blocks_vertical(const std::vector<int>& ids,
         stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
 }
 
+// ---- syndrome shares (single chunk; qi_gpu_syndrome_ctx, then the share in
+// place on the staged acc rows; qi_gpu_syndrome_locate over the summed rows) ----
+bool RsFnt::syndrome_supported(size_t n_held, size_t n_checks, size_t block_size_bytes) const
+{
+    const size_t words = block_size_bytes / word_size;
+    if (n_checks < 1 || n_checks > std::min<size_t>(QI_SYNDROME_MAX_CHECKS, code_len - n_data) ||
+        n_held < 1 || n_held > n_data + n_checks)
+        return false;
+    if (words == 0 || words > chunk_bytes(buf_size) / 2)
+        return false;
+    // the held rows and the syndrome rows, back to back
+    return (n_held + n_checks) * pad_words(words) * 2 <= (size_t{256} << 20);
+}
+
+void RsFnt::syndrome_blocks_vertical(const std::vector<int>& listed_ids,
+                                     const std::vector<int>& held_ids,
+                                     std::vector<uint8_t*>& held_bufs,
+                                     std::vector<Properties>& held_props, int n_checks, bool acc,
+                                     std::vector<uint8_t*>& out_bufs,
+                                     std::vector<Properties>& out_props, size_t block_size_bytes)
+{
+    // validate; held fragment ids -> positions into listed_ids
+    const stage::FragMap map = frag_map(*this);
+    const size_t H = held_ids.size(), R = n_checks < 0 ? 0 : static_cast<size_t>(n_checks);
+    const size_t N = n_data + R;
+    if (!syndrome_supported(H, R, block_size_bytes))
+        throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: unsupported shape");
+    if (listed_ids.size() != N || held_bufs.size() < H || held_props.size() < H ||
+        out_bufs.size() < R || (acc && out_props.size() < R))
+        throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: buffers");
+    std::vector<int> where(code_len, -1);  // fragment id -> position in listed_ids
+    for (size_t i = 0; i < N; i++) {
+        if (listed_ids[i] < 0 || listed_ids[i] >= static_cast<int>(code_len) ||
+            where[listed_ids[i]] != -1)
+            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: bad id");
+        where[listed_ids[i]] = static_cast<int>(i);
+    }
+    for (size_t j = 0; j < R; j++)
+        if (!out_bufs[j])
+            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: buffers");
+    std::vector<uint16_t> hids(listed_ids.begin(), listed_ids.end());
+    std::vector<char> taken(N, 0);
+    for (size_t hh = 0; hh < H; hh++) {
+        const int f = held_ids[hh];
+        if (f < 0 || f >= static_cast<int>(code_len) || where[f] < 0 || taken[where[f]] ||
+            !held_bufs[hh])
+            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: bad held id");
+        taken[where[f]] = 1;
+        hids.push_back(static_cast<uint16_t>(where[f]));
+    }
+    const size_t words = block_size_bytes / word_size;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // stage: the H held rows, the R syndrome rows, the buckets of both, the
+    // output counts
+    std::vector<const Properties*> hmarked(H, nullptr), amarked(R, nullptr);
+    for (size_t hh = 0; hh < H; hh++) {
+        if (map.slot(static_cast<unsigned>(held_ids[hh])).is_data)
+            continue;
+        held_props[hh].sort();
+        hmarked[hh] = &held_props[hh];
+    }
+    for (size_t j = 0; acc && j < R; j++) {
+        out_props[j].sort();
+        amarked[j] = &out_props[j];
+    }
+    const stage::PackedMarks pm = stage::pack_marks(hmarked, 0, words);
+    const stage::PackedMarks am = stage::pack_marks(amarked, 0, words);
+    const size_t P = pad_words(words);
+    const auto off = stage::layout(
+        {H * 4, pm.entries.size() * 4, R * 4, am.entries.size() * 4, R * 4});
+    const size_t ctx_bytes =
+        qi_gpu_syndrome_ctx_bytes(pl, static_cast<int>(H), static_cast<int>(R), 1);
+    reserve(h.in, (H + R) * P * 2);
+    reserve(h.counts, off[5]);
+    reserve(h.ids, hids.size() * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint16_t* drows = static_cast<uint16_t*>(h.in.p);
+    uint16_t* dacc = drows + H * P;
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
+    uint32_t* dacnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
+    uint32_t* daent = reinterpret_cast<uint32_t*>(dcb + off[3]);
+    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[4]);
+    const auto upload_acc = [&] {
+        for (size_t j = 0; acc && j < R; j++)
+            h2d(dacc + j * P, out_bufs[j], words * 2, s);
+    };
+    for (size_t hh = 0; hh < H; hh++)
+        h2d(drows + hh * P, held_bufs[hh], words * 2, s);
+    upload_acc();
+    upload_marks(pm, dcnt, dent, s);
+    upload_marks(am, dacnt, daent, s);
+    h2d(h.ids.p, hids.data(), hids.size() * 2, s);
+    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
+    check_rc(qi_gpu_syndrome_ctx(pl, dids, dids + N, static_cast<int>(H), static_cast<int>(R), 1,
+                                 h.ctx.p, s),
+             "syndrome context");
+    // launch in place; a second attempt starts from the acc rows as they were
+    const long long Pl = static_cast<long long>(P);
+    std::vector<uint32_t> ocnt(R);
+    const size_t ocap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, R * c * 4);
+            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+            check_rc(qi_gpu_syndrome(pl, h.ctx.p, static_cast<int>(H), static_cast<int>(R), drows,
+                                     0, Pl, dcnt, dent, static_cast<int>(pm.cap),
+                                     acc ? dacc : nullptr, 0, Pl, dacnt, daent,
+                                     static_cast<int>(am.cap), dacc, 0, Pl, docnt,
+                                     static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                     static_cast<long long>(words), 1, s),
+                     "syndrome");
+        },
+        [&] { return read_max(ocnt, docnt, s); }, upload_acc);
+    // collect
+    std::vector<uint32_t> ent(R * ocap);
+    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
+    for (size_t j = 0; j < R; j++)
+        d2h(out_bufs[j], dacc + j * P, words * 2, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: syndrome share failed (bad ids or OOR bucket capacity)");
+    out_props.assign(R, Properties());
+    for (size_t j = 0; j < R; j++)
+        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
+}
+
+void RsFnt::locate_syndromes(const std::vector<int>& listed_ids, std::vector<uint8_t*>& syn_bufs,
+                             std::vector<Properties>& syn_props, int max_errors,
+                             LocateResult& result, size_t block_size_bytes)
+{
+    // validate
+    const size_t N = listed_ids.size();
+    const size_t R = N > n_data ? N - n_data : 0;
+    const int t = max_errors;
+    if (!syndrome_supported(1, R, block_size_bytes) || t < 0 || 2 * static_cast<size_t>(t) > R)
+        throw std::invalid_argument("RsFnt::locate_syndromes: unsupported shape");
+    if (syn_bufs.size() < R || syn_props.size() < R)
+        throw std::invalid_argument("RsFnt::locate_syndromes: buffers");
+    std::vector<char> seen(code_len, 0);
+    for (int f : listed_ids) {
+        if (f < 0 || f >= static_cast<int>(code_len) || seen[f])
+            throw std::invalid_argument("RsFnt::locate_syndromes: bad id");
+        seen[f] = 1;
+    }
+    result.located.assign(code_len, -1);
+    result.unlocated = 0;
+    result.fixes.clear();
+    result.weights.assign(t, 0);
+    const size_t words = block_size_bytes / word_size;
+    qi_plan* pl = plan_;
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // stage: the R syndrome rows, their buckets, then located[N], unlocated,
+    // the fix count and the weights
+    std::vector<const Properties*> marked(R, nullptr);
+    for (size_t j = 0; j < R; j++) {
+        if (!syn_bufs[j])
+            throw std::invalid_argument("RsFnt::locate_syndromes: buffers");
+        syn_props[j].sort();
+        marked[j] = &syn_props[j];
+    }
+    const stage::PackedMarks pm = stage::pack_marks(marked, 0, words);
+    const size_t P = pad_words(words);
+    const size_t T = N + 2 + QI_SYNDROME_MAX_ERRORS;
+    const auto off = stage::layout({R * 4, pm.entries.size() * 4, T * 4});
+    const size_t ctx_bytes = qi_gpu_syndrome_locate_ctx_bytes(pl, static_cast<int>(R), 1);
+    reserve(h.in, R * P * 2);
+    reserve(h.counts, off[3]);
+    reserve(h.ids, N * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint16_t* dsyn = static_cast<uint16_t*>(h.in.p);
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
+    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
+    uint32_t* dres = reinterpret_cast<uint32_t*>(dcb + off[2]);
+    for (size_t j = 0; j < R; j++)
+        h2d(dsyn + j * P, syn_bufs[j], words * 2, s);
+    upload_marks(pm, dcnt, dent, s);
+    const std::vector<uint16_t> hids(listed_ids.begin(), listed_ids.end());
+    h2d(h.ids.p, hids.data(), N * 2, s);
+    check_rc(qi_gpu_syndrome_locate_ctx(pl, static_cast<uint16_t*>(h.ids.p), static_cast<int>(R),
+                                        1, h.ctx.p, s),
+             "syndrome locate context");
+    // launch: a fix list longer than the capacity is run again with the exact
+    // one (an overflowing fix list raises no error)
+    std::vector<uint32_t> res(T);
+    const size_t fcap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, c * 3 * 4);
+            check_rc(qi_gpu_syndrome_locate(pl, h.ctx.p, static_cast<int>(R), t, dsyn, 0,
+                                            static_cast<long long>(P), dcnt, dent,
+                                            static_cast<int>(pm.cap), dres, dres + N,
+                                            dres + N + 2, dres + N + 1,
+                                            static_cast<uint32_t*>(h.entries.p),
+                                            static_cast<int>(c), static_cast<long long>(words), 1,
+                                            s),
+                     "syndrome locate");
+        },
+        [&] {
+            d2h(res.data(), dres, T * 4, s);
+            check(hipStreamSynchronize(s), "sync");
+            return static_cast<size_t>(res[N + 1]);
+        },
+        [] {});
+    // collect
+    const size_t nfix = res[N + 1];
+    if (nfix > fcap)
+        throw std::runtime_error("RsFnt: syndrome locate fix list overflowed twice");
+    std::vector<uint32_t> fx(nfix * 3);
+    if (nfix)
+        d2h(fx.data(), h.entries.p, nfix * 3 * 4, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error("RsFnt: syndrome locate failed (bad ids or OOR bucket capacity)");
+    for (size_t i = 0; i < N; i++)
+        result.located[listed_ids[i]] = static_cast<long long>(res[i]);
+    result.unlocated = static_cast<long long>(res[N]);
+    for (int nu = 0; nu < t; nu++)
+        result.weights[nu] = static_cast<long long>(res[N + 2 + nu]);
+    for (size_t e = 0; e < nfix; e++)
+        result.fixes.push_back(LocateFix{fx[3 * e], listed_ids[fx[3 * e + 1]], fx[3 * e + 2]});
+}
+
+long long RsFnt::apply_deltas(const std::vector<int>& fragment_ids, std::vector<uint8_t*>& bufs,
+                              std::vector<Properties>& props,
+                              const std::vector<LocateFix>& deltas, size_t block_size_bytes,
+                              size_t max_marks) const
+{
+    if (bufs.size() < fragment_ids.size() || props.size() < fragment_ids.size())
+        throw std::invalid_argument("RsFnt::apply_deltas: buffers");
+    const size_t words = block_size_bytes / word_size;
+    for (auto const& d : deltas)
+        if (d.column >= words || d.symbol < 1 || d.symbol > 65536)
+            throw std::invalid_argument("RsFnt::apply_deltas: bad fix");
+    for (size_t hh = 0; hh < fragment_ids.size(); hh++)
+        if (!bufs[hh])
+            throw std::invalid_argument("RsFnt::apply_deltas: buffers");
+    return stage::apply_deltas(frag_map(*this), fragment_ids, bufs, props, deltas, max_marks);
+}
+
+int RsFnt::scrub_blocks_vertical(std::vector<uint8_t*>& data_bufs,
+                                 std::vector<uint8_t*>& parities_bufs,
+                                 std::vector<Properties>& parities_props,
+                                 std::vector<int>& missing_idxs, LocateResult& result,
+                                 int max_errors, bool correct, size_t block_size_bytes,
+                                 size_t max_marks)
+{
+    if (max_errors < 0 || max_errors > QI_SYNDROME_MAX_ERRORS)
+        throw std::invalid_argument("RsFnt::scrub_blocks_vertical: max_errors");
+    const stage::FragMap map = frag_map(*this);
+    const std::vector<int> present = map.present(missing_idxs);
+    result.located.assign(code_len, -1);
+    result.unlocated = 0;
+    result.fixes.clear();
+    result.weights.assign(max_errors, 0);
+    const std::vector<int> ids = map.select_upto(present, n_data + QI_SYNDROME_MAX_CHECKS);
+    if (ids.size() < n_data + std::max(1, 2 * max_errors))
+        return 0;
+    const size_t N = ids.size(), R = N - n_data;
+    if (!syndrome_supported(N, R, block_size_bytes))
+        throw std::invalid_argument("RsFnt::scrub_blocks_vertical: unsupported shape");
+    // the share of a holder of every listed fragment, then the decision
+    std::vector<uint8_t*> rows(N);
+    std::vector<Properties> props(N);
+    for (size_t i = 0; i < N; i++) {
+        const auto fs = map.slot(static_cast<unsigned>(ids[i]));
+        rows[i] = fs.is_data ? data_bufs[fs.slot] : parities_bufs[fs.slot];
+        if (!fs.is_data)
+            props[i] = parities_props[fs.slot];
+    }
+    std::vector<std::vector<uint8_t>> syn(R, std::vector<uint8_t>(block_size_bytes));
+    std::vector<uint8_t*> syn_bufs(R);
+    for (size_t j = 0; j < R; j++)
+        syn_bufs[j] = syn[j].data();
+    std::vector<Properties> syn_props;
+    syndrome_blocks_vertical(ids, ids, rows, props, static_cast<int>(R), false, syn_bufs,
+                             syn_props, block_size_bytes);
+    locate_syndromes(ids, syn_bufs, syn_props, max_errors, result, block_size_bytes);
+    if (!correct || result.fixes.empty() || result.unlocated != 0)
+        return 1;
+    if (apply_deltas(ids, rows, props, result.fixes, block_size_bytes, max_marks) < 0)
+        throw std::length_error("RsFnt::scrub_blocks_vertical: patch refused");
+    for (size_t i = 0; i < N; i++) {
+        const auto fs = map.slot(static_cast<unsigned>(ids[i]));
+        if (!fs.is_data)
+            parities_props[fs.slot] = props[i];
+    }
+    return 2;
+}
+
 namespace {
 
 // One stage of the pipelined stream API: pinned host staging, device
@@ -2112,6 +2407,133 @@ int qi_fec_partial_repair_blocks(qi_fec* h, const int* ids, const int* held_ids,
         f.partial_repair_blocks_vertical(iv, hv, rv, hp, tv, acc != 0, ov, op, block_bytes);
         qi::fec::stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
         return 1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_syndrome_blocks(qi_fec* h, const int* listed_ids, int n_listed, const int* held_ids,
+                           int n_held, uint8_t** rows, const uint32_t* oor,
+                           const uint32_t* oor_count, uint32_t cap, int n_checks, int acc,
+                           uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
+                           uint32_t out_cap, size_t block_bytes)
+{
+    try {
+        if (!h || !listed_ids || !held_ids || !rows || !out || !out_count || n_held < 0 ||
+            n_checks < 0 || n_listed < 0 || (out_cap > 0 && !out_oor))
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.syndrome_supported(static_cast<size_t>(n_held), static_cast<size_t>(n_checks),
+                                  block_bytes) ||
+            static_cast<size_t>(n_listed) != f.n_data + static_cast<size_t>(n_checks))
+            return -2;
+        std::vector<int> iv(listed_ids, listed_ids + n_listed), hv(held_ids, held_ids + n_held);
+        std::vector<uint8_t*> rv(rows, rows + n_held), ov(out, out + n_checks);
+        // (oor_count null: no marks)
+        std::vector<qi::Properties> hp(static_cast<size_t>(n_held)),
+            op(static_cast<size_t>(n_checks));
+        qi::fec::stage::props_from_flat(hp, oor, nullptr, oor_count, cap);
+        if (acc)
+            qi::fec::stage::props_from_flat(op, out_oor, nullptr, out_count, out_cap);
+        f.syndrome_blocks_vertical(iv, hv, rv, hp, n_checks, acc != 0, ov, op, block_bytes);
+        qi::fec::stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
+        return 1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_locate_syndromes(qi_fec* h, const int* listed_ids, int n_listed, uint8_t** rows,
+                            const uint32_t* oor, const uint32_t* oor_count, uint32_t cap,
+                            int max_errors, long long* result, uint32_t* fixes, uint32_t fix_cap,
+                            uint32_t* n_fixes, size_t block_bytes)
+{
+    try {
+        if (!h || !listed_ids || !rows || !result || !n_fixes || n_listed < 0 ||
+            (fix_cap > 0 && !fixes))
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        const size_t R = static_cast<size_t>(n_listed) > f.n_data ? n_listed - f.n_data : 0;
+        if (!f.syndrome_supported(1, R, block_bytes) || max_errors < 0 ||
+            2 * static_cast<size_t>(max_errors) > R)
+            return -2;
+        std::vector<int> iv(listed_ids, listed_ids + n_listed);
+        std::vector<uint8_t*> rv(rows, rows + R);
+        std::vector<qi::Properties> sp(R);
+        qi::fec::stage::props_from_flat(sp, oor, nullptr, oor_count, cap);
+        qi::fec::LocateResult res;
+        f.locate_syndromes(iv, rv, sp, max_errors, res, block_bytes);
+        for (unsigned i = 0; i < f.code_len; i++)
+            result[i] = res.located[i];
+        result[f.code_len] = res.unlocated;
+        for (int nu = 0; nu < max_errors; nu++)
+            result[f.code_len + 1 + nu] = res.weights[nu];
+        *n_fixes = static_cast<uint32_t>(res.fixes.size());
+        for (size_t e = 0; e < res.fixes.size() && e < fix_cap; e++) {
+            fixes[3 * e] = res.fixes[e].column;
+            fixes[3 * e + 1] = static_cast<uint32_t>(res.fixes[e].fragment);
+            fixes[3 * e + 2] = res.fixes[e].symbol;
+        }
+        return 1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_apply_deltas(qi_fec* h, const int* fragment_ids, int n_rows, uint8_t** rows,
+                        uint32_t* oor, uint32_t* oor_count, uint32_t cap, const uint32_t* fixes,
+                        uint32_t n_fixes, size_t block_bytes)
+{
+    try {
+        if (!h || !fragment_ids || !rows || n_rows < 0 || (n_fixes > 0 && !fixes) ||
+            (oor_count && cap > 0 && !oor))
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        std::vector<int> iv(fragment_ids, fragment_ids + n_rows);
+        std::vector<uint8_t*> rv(rows, rows + n_rows);
+        std::vector<qi::Properties> props(static_cast<size_t>(n_rows));
+        qi::fec::stage::props_from_flat(props, oor, nullptr, oor_count, cap);
+        std::vector<qi::fec::LocateFix> dl;
+        for (uint32_t e = 0; e < n_fixes; e++)
+            dl.push_back(qi::fec::LocateFix{fixes[3 * e], static_cast<int>(fixes[3 * e + 1]),
+                                            fixes[3 * e + 2]});
+        const long long n = f.apply_deltas(iv, rv, props, dl, block_bytes, oor_count ? cap : 0);
+        if (n < 0)
+            return -3;
+        if (oor_count)
+            qi::fec::stage::props_to_flat(props, oor, nullptr, oor_count, cap);
+        return static_cast<int>(n);
+    } catch (...) {
+        return -1;
+    }
+}
+
+int qi_fec_scrub_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t* oor,
+                        uint32_t* oor_count, uint32_t cap, const int* missing, int max_errors,
+                        long long* result, int correct, size_t block_bytes)
+{
+    try {
+        if (!h || !parities || !missing || !result || max_errors < 0 ||
+            max_errors > QI_SYNDROME_MAX_ERRORS)
+            return -1;
+        qi::fec::RsFnt& f = *h->f;
+        if (!f.syndrome_supported(1, 1, block_bytes))
+            return -2;
+        // (oor_count null: no marks, and none can be written)
+        FlatFragments fr(f, data, parities, oor, oor_count, cap, missing);
+        qi::fec::LocateResult res;
+        const int rc = f.scrub_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res, max_errors,
+                                               correct != 0, block_bytes, oor_count ? cap : 0);
+        for (unsigned i = 0; i < f.code_len; i++)
+            result[i] = res.located[i];
+        result[f.code_len] = res.unlocated;
+        for (int nu = 0; nu < max_errors; nu++)
+            result[f.code_len + 1 + nu] = res.weights[nu];
+        if (rc == 2 && oor_count)
+            stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
+        return rc;
+    } catch (const std::invalid_argument&) {
+        return -2;
     } catch (...) {
         return -1;
     }

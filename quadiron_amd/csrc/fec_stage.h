@@ -252,6 +252,68 @@ inline bool apply_fixes(const FragMap& map, const std::vector<LocateFix>& fixes,
     return true;
 }
 
+// ---- syndrome deltas -> a holder's rows --------------------------------------
+// A syndrome resolve (qi_gpu_syndrome_locate) reports what a fragment is off
+// by, not what it should hold: LocateFix::symbol is the error e in [1, 65536]
+// and the true symbol (y - e) mod 65537, with y the restored symbol of the row
+// (65536 where its ascending mark list names the column).  The holder of the
+// fragments `fragment_ids` (rows[h], props[h]; a systematic data row has no
+// marks) applies the deltas that name one of them and skips the others.
+// Nothing is touched, and -1 returned, when a data row would have to hold
+// 65536 or a mark list would grow past max_marks (apply_fixes' rule); else the
+// number of deltas applied.  A (fragment, column) pair is named at most once.
+inline long long apply_deltas(const FragMap& map, const std::vector<int>& fragment_ids,
+                              const std::vector<uint8_t*>& rows, std::vector<Properties>& props,
+                              const std::vector<LocateFix>& deltas, size_t max_marks)
+{
+    std::vector<int> where(map.code_len(), -1);
+    std::vector<uint8_t*> data_bufs(map.data_rows(), nullptr), coded_bufs(map.n_outputs, nullptr);
+    std::vector<Properties> coded_props(map.n_outputs);
+    std::vector<std::vector<size_t>> marks(map.n_outputs);  // ascending
+    for (size_t h = 0; h < fragment_ids.size(); h++) {
+        const int f = fragment_ids[h];
+        if (f < 0 || static_cast<unsigned>(f) >= map.code_len() || where[f] >= 0)
+            return -1;
+        where[f] = static_cast<int>(h);
+        const auto fs = map.slot(static_cast<unsigned>(f));
+        if (fs.is_data) {
+            data_bufs[fs.slot] = rows[h];
+        } else {
+            coded_bufs[fs.slot] = rows[h];
+            coded_props[fs.slot] = props[h];
+            for (auto const& it : props[h].get_map())
+                marks[fs.slot].push_back(it.first);
+            std::sort(marks[fs.slot].begin(), marks[fs.slot].end());
+        }
+    }
+    std::vector<LocateFix> fixes;
+    for (auto const& d : deltas) {
+        if (d.fragment < 0 || static_cast<unsigned>(d.fragment) >= map.code_len() ||
+            where[d.fragment] < 0)
+            continue;
+        const auto fs = map.slot(static_cast<unsigned>(d.fragment));
+        const uint8_t* row = rows[where[d.fragment]];
+        uint32_t y = static_cast<uint32_t>(row[2 * static_cast<size_t>(d.column)]) |
+                     static_cast<uint32_t>(row[2 * static_cast<size_t>(d.column) + 1]) << 8;
+        if (!fs.is_data && std::binary_search(marks[fs.slot].begin(), marks[fs.slot].end(),
+                                              static_cast<size_t>(d.column)))
+            y = 65536u;
+        const uint32_t e = d.symbol % 65537u;
+        const uint32_t v = y >= e ? y - e : y + 65537u - e;
+        if (fs.is_data && v == 65536u)
+            return -1;
+        fixes.push_back(LocateFix{d.column, d.fragment, v});
+    }
+    if (!apply_fixes(map, fixes, data_bufs, coded_bufs, coded_props, max_marks))
+        return -1;
+    for (size_t h = 0; h < fragment_ids.size(); h++) {
+        const auto fs = map.slot(static_cast<unsigned>(fragment_ids[h]));
+        if (!fs.is_data)
+            props[h] = coded_props[fs.slot];
+    }
+    return static_cast<long long>(fixes.size());
+}
+
 // ---- flat C arrays <-> Properties ---------------------------------------
 // (oor, flags, count, cap): props.size() rows of cap locations (and markers;
 // flags null: OOR_MARK) with a count each.  A count above cap is clamped on

@@ -15,6 +15,7 @@
 #include "partial_math.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
+#include "syndrome_math.h"
 #include "update_coef.h"
 
 using namespace qi;
@@ -745,6 +746,139 @@ const char* qi_gpu_partial_kernels(const qi_plan* p, int H, int R, long long wor
         return "";
     names = "partial=" + partial_ctx_kernel_name() + " + " +
             partial_kernel_name(partial_rp(R), true);
+    return names.c_str();
+}
+
+// ---- syndrome shares (any k): syndrome_ctx_kernel leaves the H x RP syndrome
+// coefficients of the held rows in a partial repair's context layout and the
+// share is launch_partial; syndrome_locate_ctx_kernel and
+// syndrome_locate_kernel decide the columns from the R summed rows
+// (syndrome.hip, syndrome_math.h) ----
+static_assert(QI_SYNDROME_MAX_CHECKS == kSynMaxChecks && QI_SYNDROME_MAX_ERRORS == kSynMaxErrors,
+              "qi_gpu.h and syndrome_math.h differ");
+
+static bool syndrome_checks_ok(const qi_plan* p, int R)
+{
+    return R >= 1 && R <= std::min(QI_SYNDROME_MAX_CHECKS, p->code_len - p->k);
+}
+
+static bool syndrome_ok(const qi_plan* p, int H, int R)
+{
+    return syndrome_checks_ok(p, R) && H >= 1 && H <= p->k + R;
+}
+
+size_t qi_gpu_syndrome_ctx_bytes(const qi_plan* p, int H, int R, int n_stripes)
+{
+    if (!p || n_stripes < 0 || !syndrome_ok(p, H, R))
+        return 0;
+    return static_cast<size_t>(syndrome_ctx_words(H, R)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_syndrome_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_held, int H, int R,
+                        int n_stripes, void* d_ctx, void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0)
+        return -1;
+    if (!syndrome_ok(p, H, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids || !d_held)
+        return -1;
+    return launch_syndrome_ctx(p->k, p->code_len, p->r, d_ids, d_held, H, R, n_stripes,
+                               static_cast<int32_t*>(d_ctx), p->d_err, st(stream));
+}
+
+int qi_gpu_syndrome(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t* d_rows,
+                    long long rss, long long rrs, const uint32_t* d_in_counts,
+                    const uint32_t* d_in_entries, int in_cap, const uint16_t* d_acc,
+                    long long ass, long long ars, const uint32_t* d_acc_counts,
+                    const uint32_t* d_acc_entries, int acc_cap, uint16_t* d_out, long long oss,
+                    long long ors, uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                    long long words, int n_stripes, void* stream)
+{
+    if (!p || !d_ctx || !d_rows || !d_out || n_stripes < 0 || words < 0 || in_cap < 0 ||
+        acc_cap < 0 || out_cap < 0 || (d_in_counts && in_cap > 0 && !d_in_entries) ||
+        (d_acc_counts && acc_cap > 0 && !d_acc_entries) ||
+        (d_out_counts && out_cap > 0 && !d_out_entries))
+        return -1;
+    if (!syndrome_ok(p, H, R))
+        return -1;
+    if (n_stripes == 0 || words == 0)
+        return 0;
+    const Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries), H,
+                 in_cap};
+    // (no acc rows: no acc marks)
+    const Oor accm{d_acc ? const_cast<uint32_t*>(d_acc_counts) : nullptr,
+                   const_cast<uint32_t*>(d_acc_entries), R, acc_cap};
+    const Oor outm{d_out_counts, d_out_entries, R, out_cap};
+    return launch_partial(static_cast<const int32_t*>(d_ctx), H, R, p->sys ? p->k : 0, d_rows, rss,
+                          rrs, in, d_acc, ass, ars, accm, d_out, oss, ors, outm, words, n_stripes,
+                          p->d_err, st(stream));
+}
+
+const char* qi_gpu_syndrome_kernels(const qi_plan* p, int H, int R, long long words)
+{
+    static thread_local std::string names;
+    if (!p || words <= 0 || !syndrome_ok(p, H, R))
+        return "";
+    names = "syndrome=" + syndrome_ctx_kernel_name() + " + " +
+            partial_kernel_name(partial_rp(R), true);
+    return names.c_str();
+}
+
+size_t qi_gpu_syndrome_locate_ctx_bytes(const qi_plan* p, int R, int n_stripes)
+{
+    if (!p || n_stripes < 0 || !syndrome_checks_ok(p, R))
+        return 0;
+    return static_cast<size_t>(syndrome_locate_ctx_words(p->k + R)) * sizeof(int32_t) *
+           static_cast<size_t>(n_stripes);
+}
+
+int qi_gpu_syndrome_locate_ctx(qi_plan* p, const uint16_t* d_ids, int R, int n_stripes,
+                               void* d_ctx, void* stream)
+{
+    if (!p || !d_ctx || n_stripes < 0)
+        return -1;
+    if (!syndrome_checks_ok(p, R))
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    if (!d_ids)
+        return -1;
+    return launch_syndrome_locate_ctx(p->k, R, p->code_len, p->r, d_ids, n_stripes,
+                                      static_cast<int32_t*>(d_ctx), p->d_err, st(stream));
+}
+
+int qi_gpu_syndrome_locate(qi_plan* p, const void* d_ctx, int R, int t, const uint16_t* d_syn,
+                           long long sss, long long srs, const uint32_t* d_counts,
+                           const uint32_t* d_entries, int cap, uint32_t* d_located,
+                           uint32_t* d_unlocated, uint32_t* d_weights, uint32_t* d_fix_counts,
+                           uint32_t* d_fixes, int fix_cap, long long words, int n_stripes,
+                           void* stream)
+{
+    if (!p || !d_ctx || !d_syn || !d_located || !d_unlocated || !d_weights || !d_fix_counts ||
+        n_stripes < 0 || words < 0 || cap < 0 || fix_cap < 0 || (fix_cap > 0 && !d_fixes) ||
+        (d_counts && cap > 0 && !d_entries))
+        return -1;
+    if (!syndrome_checks_ok(p, R) || t < 0 || 2 * t > R)
+        return -1;
+    if (n_stripes == 0)
+        return 0;
+    const Oor in{const_cast<uint32_t*>(d_counts), const_cast<uint32_t*>(d_entries), R, cap};
+    return launch_syndrome_locate(static_cast<const int32_t*>(d_ctx), p->k, R, t, d_syn, sss, srs,
+                                  in, d_located, d_unlocated, d_weights, d_fix_counts, d_fixes,
+                                  fix_cap, words, n_stripes, p->d_err, st(stream));
+}
+
+const char* qi_gpu_syndrome_locate_kernels(const qi_plan* p, int R, int t, long long words)
+{
+    static thread_local std::string names;
+    if (!p || words <= 0 || !syndrome_checks_ok(p, R) || t < 0 || 2 * t > R)
+        return "";
+    names = "syndrome_locate=" + syndrome_locate_ctx_kernel_name() + " + " +
+            syndrome_locate_kernel_name(syndrome_locate_rp(R), true);
     return names.c_str();
 }
 

@@ -382,6 +382,31 @@ int launch_partial(const int32_t* d_ctx, int H, int R, int split, const uint16_t
 std::string partial_ctx_kernel_name();
 std::string partial_kernel_name(int RP, bool vec);
 
+// per-stripe syndrome-share contexts (syndrome.hip, syndrome_math.h; S x (k +
+// R) listed ids, S x H positions into them): partial_ctx_words(H, R) words
+// each in the layout launch_partial reads, the H x RP balanced coefficients
+// x^j / w of the held rows, RP filler words and the held rows' ids.  An id not
+// below code_len or repeated, a position not below k + R or repeated raise
+// kErrBadIds; that row's coefficients are 0.  The share itself is
+// launch_partial
+int launch_syndrome_ctx(int k, int code_len, uint32_t r, const uint16_t* d_ids,
+                        const uint16_t* d_held, int H, int R, int S, int32_t* d_ctx,
+                        uint32_t* err, hipStream_t st);
+// per-stripe resolve contexts: the k + R ids, points and weights,
+// syndrome_locate_ctx_words(k + R) words each
+int launch_syndrome_locate_ctx(int k, int R, int code_len, uint32_t r, const uint16_t* d_ids,
+                               int S, int32_t* d_ctx, uint32_t* err, hipStream_t st);
+// the decision over the R summed syndrome rows (buckets `in` by slot j), bound
+// 0 <= t <= R / 2; the five outputs are cleared by the call
+int launch_syndrome_locate(const int32_t* d_ctx, int k, int R, int t, const uint16_t* d_syn,
+                           long long sss, long long srs, const Oor& in, uint32_t* d_located,
+                           uint32_t* d_unlocated, uint32_t* d_weights, uint32_t* d_fix_counts,
+                           uint32_t* d_fixes, int fix_cap, long long words, int n_stripes,
+                           uint32_t* d_err, hipStream_t st);
+std::string syndrome_ctx_kernel_name();
+std::string syndrome_locate_ctx_kernel_name();
+std::string syndrome_locate_kernel_name(int RP, bool vec);
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.
