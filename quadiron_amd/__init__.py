@@ -208,6 +208,13 @@ def _row_args(t):
     return (t.data_ptr(), t.stride(0), t.stride(1)) if t is not None else (None, 0, 0)
 
 
+def _need(need, S, unsupported):
+    """a context size, or the ValueError of a shape whose size is 0"""
+    if need == 0 and S > 0:
+        raise ValueError(unsupported)
+    return need
+
+
 def require_device():
     n = lib().qi_gpu_device_count()
     if n < 1:
@@ -377,12 +384,10 @@ class Plan:
     def _repair_need(self, what, R, S, words):
         """repair_ctx_bytes, or the error of a "repair" / "check" of R
         fragments that the plan does not support."""
-        need = self.repair_ctx_bytes(R, S, words)
-        if need == 0 and S > 0:
-            noun = "targets" if what == "repair" else "fragments"
-            raise ValueError(f"{what} of {R} {noun} is not supported on "
-                             f"this plan (k <= 256, 1 <= R <= min(64, m))")
-        return need
+        noun = "targets" if what == "repair" else "fragments"
+        return _need(self.repair_ctx_bytes(R, S, words), S,
+                     f"{what} of {R} {noun} is not supported on "
+                     f"this plan (k <= 256, 1 <= R <= min(64, m))")
 
     def repair_ctx(self, ids, targets, ctx, words, counts=None, entries=None,
                    cap=0, stream=None):
@@ -575,11 +580,9 @@ class Plan:
         return lib().qi_gpu_partial_ctx_bytes(self.h, n_held, n_targets, n_stripes)
 
     def _partial_need(self, H, R, S):
-        need = self.partial_ctx_bytes(H, R, S)
-        if need == 0 and S > 0:
-            raise ValueError(f"partial repair of {R} targets from {H} held rows is not "
-                             f"supported (1 <= H <= k, 1 <= R <= min(8, m))")
-        return need
+        return _need(self.partial_ctx_bytes(H, R, S), S,
+                     f"partial repair of {R} targets from {H} held rows is not "
+                     f"supported (1 <= H <= k, 1 <= R <= min(8, m))")
 
     def partial_ctx(self, ids, held, targets, ctx, stream=None):
         """ids: int16 tensor [S, k] (the k helper fragments of the repair);
@@ -614,6 +617,13 @@ class Plan:
         target t, may be acc itself; its marks go to out_counts / out_entries
         (slots = R, cleared by the caller, distinct from the acc buckets).
         Returns the sticky error flags when check."""
+        return self._share(lib().qi_gpu_partial, "qi_gpu_partial", self._partial_need, ctx, rows,
+                           out, acc, counts, entries, cap, acc_counts, acc_entries, acc_cap,
+                           out_counts, out_entries, out_cap, stream, check)
+
+    def _share(self, fn, name, need_of, ctx, rows, out, acc, counts, entries, cap, acc_counts,
+               acc_entries, acc_cap, out_counts, out_entries, out_cap, stream, check):
+        """the accumulating row call of partial and syndrome"""
         import torch
         _rows(rows, "rows")
         S, H, P = rows.shape
@@ -623,12 +633,12 @@ class Plan:
             _rows(acc, "acc", R, S)
         if out.shape[2] != P or (acc is not None and acc.shape[2] != P):
             raise ValueError("rows, acc and out differ in width")
-        need = self._partial_need(H, R, S)
+        need = need_of(H, R, S)
         _flat(ctx, "ctx", need, (torch.uint8,))
         _oor(counts, entries, cap, S, H)
         _oor(acc_counts, acc_entries, acc_cap, S, R)
         _oor(out_counts, out_entries, out_cap, S, R)
-        rc = lib().qi_gpu_partial(
+        rc = fn(
             self.h, ctx.data_ptr(), H, R,
             rows.data_ptr(), rows.stride(0), rows.stride(1),
             _ptr(counts), _ptr(entries), int(cap),
@@ -636,7 +646,7 @@ class Plan:
             out.data_ptr(), out.stride(0), out.stride(1),
             _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
         if rc:
-            raise RuntimeError(f"qi_gpu_partial failed: {rc}")
+            raise RuntimeError(f"{name} failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
     SYNDROME_MAX_CHECKS = 8  # QI_SYNDROME_MAX_CHECKS
@@ -654,11 +664,9 @@ class Plan:
         return lib().qi_gpu_syndrome_ctx_bytes(self.h, n_held, n_checks, n_stripes)
 
     def _syndrome_need(self, H, R, S):
-        need = self.syndrome_ctx_bytes(H, R, S)
-        if need == 0 and S > 0:
-            raise ValueError(f"a syndrome share of {H} held rows with {R} checks is not "
-                             f"supported (1 <= R <= min(8, m), 1 <= H <= k + R)")
-        return need
+        return _need(self.syndrome_ctx_bytes(H, R, S), S,
+                     f"a syndrome share of {H} held rows with {R} checks is not "
+                     f"supported (1 <= R <= min(8, m), 1 <= H <= k + R)")
 
     def syndrome_ctx(self, ids, held, ctx, stream=None):
         """ids: int16 tensor [S, k + R] (the listed fragments; R = n_checks
@@ -685,30 +693,9 @@ class Plan:
         [S, H, P], row h the listed fragment at position held[s][h]; acc and
         out [S, R, P], row j = syndrome j, out may be acc itself.  Returns the
         sticky error flags when check."""
-        import torch
-        _rows(rows, "rows")
-        S, H, P = rows.shape
-        _rows(out, "out", None, S)
-        R = out.shape[1]
-        if acc is not None:
-            _rows(acc, "acc", R, S)
-        if out.shape[2] != P or (acc is not None and acc.shape[2] != P):
-            raise ValueError("rows, acc and out differ in width")
-        need = self._syndrome_need(H, R, S)
-        _flat(ctx, "ctx", need, (torch.uint8,))
-        _oor(counts, entries, cap, S, H)
-        _oor(acc_counts, acc_entries, acc_cap, S, R)
-        _oor(out_counts, out_entries, out_cap, S, R)
-        rc = lib().qi_gpu_syndrome(
-            self.h, ctx.data_ptr(), H, R,
-            rows.data_ptr(), rows.stride(0), rows.stride(1),
-            _ptr(counts), _ptr(entries), int(cap),
-            *_row_args(acc), _ptr(acc_counts), _ptr(acc_entries), int(acc_cap),
-            out.data_ptr(), out.stride(0), out.stride(1),
-            _ptr(out_counts), _ptr(out_entries), int(out_cap), P, S, self._stream(stream))
-        if rc:
-            raise RuntimeError(f"qi_gpu_syndrome failed: {rc}")
-        return lib().qi_gpu_take_error(self.h) if check else 0
+        return self._share(lib().qi_gpu_syndrome, "qi_gpu_syndrome", self._syndrome_need, ctx,
+                           rows, out, acc, counts, entries, cap, acc_counts, acc_entries, acc_cap,
+                           out_counts, out_entries, out_cap, stream, check)
 
     def syndrome_locate_kernels(self, n_checks, max_errors, words):
         """'syndrome_locate=<context kernel> + <kernel>'
@@ -723,11 +710,9 @@ class Plan:
         return lib().qi_gpu_syndrome_locate_ctx_bytes(self.h, n_checks, n_stripes)
 
     def _syndrome_locate_need(self, R, S):
-        need = self.syndrome_locate_ctx_bytes(R, S)
-        if need == 0 and S > 0:
-            raise ValueError(f"a syndrome locate with {R} checks is not supported "
-                             f"(1 <= R <= min(8, m))")
-        return need
+        return _need(self.syndrome_locate_ctx_bytes(R, S), S,
+                     f"a syndrome locate with {R} checks is not supported "
+                     f"(1 <= R <= min(8, m))")
 
     def syndrome_locate_ctx(self, ids, ctx, stream=None):
         """ids: int16 tensor [S, k + R], the listed fragments; R = n_checks
@@ -1236,38 +1221,49 @@ class Fec:
             raise ValueError("partial_repair_blocks: k ids and one row per held id")
         if len(hv) == 0:
             raise ValueError("partial_repair_blocks: shape not supported")
+        return self._share_blocks(
+            "partial_repair_blocks", "target", hv, rows, oor, counts, len(tg), acc, out_cap,
+            lambda held, out: lib().qi_fec_partial_repair_blocks(
+                self.h, idv.ctypes.data_as(C.c_void_p), *held, tg.ctypes.data_as(C.c_void_p),
+                len(tg), *out))
+
+    def _share_blocks(self, name, noun, hv, rows, oor, counts, R, acc, out_cap, call):
+        """The staging of partial_repair_blocks and syndrome_blocks: the held
+        rows and their marks, R output rows started from acc, and the call
+        again with the exact capacity when a mark list did not fit.
+        call(held, out): the C call, given its held-row and its output
+        arguments."""
+        import numpy as np
         B = len(rows[0])
         if oor is not None:
             oor = np.ascontiguousarray(oor, np.uint32).reshape(len(hv), -1)
             counts = np.ascontiguousarray(counts, np.uint32)
         if acc is not None:
             a_rows, a_oor, a_cnt = acc
-            if len(a_rows) != len(tg) or int(np.max(a_cnt, initial=0)) > a_oor.shape[1]:
-                raise ValueError("partial_repair_blocks: acc needs one row per target "
+            if len(a_rows) != R or int(np.max(a_cnt, initial=0)) > a_oor.shape[1]:
+                raise ValueError(f"{name}: acc needs one row per {noun} "
                                  "and complete mark lists")
             out_cap = max(out_cap, a_oor.shape[1])
         while True:
-            outs = [np.zeros(B, np.uint8) for _ in range(len(tg))]
-            o_oor = np.zeros((len(tg), out_cap), np.uint32)
-            o_cnt = np.zeros(len(tg), np.uint32)
+            outs = [np.zeros(B, np.uint8) for _ in range(R)]
+            o_oor = np.zeros((R, out_cap), np.uint32)
+            o_cnt = np.zeros(R, np.uint32)
             if acc is not None:
-                for j in range(len(tg)):
+                for j in range(R):
                     outs[j][:] = a_rows[j]
                 o_oor[:, :a_oor.shape[1]] = a_oor
                 o_cnt[:] = a_cnt
-            rc = lib().qi_fec_partial_repair_blocks(
-                self.h, idv.ctypes.data_as(C.c_void_p), hv.ctypes.data_as(C.c_void_p),
-                len(hv), ptr_array(list(rows)),
-                oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
-                counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
-                oor.shape[1] if oor is not None else 0,
-                tg.ctypes.data_as(C.c_void_p), len(tg), int(acc is not None),
-                ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
-                o_cnt.ctypes.data_as(C.c_void_p), out_cap, B)
+            rc = call(
+                (hv.ctypes.data_as(C.c_void_p), len(hv), ptr_array(list(rows)),
+                 oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                 counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
+                 oor.shape[1] if oor is not None else 0),
+                (int(acc is not None), ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
+                 o_cnt.ctypes.data_as(C.c_void_p), out_cap, B))
             if rc == -2:
-                raise ValueError("partial_repair_blocks: shape not supported")
+                raise ValueError(f"{name}: shape not supported")
             if rc != 1:
-                raise RuntimeError(f"qi_fec_partial_repair_blocks failed: {rc}")
+                raise RuntimeError(f"qi_fec_{name} failed: {rc}")
             if o_cnt.max(initial=0) <= out_cap:
                 return outs, o_oor, o_cnt
             out_cap = int(o_cnt.max())   # the list did not fit: once more
@@ -1290,40 +1286,10 @@ class Fec:
             raise ValueError("syndrome_blocks: one row per held id")
         if len(hv) == 0 or R < 1 or len(idv) != self.k + R:
             raise ValueError("syndrome_blocks: shape not supported")
-        B = len(rows[0])
-        if oor is not None:
-            oor = np.ascontiguousarray(oor, np.uint32).reshape(len(hv), -1)
-            counts = np.ascontiguousarray(counts, np.uint32)
-        if acc is not None:
-            a_rows, a_oor, a_cnt = acc
-            if len(a_rows) != R or int(np.max(a_cnt, initial=0)) > a_oor.shape[1]:
-                raise ValueError("syndrome_blocks: acc needs one row per check "
-                                 "and complete mark lists")
-            out_cap = max(out_cap, a_oor.shape[1])
-        while True:
-            outs = [np.zeros(B, np.uint8) for _ in range(R)]
-            o_oor = np.zeros((R, out_cap), np.uint32)
-            o_cnt = np.zeros(R, np.uint32)
-            if acc is not None:
-                for j in range(R):
-                    outs[j][:] = a_rows[j]
-                o_oor[:, :a_oor.shape[1]] = a_oor
-                o_cnt[:] = a_cnt
-            rc = lib().qi_fec_syndrome_blocks(
-                self.h, idv.ctypes.data_as(C.c_void_p), len(idv),
-                hv.ctypes.data_as(C.c_void_p), len(hv), ptr_array(list(rows)),
-                oor.ctypes.data_as(C.c_void_p) if oor is not None else None,
-                counts.ctypes.data_as(C.c_void_p) if oor is not None else None,
-                oor.shape[1] if oor is not None else 0, R, int(acc is not None),
-                ptr_array(outs), o_oor.ctypes.data_as(C.c_void_p),
-                o_cnt.ctypes.data_as(C.c_void_p), out_cap, B)
-            if rc == -2:
-                raise ValueError("syndrome_blocks: shape not supported")
-            if rc != 1:
-                raise RuntimeError(f"qi_fec_syndrome_blocks failed: {rc}")
-            if o_cnt.max(initial=0) <= out_cap:
-                return outs, o_oor, o_cnt
-            out_cap = int(o_cnt.max())   # the list did not fit: once more
+        return self._share_blocks(
+            "syndrome_blocks", "check", hv, rows, oor, counts, R, acc, out_cap,
+            lambda held, out: lib().qi_fec_syndrome_blocks(
+                self.h, idv.ctypes.data_as(C.c_void_p), len(idv), *held, R, *out))
 
     def locate_syndromes(self, listed_ids, rows, oor, counts, max_errors=1, fix_cap=256):
         """The coordinator's decision over the complete syndrome sums

@@ -469,6 +469,142 @@ Staged stage_fragments(qi_plan* pl, const stage::FragMap& map, const std::vector
     return st;
 }
 
+// The compact sibling, for the calls that address rows by position (update,
+// the shares, the syndrome locate): `n_rows` row slots in h.in, of which the
+// rows `up` are uploaded, in that order, to the slots they name; the M mark
+// groups' buckets (counts, then entries, per group) at the head of h.counts,
+// followed by `tail_bytes`; h.ids holds `hids`; h.ctx is reserved.  Uploads:
+// the rows, the marks, the ids.
+struct RowUpload {
+    const uint8_t* src;
+    size_t row;
+};
+
+template <size_t M>
+struct StagedRows {
+    size_t P;
+    uint16_t* din;
+    uint32_t *dcnt[M], *dent[M], *dtail;
+    const uint16_t* dids;
+    stage::PackedMarks pm[M];  // host side of the buckets: alive until the sync
+};
+
+template <size_t M>
+StagedRows<M> stage_rows(qi_plan* pl, size_t n_rows, const std::vector<RowUpload>& up,
+                         const std::vector<const Properties*> (&marks)[M], size_t words,
+                         size_t tail_bytes, const std::vector<uint16_t>& hids, size_t ctx_bytes)
+{
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    StagedRows<M> st;
+    const size_t P = st.P = pad_words(words);
+    size_t bytes[2 * M + 1];
+    for (size_t g = 0; g < M; g++) {
+        st.pm[g] = stage::pack_marks(marks[g], 0, words);
+        bytes[2 * g] = marks[g].size() * 4;
+        bytes[2 * g + 1] = st.pm[g].entries.size() * 4;
+    }
+    bytes[2 * M] = tail_bytes;
+    const auto off = stage::layout(bytes);
+    reserve(h.in, n_rows * P * 2);
+    reserve(h.counts, off[2 * M + 1]);
+    reserve(h.ids, hids.size() * 2);
+    reserve(h.ctx, ctx_bytes);
+    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
+    st.din = static_cast<uint16_t*>(h.in.p);
+    for (size_t g = 0; g < M; g++) {
+        st.dcnt[g] = reinterpret_cast<uint32_t*>(dcb + off[2 * g]);
+        st.dent[g] = reinterpret_cast<uint32_t*>(dcb + off[2 * g + 1]);
+    }
+    st.dtail = reinterpret_cast<uint32_t*>(dcb + off[2 * M]);
+    st.dids = static_cast<uint16_t*>(h.ids.p);
+    for (auto const& u : up)
+        h2d(st.din + u.row * P, u.src, words * 2, s);
+    for (size_t g = 0; g < M; g++)
+        upload_marks(st.pm[g], st.dcnt[g], st.dent[g], s);
+    h2d(h.ids.p, hids.data(), hids.size() * 2, s);
+    return st;
+}
+
+// The tail of every call that leaves R marked rows (repair, update, the
+// shares): launch(entries, cap) into the cleared counts `docnt`, first with
+// 64 + words / 512 entries per row and, if a row has more marks, once more
+// with the exact capacity after between() has put back what the first attempt
+// overwrote.  No error drain between the attempts: the sticky error is read
+// once, after the rows drows[j * P] are back in rows_out[j] (null: not
+// wanted).  Returns the R ascending mark lists.
+template <typename Launch, typename Between>
+std::vector<Properties> finish_marked_rows(qi_plan* pl, size_t R, size_t words, uint32_t* docnt,
+                                           Launch launch, Between between,
+                                           const uint16_t* drows, size_t P,
+                                           uint8_t* const* rows_out, const char* what)
+{
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    std::vector<uint32_t> ocnt(R);
+    const size_t ocap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, R * c * 4);
+            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+            launch(static_cast<uint32_t*>(h.entries.p), static_cast<int>(c));
+        },
+        [&] { return read_max(ocnt, docnt, s); }, between);
+    std::vector<uint32_t> ent(R * ocap);
+    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
+    for (size_t j = 0; j < R; j++)
+        if (rows_out[j])
+            d2h(rows_out[j], drows + j * P, words * 2, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error(std::string("RsFnt: ") + what +
+                                 " failed (bad ids or OOR bucket capacity)");
+    std::vector<Properties> marks(R);
+    for (size_t j = 0; j < R; j++)
+        stage::add_sorted(marks[j], ent.data() + j * ocap, ocnt[j], 0);
+    return marks;
+}
+
+// The tail of the two locates: launch(fixes, cap) leaves located[N],
+// unlocated, the fix count and the weights in `dres`, of which T_read words
+// are read back (the read synchronises).  A fix list longer than the capacity
+// is run again with the exact one; an overflowing fix list raises no error, so
+// there is nothing to drain.  Fills the reset `result`: fix positions become
+// fragment ids through `ids`.
+template <typename Launch>
+void finish_fix_list(qi_plan* pl, size_t words, size_t T_read, const uint32_t* dres,
+                     Launch launch, const std::vector<int>& ids, LocateResult& result,
+                     const char* what)
+{
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    const size_t N = ids.size();
+    std::vector<uint32_t> res(T_read);
+    const size_t fcap = stage::run_with_retry(
+        64 + words / 512,
+        [&](size_t c) {
+            reserve(h.entries, c * 3 * 4);
+            launch(static_cast<uint32_t*>(h.entries.p), static_cast<int>(c));
+        },
+        [&] {
+            d2h(res.data(), dres, T_read * 4, s);
+            check(hipStreamSynchronize(s), "sync");
+            return static_cast<size_t>(res[N + 1]);
+        },
+        [] {});
+    const size_t nfix = res[N + 1];
+    if (nfix > fcap)
+        throw std::runtime_error(std::string("RsFnt: ") + what + " fix list overflowed twice");
+    std::vector<uint32_t> fx(nfix * 3);
+    if (nfix)
+        d2h(fx.data(), h.entries.p, nfix * 3 * 4, s);
+    check(hipStreamSynchronize(s), "sync");
+    if (qi_gpu_take_error(pl))
+        throw std::runtime_error(std::string("RsFnt: ") + what +
+                                 " failed (bad ids or OOR bucket capacity)");
+    stage::fill_locate(result, ids, res.data(), fx.data(), nfix);
+}
+
 }  // namespace
 
 bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
@@ -521,32 +657,16 @@ bool RsFnt::repair_blocks_vertical(std::vector<uint8_t*>& data_bufs,
     check_rc(qi_gpu_repair_ctx(pl, dids, dids + k, static_cast<int>(R), 1, st.dcnt, st.dent, cap,
                                static_cast<long long>(words), h.ctx.p, s),
              "repair context");
-    // launch (no error drain between the attempts: the sticky error is read
-    // once, after the rows are back)
-    std::vector<uint32_t> ocnt(R);
-    const size_t ocap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, R * c * 4);
-            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+    // launch and collect (a null out_bufs[j] is a row not wanted)
+    out_props = finish_marked_rows(
+        pl, R, words, docnt,
+        [&](uint32_t* oent, int ocap) {
             check_rc(qi_gpu_repair(pl, h.ctx.p, static_cast<int>(R), st.din, 0, P, st.dcoded, 0,
-                                   P, st.dcnt, st.dent, cap, dout, 0, P, docnt,
-                                   static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                   P, st.dcnt, st.dent, cap, dout, 0, P, docnt, oent, ocap,
                                    static_cast<long long>(words), 1, s),
                      "repair");
         },
-        [&] { return read_max(ocnt, docnt, s); }, [] {});
-    // collect
-    std::vector<uint32_t> ent(R * ocap);
-    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
-    for (size_t j = 0; j < R; j++)
-        if (out_bufs[j])
-            d2h(out_bufs[j], dout + j * st.P, words * 2, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: repair failed (bad ids or OOR bucket capacity)");
-    for (size_t j = 0; j < R; j++)
-        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
+        [] {}, dout, st.P, out_bufs.data(), "repair");
     return true;
 }
 
@@ -687,10 +807,7 @@ int RsFnt::locate_run(std::vector<uint8_t*>& data_bufs, std::vector<uint8_t*>& p
     if (!locate_supported(block_size_bytes))
         throw std::invalid_argument("RsFnt::locate_blocks_vertical: unsupported shape");
     const std::vector<int> present = map.present(missing_idxs);
-    result.located.assign(code_len, -1);
-    result.unlocated = 0;
-    result.fixes.clear();
-    result.weights.assign(t, 0);
+    stage::reset_locate(result, code_len, t);
     const std::vector<int> ids = map.select_upto(present, n_data + QI_LOCATE_MAX_CHECKS);
     if (ids.size() < n_data + 2)
         return 0;
@@ -719,52 +836,23 @@ int RsFnt::locate_run(std::vector<uint8_t*>& data_bufs, std::vector<uint8_t*>& p
     h2d(h.ids.p, hids.data(), N * 2, s);
     check_rc(qi_gpu_locate_ctx(pl, static_cast<uint16_t*>(h.ids.p), R, 1, h.ctx.p, s),
              "locate context");
-    // launch: a fix list longer than the capacity is run again with the exact
-    // one (no error drain between the attempts: an overflowing fix list
-    // raises none)
-    std::vector<uint32_t> res(T);
-    const size_t fcap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, c * 3 * 4);
+    // launch and collect (the single locate writes no weights: N + 2 words)
+    finish_fix_list(
+        pl, words, t ? T : N + 2, dres,
+        [&](uint32_t* fixes, int fcap) {
+            const long long w = static_cast<long long>(words);
             if (t == 0)
                 check_rc(qi_gpu_locate(pl, h.ctx.p, R, nullptr, st.din, 0, P, st.dcoded, 0, P,
-                                       st.dcnt, st.dent, cap, dres, dres + N, dres + N + 1,
-                                       static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
-                                       static_cast<long long>(words), 1, s),
+                                       st.dcnt, st.dent, cap, dres, dres + N, dres + N + 1, fixes,
+                                       fcap, w, 1, s),
                          "locate");
             else
                 check_rc(qi_gpu_locate_multi(pl, h.ctx.p, R, t, nullptr, st.din, 0, P, st.dcoded,
                                              0, P, st.dcnt, st.dent, cap, dres, dres + N,
-                                             dres + N + 2, dres + N + 1,
-                                             static_cast<uint32_t*>(h.entries.p),
-                                             static_cast<int>(c), static_cast<long long>(words),
-                                             1, s),
+                                             dres + N + 2, dres + N + 1, fixes, fcap, w, 1, s),
                          "locate");
         },
-        [&] {
-            d2h(res.data(), dres, (t ? T : N + 2) * 4, s);
-            check(hipStreamSynchronize(s), "sync");
-            return static_cast<size_t>(res[N + 1]);
-        },
-        [] {});
-    // collect
-    const size_t nfix = res[N + 1];
-    if (nfix > fcap)
-        throw std::runtime_error("RsFnt: locate fix list overflowed twice");
-    std::vector<uint32_t> fx(nfix * 3);
-    if (nfix)
-        d2h(fx.data(), h.entries.p, nfix * 3 * 4, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: locate failed (bad ids or OOR bucket capacity)");
-    for (size_t i = 0; i < N; i++)
-        result.located[ids[i]] = static_cast<long long>(res[i]);
-    result.unlocated = static_cast<long long>(res[N]);
-    for (int nu = 0; nu < t; nu++)
-        result.weights[nu] = static_cast<long long>(res[N + 2 + nu]);
-    for (size_t e = 0; e < nfix; e++)
-        result.fixes.push_back(LocateFix{fx[3 * e], ids[fx[3 * e + 1]], fx[3 * e + 2]});
+        ids, result, "locate");
     if (!correct || result.fixes.empty() || result.unlocated != 0)
         return 1;
     if (!stage::apply_fixes(map, result.fixes, data_bufs, parities_bufs, parities_props,
@@ -896,76 +984,163 @@ void RsFnt::update_blocks_vertical(const std::vector<int>& ids, std::vector<uint
     hipStream_t s = h.stream;
     // stage: U old rows, U new rows, the R held rows (row j = held[j]: the
     // compact addressing of update_rows), their buckets, the output counts
-    std::vector<const Properties*> marked(R);
+    std::vector<const Properties*> marked[1] = {std::vector<const Properties*>(R)};
+    std::vector<uint8_t*> coded(R);
+    std::vector<RowUpload> up;
+    for (size_t u = 0; u < U; u++) {
+        up.push_back({old_bufs[u], u});
+        up.push_back({new_bufs[u], U + u});
+    }
     for (size_t j = 0; j < R; j++) {
         parities_props[held[j]].sort();
-        marked[j] = &parities_props[held[j]];
+        marked[0][j] = &parities_props[held[j]];
+        coded[j] = parities_bufs[held[j]];
+        up.push_back({coded[j], 2 * U + j});
     }
-    const stage::PackedMarks pm = stage::pack_marks(marked, 0, words);
-    const size_t P = pad_words(words);
-    const auto off = stage::layout({R * 4, pm.entries.size() * 4, R * 4});
-    const size_t ctx_bytes =
-        qi_gpu_update_ctx_bytes(pl, static_cast<int>(U), static_cast<int>(R), 1);
-    reserve(h.in, (2 * U + R) * P * 2);
-    reserve(h.counts, off[3]);
-    reserve(h.ids, (U + R) * 2);
-    reserve(h.ctx, ctx_bytes);
-    uint16_t* dold = static_cast<uint16_t*>(h.in.p);
-    uint16_t* dnew = dold + U * P;
-    uint16_t* dcoded = dnew + U * P;
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
-    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
-    const auto upload_coded = [&] {
-        for (size_t j = 0; j < R; j++)
-            h2d(dcoded + j * P, parities_bufs[held[j]], words * 2, s);
-    };
-    for (size_t u = 0; u < U; u++) {
-        h2d(dold + u * P, old_bufs[u], words * 2, s);
-        h2d(dnew + u * P, new_bufs[u], words * 2, s);
-    }
-    upload_coded();
-    upload_marks(pm, dcnt, dent, s);
     std::vector<uint16_t> hids(ids.begin(), ids.end());
     hids.insert(hids.end(), held.begin(), held.end());
-    h2d(h.ids.p, hids.data(), (U + R) * 2, s);
-    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
-    check_rc(qi_gpu_update_ctx(pl, dids, dids + U, static_cast<int>(U), static_cast<int>(R), 1,
-                               h.ctx.p, s),
+    const size_t ctx_bytes =
+        qi_gpu_update_ctx_bytes(pl, static_cast<int>(U), static_cast<int>(R), 1);
+    const StagedRows<1> st = stage_rows(pl, 2 * U + R, up, marked, words, R * 4, hids, ctx_bytes);
+    uint16_t* dold = st.din;
+    uint16_t* dnew = dold + U * st.P;
+    uint16_t* dcoded = dnew + U * st.P;
+    uint32_t* docnt = st.dtail;
+    check_rc(qi_gpu_update_ctx(pl, st.dids, st.dids + U, static_cast<int>(U),
+                               static_cast<int>(R), 1, h.ctx.p, s),
              "update context");
     // launch in place; a second attempt starts from the rows as they were
-    const long long Pl = static_cast<long long>(P);
-    std::vector<uint32_t> ocnt(R);
-    const size_t ocap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, R * c * 4);
-            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
+    const long long Pl = static_cast<long long>(st.P);
+    const std::vector<Properties> marks = finish_marked_rows(
+        pl, R, words, docnt,
+        [&](uint32_t* oent, int ocap) {
             check_rc(update_rows(pl, h.ctx.p, static_cast<int>(U), static_cast<int>(R), 1, dold,
-                                 0, Pl, dnew, 0, Pl, dcoded, 0, Pl, dcnt, dent,
-                                 static_cast<int>(pm.cap), dcoded, 0, Pl, docnt,
-                                 static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
+                                 0, Pl, dnew, 0, Pl, dcoded, 0, Pl, st.dcnt[0], st.dent[0],
+                                 static_cast<int>(st.pm[0].cap), dcoded, 0, Pl, docnt, oent, ocap,
                                  static_cast<long long>(words), 1, s),
                      "update");
         },
-        [&] { return read_max(ocnt, docnt, s); }, upload_coded);
-    // collect
-    std::vector<uint32_t> ent(R * ocap);
-    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
+        [&] {
+            for (size_t j = 0; j < R; j++)
+                h2d(dcoded + j * st.P, coded[j], words * 2, s);
+        },
+        dcoded, st.P, coded.data(), "update");
     for (size_t j = 0; j < R; j++)
-        d2h(parities_bufs[held[j]], dcoded + j * P, words * 2, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: update failed (bad ids or OOR bucket capacity)");
-    for (size_t j = 0; j < R; j++) {
-        parities_props[held[j]] = Properties();
-        stage::add_sorted(parities_props[held[j]], ent.data() + j * ocap, ocnt[j], 0);
-    }
+        parities_props[held[j]] = marks[j];
 }
 
-// ---- partial repair (single chunk; qi_gpu_partial_ctx, then the partial in
-// place on the staged acc rows) ----
+// ---- accumulating shares: partial repair and syndrome shares (single chunk;
+// the share's context call, then the row call in place on the staged acc
+// rows) ----
+namespace {
+
+// what tells the two shares apart
+struct ShareKind {
+    const char* fn;        // the public function: named by invalid_argument
+    const char* what;      // named by the runtime errors
+    const char* null_out;  // what a null out row is reported as
+    const char *ctx_name, *rows_name;
+    decltype(&qi_gpu_partial_ctx_bytes) ctx_bytes;
+    // the context from the device ids: `listed` ids, the H held positions,
+    // then the targets
+    int (*ctx)(qi_plan*, const uint16_t* dids, size_t listed, int H, int R, void* dctx,
+               hipStream_t s);
+    decltype(&qi_gpu_partial) rows;
+};
+
+const ShareKind kPartialShare = {
+    "RsFnt::partial_repair_blocks_vertical", "partial repair", "bad target", "partial context",
+    "partial", qi_gpu_partial_ctx_bytes,
+    [](qi_plan* pl, const uint16_t* dids, size_t listed, int H, int R, void* dctx,
+       hipStream_t s) {
+        return qi_gpu_partial_ctx(pl, dids, dids + listed, dids + listed + H, H, R, 1, dctx, s);
+    },
+    qi_gpu_partial};
+
+const ShareKind kSyndromeShare = {
+    "RsFnt::syndrome_blocks_vertical", "syndrome share", "buffers", "syndrome context",
+    "syndrome", qi_gpu_syndrome_ctx_bytes,
+    [](qi_plan* pl, const uint16_t* dids, size_t listed, int H, int R, void* dctx,
+       hipStream_t s) { return qi_gpu_syndrome_ctx(pl, dids, dids + listed, H, R, 1, dctx, s); },
+    qi_gpu_syndrome};
+
+// The share of the R output rows (the targets of a partial repair: then
+// `targets` names them; the checks of a syndrome share) that the holder of
+// `held_ids`, each one of `listed`, can form: added to out_bufs / out_props
+// when acc, else started from 0.  Shapes and buffer counts are the caller's
+// to check.
+void share_rows(qi_plan* pl, const stage::FragMap& map, const ShareKind& kind,
+                const std::vector<int>& listed, const std::vector<int>& held_ids,
+                std::vector<uint8_t*>& held_bufs, std::vector<Properties>& held_props,
+                const std::vector<int>& targets, size_t R, bool acc,
+                std::vector<uint8_t*>& out_bufs, std::vector<Properties>& out_props, size_t words)
+{
+    // validate; held fragment ids -> positions into listed
+    const auto bad = [&](const char* why) {
+        return std::invalid_argument(std::string(kind.fn) + ": " + why);
+    };
+    const size_t H = held_ids.size();
+    std::vector<uint16_t> pos;
+    const auto hc = stage::held_positions(map.code_len(), listed, targets, held_ids, pos);
+    if (hc == stage::HeldCheck::bad_id)
+        throw bad("bad id");
+    if (hc == stage::HeldCheck::bad_target ||
+        std::find(out_bufs.begin(), out_bufs.begin() + R, nullptr) != out_bufs.begin() + R)
+        throw bad(kind.null_out);
+    if (hc == stage::HeldCheck::bad_held ||
+        std::find(held_bufs.begin(), held_bufs.begin() + H, nullptr) != held_bufs.begin() + H)
+        throw bad("bad held id");
+    std::vector<uint16_t> hids(listed.begin(), listed.end());
+    hids.insert(hids.end(), pos.begin(), pos.end());
+    hids.insert(hids.end(), targets.begin(), targets.end());
+    HostState& h = pl->host;
+    hipStream_t s = h.stream;
+    // stage: the H held rows, the R output rows, the buckets of both, the
+    // output counts
+    std::vector<const Properties*> marked[2] = {std::vector<const Properties*>(H, nullptr),
+                                                std::vector<const Properties*>(R, nullptr)};
+    std::vector<RowUpload> up;
+    for (size_t hh = 0; hh < H; hh++) {
+        up.push_back({held_bufs[hh], hh});
+        if (map.slot(static_cast<unsigned>(held_ids[hh])).is_data)
+            continue;
+        held_props[hh].sort();
+        marked[0][hh] = &held_props[hh];
+    }
+    for (size_t j = 0; acc && j < R; j++) {
+        up.push_back({out_bufs[j], H + j});
+        out_props[j].sort();
+        marked[1][j] = &out_props[j];
+    }
+    const size_t ctx_bytes = kind.ctx_bytes(pl, static_cast<int>(H), static_cast<int>(R), 1);
+    const StagedRows<2> st = stage_rows(pl, H + R, up, marked, words, R * 4, hids, ctx_bytes);
+    uint16_t* dacc = st.din + H * st.P;
+    uint32_t* docnt = st.dtail;
+    check_rc(kind.ctx(pl, st.dids, listed.size(), static_cast<int>(H), static_cast<int>(R),
+                      h.ctx.p, s),
+             kind.ctx_name);
+    // launch in place; a second attempt starts from the acc rows as they were
+    const long long Pl = static_cast<long long>(st.P);
+    out_props = finish_marked_rows(
+        pl, R, words, docnt,
+        [&](uint32_t* oent, int ocap) {
+            check_rc(kind.rows(pl, h.ctx.p, static_cast<int>(H), static_cast<int>(R), st.din, 0,
+                               Pl, st.dcnt[0], st.dent[0], static_cast<int>(st.pm[0].cap),
+                               acc ? dacc : nullptr, 0, Pl, st.dcnt[1], st.dent[1],
+                               static_cast<int>(st.pm[1].cap), dacc, 0, Pl, docnt, oent, ocap,
+                               static_cast<long long>(words), 1, s),
+                     kind.rows_name);
+        },
+        [&] {
+            for (size_t j = 0; acc && j < R; j++)
+                h2d(dacc + j * st.P, out_bufs[j], words * 2, s);
+        },
+        dacc, st.P, out_bufs.data(), kind.what);
+}
+
+}  // namespace
+
+// ---- partial repair ----
 bool RsFnt::partial_supported(size_t n_held, size_t n_targets, size_t block_size_bytes) const
 {
     const size_t words = block_size_bytes / word_size;
@@ -987,119 +1162,17 @@ void RsFnt::partial_repair_blocks_vertical(const std::vector<int>& ids,
                                            std::vector<Properties>& out_props,
                                            size_t block_size_bytes)
 {
-    // validate; held fragment ids -> positions into ids
-    const stage::FragMap map = frag_map(*this);
     const size_t k = n_data, H = held_ids.size(), R = targets.size();
     if (!partial_supported(H, R, block_size_bytes))
         throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: unsupported shape");
     if (ids.size() != k || held_bufs.size() < H || held_props.size() < H || out_bufs.size() < R ||
         (acc && out_props.size() < R))
         throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: buffers");
-    std::vector<int> where(code_len, -1);  // fragment id -> position in ids, -2: a target
-    for (size_t i = 0; i < k; i++) {
-        if (ids[i] < 0 || ids[i] >= static_cast<int>(code_len) || where[ids[i]] != -1)
-            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad id");
-        where[ids[i]] = static_cast<int>(i);
-    }
-    for (size_t j = 0; j < R; j++) {
-        if (targets[j] < 0 || targets[j] >= static_cast<int>(code_len) ||
-            where[targets[j]] != -1 || !out_bufs[j])
-            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad target");
-        where[targets[j]] = -2;
-    }
-    std::vector<uint16_t> hids(ids.begin(), ids.end());
-    std::vector<char> taken(k, 0);
-    for (size_t hh = 0; hh < H; hh++) {
-        const int f = held_ids[hh];
-        if (f < 0 || f >= static_cast<int>(code_len) || where[f] < 0 || taken[where[f]] ||
-            !held_bufs[hh])
-            throw std::invalid_argument("RsFnt::partial_repair_blocks_vertical: bad held id");
-        taken[where[f]] = 1;
-        hids.push_back(static_cast<uint16_t>(where[f]));
-    }
-    hids.insert(hids.end(), targets.begin(), targets.end());
-    const size_t words = block_size_bytes / word_size;
-    qi_plan* pl = plan_;
-    HostState& h = pl->host;
-    hipStream_t s = h.stream;
-    // stage: the H held rows, the R partial rows, the buckets of both, the
-    // output counts
-    std::vector<const Properties*> hmarked(H, nullptr), amarked(R, nullptr);
-    for (size_t hh = 0; hh < H; hh++) {
-        if (map.slot(static_cast<unsigned>(held_ids[hh])).is_data)
-            continue;
-        held_props[hh].sort();
-        hmarked[hh] = &held_props[hh];
-    }
-    for (size_t j = 0; acc && j < R; j++) {
-        out_props[j].sort();
-        amarked[j] = &out_props[j];
-    }
-    const stage::PackedMarks pm = stage::pack_marks(hmarked, 0, words);
-    const stage::PackedMarks am = stage::pack_marks(amarked, 0, words);
-    const size_t P = pad_words(words);
-    const auto off = stage::layout(
-        {H * 4, pm.entries.size() * 4, R * 4, am.entries.size() * 4, R * 4});
-    const size_t ctx_bytes =
-        qi_gpu_partial_ctx_bytes(pl, static_cast<int>(H), static_cast<int>(R), 1);
-    reserve(h.in, (H + R) * P * 2);
-    reserve(h.counts, off[5]);
-    reserve(h.ids, hids.size() * 2);
-    reserve(h.ctx, ctx_bytes);
-    uint16_t* drows = static_cast<uint16_t*>(h.in.p);
-    uint16_t* dacc = drows + H * P;
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
-    uint32_t* dacnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
-    uint32_t* daent = reinterpret_cast<uint32_t*>(dcb + off[3]);
-    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[4]);
-    const auto upload_acc = [&] {
-        for (size_t j = 0; acc && j < R; j++)
-            h2d(dacc + j * P, out_bufs[j], words * 2, s);
-    };
-    for (size_t hh = 0; hh < H; hh++)
-        h2d(drows + hh * P, held_bufs[hh], words * 2, s);
-    upload_acc();
-    upload_marks(pm, dcnt, dent, s);
-    upload_marks(am, dacnt, daent, s);
-    h2d(h.ids.p, hids.data(), hids.size() * 2, s);
-    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
-    check_rc(qi_gpu_partial_ctx(pl, dids, dids + k, dids + k + H, static_cast<int>(H),
-                                static_cast<int>(R), 1, h.ctx.p, s),
-             "partial context");
-    // launch in place; a second attempt starts from the acc rows as they were
-    const long long Pl = static_cast<long long>(P);
-    std::vector<uint32_t> ocnt(R);
-    const size_t ocap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, R * c * 4);
-            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
-            check_rc(qi_gpu_partial(pl, h.ctx.p, static_cast<int>(H), static_cast<int>(R), drows,
-                                    0, Pl, dcnt, dent, static_cast<int>(pm.cap),
-                                    acc ? dacc : nullptr, 0, Pl, dacnt, daent,
-                                    static_cast<int>(am.cap), dacc, 0, Pl, docnt,
-                                    static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
-                                    static_cast<long long>(words), 1, s),
-                     "partial");
-        },
-        [&] { return read_max(ocnt, docnt, s); }, upload_acc);
-    // collect
-    std::vector<uint32_t> ent(R * ocap);
-    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
-    for (size_t j = 0; j < R; j++)
-        d2h(out_bufs[j], dacc + j * P, words * 2, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: partial repair failed (bad ids or OOR bucket capacity)");
-    out_props.assign(R, Properties());
-    for (size_t j = 0; j < R; j++)
-        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
+    share_rows(plan_, frag_map(*this), kPartialShare, ids, held_ids, held_bufs, held_props,
+               targets, R, acc, out_bufs, out_props, block_size_bytes / word_size);
 }
 
-// ---- syndrome shares (single chunk; qi_gpu_syndrome_ctx, then the share in
-// place on the staged acc rows; qi_gpu_syndrome_locate over the summed rows) ----
+// ---- syndrome shares, and qi_gpu_syndrome_locate over the summed rows ----
 bool RsFnt::syndrome_supported(size_t n_held, size_t n_checks, size_t block_size_bytes) const
 {
     const size_t words = block_size_bytes / word_size;
@@ -1119,113 +1192,14 @@ void RsFnt::syndrome_blocks_vertical(const std::vector<int>& listed_ids,
                                      std::vector<uint8_t*>& out_bufs,
                                      std::vector<Properties>& out_props, size_t block_size_bytes)
 {
-    // validate; held fragment ids -> positions into listed_ids
-    const stage::FragMap map = frag_map(*this);
     const size_t H = held_ids.size(), R = n_checks < 0 ? 0 : static_cast<size_t>(n_checks);
-    const size_t N = n_data + R;
     if (!syndrome_supported(H, R, block_size_bytes))
         throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: unsupported shape");
-    if (listed_ids.size() != N || held_bufs.size() < H || held_props.size() < H ||
+    if (listed_ids.size() != n_data + R || held_bufs.size() < H || held_props.size() < H ||
         out_bufs.size() < R || (acc && out_props.size() < R))
         throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: buffers");
-    std::vector<int> where(code_len, -1);  // fragment id -> position in listed_ids
-    for (size_t i = 0; i < N; i++) {
-        if (listed_ids[i] < 0 || listed_ids[i] >= static_cast<int>(code_len) ||
-            where[listed_ids[i]] != -1)
-            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: bad id");
-        where[listed_ids[i]] = static_cast<int>(i);
-    }
-    for (size_t j = 0; j < R; j++)
-        if (!out_bufs[j])
-            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: buffers");
-    std::vector<uint16_t> hids(listed_ids.begin(), listed_ids.end());
-    std::vector<char> taken(N, 0);
-    for (size_t hh = 0; hh < H; hh++) {
-        const int f = held_ids[hh];
-        if (f < 0 || f >= static_cast<int>(code_len) || where[f] < 0 || taken[where[f]] ||
-            !held_bufs[hh])
-            throw std::invalid_argument("RsFnt::syndrome_blocks_vertical: bad held id");
-        taken[where[f]] = 1;
-        hids.push_back(static_cast<uint16_t>(where[f]));
-    }
-    const size_t words = block_size_bytes / word_size;
-    qi_plan* pl = plan_;
-    HostState& h = pl->host;
-    hipStream_t s = h.stream;
-    // stage: the H held rows, the R syndrome rows, the buckets of both, the
-    // output counts
-    std::vector<const Properties*> hmarked(H, nullptr), amarked(R, nullptr);
-    for (size_t hh = 0; hh < H; hh++) {
-        if (map.slot(static_cast<unsigned>(held_ids[hh])).is_data)
-            continue;
-        held_props[hh].sort();
-        hmarked[hh] = &held_props[hh];
-    }
-    for (size_t j = 0; acc && j < R; j++) {
-        out_props[j].sort();
-        amarked[j] = &out_props[j];
-    }
-    const stage::PackedMarks pm = stage::pack_marks(hmarked, 0, words);
-    const stage::PackedMarks am = stage::pack_marks(amarked, 0, words);
-    const size_t P = pad_words(words);
-    const auto off = stage::layout(
-        {H * 4, pm.entries.size() * 4, R * 4, am.entries.size() * 4, R * 4});
-    const size_t ctx_bytes =
-        qi_gpu_syndrome_ctx_bytes(pl, static_cast<int>(H), static_cast<int>(R), 1);
-    reserve(h.in, (H + R) * P * 2);
-    reserve(h.counts, off[5]);
-    reserve(h.ids, hids.size() * 2);
-    reserve(h.ctx, ctx_bytes);
-    uint16_t* drows = static_cast<uint16_t*>(h.in.p);
-    uint16_t* dacc = drows + H * P;
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
-    uint32_t* dacnt = reinterpret_cast<uint32_t*>(dcb + off[2]);
-    uint32_t* daent = reinterpret_cast<uint32_t*>(dcb + off[3]);
-    uint32_t* docnt = reinterpret_cast<uint32_t*>(dcb + off[4]);
-    const auto upload_acc = [&] {
-        for (size_t j = 0; acc && j < R; j++)
-            h2d(dacc + j * P, out_bufs[j], words * 2, s);
-    };
-    for (size_t hh = 0; hh < H; hh++)
-        h2d(drows + hh * P, held_bufs[hh], words * 2, s);
-    upload_acc();
-    upload_marks(pm, dcnt, dent, s);
-    upload_marks(am, dacnt, daent, s);
-    h2d(h.ids.p, hids.data(), hids.size() * 2, s);
-    const uint16_t* dids = static_cast<uint16_t*>(h.ids.p);
-    check_rc(qi_gpu_syndrome_ctx(pl, dids, dids + N, static_cast<int>(H), static_cast<int>(R), 1,
-                                 h.ctx.p, s),
-             "syndrome context");
-    // launch in place; a second attempt starts from the acc rows as they were
-    const long long Pl = static_cast<long long>(P);
-    std::vector<uint32_t> ocnt(R);
-    const size_t ocap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, R * c * 4);
-            check_rc(qi_gpu_oor_clear(docnt, R, s), "oor_clear");
-            check_rc(qi_gpu_syndrome(pl, h.ctx.p, static_cast<int>(H), static_cast<int>(R), drows,
-                                     0, Pl, dcnt, dent, static_cast<int>(pm.cap),
-                                     acc ? dacc : nullptr, 0, Pl, dacnt, daent,
-                                     static_cast<int>(am.cap), dacc, 0, Pl, docnt,
-                                     static_cast<uint32_t*>(h.entries.p), static_cast<int>(c),
-                                     static_cast<long long>(words), 1, s),
-                     "syndrome");
-        },
-        [&] { return read_max(ocnt, docnt, s); }, upload_acc);
-    // collect
-    std::vector<uint32_t> ent(R * ocap);
-    d2h(ent.data(), h.entries.p, R * ocap * 4, s);
-    for (size_t j = 0; j < R; j++)
-        d2h(out_bufs[j], dacc + j * P, words * 2, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: syndrome share failed (bad ids or OOR bucket capacity)");
-    out_props.assign(R, Properties());
-    for (size_t j = 0; j < R; j++)
-        stage::add_sorted(out_props[j], ent.data() + j * ocap, ocnt[j], 0);
+    share_rows(plan_, frag_map(*this), kSyndromeShare, listed_ids, held_ids, held_bufs, held_props,
+               {}, R, acc, out_bufs, out_props, block_size_bytes / word_size);
 }
 
 void RsFnt::locate_syndromes(const std::vector<int>& listed_ids, std::vector<uint8_t*>& syn_bufs,
@@ -1246,84 +1220,41 @@ void RsFnt::locate_syndromes(const std::vector<int>& listed_ids, std::vector<uin
             throw std::invalid_argument("RsFnt::locate_syndromes: bad id");
         seen[f] = 1;
     }
-    result.located.assign(code_len, -1);
-    result.unlocated = 0;
-    result.fixes.clear();
-    result.weights.assign(t, 0);
+    stage::reset_locate(result, code_len, t);
     const size_t words = block_size_bytes / word_size;
     qi_plan* pl = plan_;
     HostState& h = pl->host;
     hipStream_t s = h.stream;
     // stage: the R syndrome rows, their buckets, then located[N], unlocated,
     // the fix count and the weights
-    std::vector<const Properties*> marked(R, nullptr);
+    std::vector<const Properties*> marked[1] = {std::vector<const Properties*>(R, nullptr)};
+    std::vector<RowUpload> up;
     for (size_t j = 0; j < R; j++) {
         if (!syn_bufs[j])
             throw std::invalid_argument("RsFnt::locate_syndromes: buffers");
         syn_props[j].sort();
-        marked[j] = &syn_props[j];
+        marked[0][j] = &syn_props[j];
+        up.push_back({syn_bufs[j], j});
     }
-    const stage::PackedMarks pm = stage::pack_marks(marked, 0, words);
-    const size_t P = pad_words(words);
     const size_t T = N + 2 + QI_SYNDROME_MAX_ERRORS;
-    const auto off = stage::layout({R * 4, pm.entries.size() * 4, T * 4});
-    const size_t ctx_bytes = qi_gpu_syndrome_locate_ctx_bytes(pl, static_cast<int>(R), 1);
-    reserve(h.in, R * P * 2);
-    reserve(h.counts, off[3]);
-    reserve(h.ids, N * 2);
-    reserve(h.ctx, ctx_bytes);
-    uint16_t* dsyn = static_cast<uint16_t*>(h.in.p);
-    uint8_t* dcb = static_cast<uint8_t*>(h.counts.p);
-    uint32_t* dcnt = reinterpret_cast<uint32_t*>(dcb + off[0]);
-    uint32_t* dent = reinterpret_cast<uint32_t*>(dcb + off[1]);
-    uint32_t* dres = reinterpret_cast<uint32_t*>(dcb + off[2]);
-    for (size_t j = 0; j < R; j++)
-        h2d(dsyn + j * P, syn_bufs[j], words * 2, s);
-    upload_marks(pm, dcnt, dent, s);
     const std::vector<uint16_t> hids(listed_ids.begin(), listed_ids.end());
-    h2d(h.ids.p, hids.data(), N * 2, s);
-    check_rc(qi_gpu_syndrome_locate_ctx(pl, static_cast<uint16_t*>(h.ids.p), static_cast<int>(R),
-                                        1, h.ctx.p, s),
+    const size_t ctx_bytes = qi_gpu_syndrome_locate_ctx_bytes(pl, static_cast<int>(R), 1);
+    const StagedRows<1> st = stage_rows(pl, R, up, marked, words, T * 4, hids, ctx_bytes);
+    uint32_t* dres = st.dtail;
+    check_rc(qi_gpu_syndrome_locate_ctx(pl, st.dids, static_cast<int>(R), 1, h.ctx.p, s),
              "syndrome locate context");
-    // launch: a fix list longer than the capacity is run again with the exact
-    // one (an overflowing fix list raises no error)
-    std::vector<uint32_t> res(T);
-    const size_t fcap = stage::run_with_retry(
-        64 + words / 512,
-        [&](size_t c) {
-            reserve(h.entries, c * 3 * 4);
-            check_rc(qi_gpu_syndrome_locate(pl, h.ctx.p, static_cast<int>(R), t, dsyn, 0,
-                                            static_cast<long long>(P), dcnt, dent,
-                                            static_cast<int>(pm.cap), dres, dres + N,
-                                            dres + N + 2, dres + N + 1,
-                                            static_cast<uint32_t*>(h.entries.p),
-                                            static_cast<int>(c), static_cast<long long>(words), 1,
-                                            s),
+    // launch and collect
+    finish_fix_list(
+        pl, words, T, dres,
+        [&](uint32_t* fixes, int fcap) {
+            check_rc(qi_gpu_syndrome_locate(pl, h.ctx.p, static_cast<int>(R), t, st.din, 0,
+                                            static_cast<long long>(st.P), st.dcnt[0], st.dent[0],
+                                            static_cast<int>(st.pm[0].cap), dres, dres + N,
+                                            dres + N + 2, dres + N + 1, fixes, fcap,
+                                            static_cast<long long>(words), 1, s),
                      "syndrome locate");
         },
-        [&] {
-            d2h(res.data(), dres, T * 4, s);
-            check(hipStreamSynchronize(s), "sync");
-            return static_cast<size_t>(res[N + 1]);
-        },
-        [] {});
-    // collect
-    const size_t nfix = res[N + 1];
-    if (nfix > fcap)
-        throw std::runtime_error("RsFnt: syndrome locate fix list overflowed twice");
-    std::vector<uint32_t> fx(nfix * 3);
-    if (nfix)
-        d2h(fx.data(), h.entries.p, nfix * 3 * 4, s);
-    check(hipStreamSynchronize(s), "sync");
-    if (qi_gpu_take_error(pl))
-        throw std::runtime_error("RsFnt: syndrome locate failed (bad ids or OOR bucket capacity)");
-    for (size_t i = 0; i < N; i++)
-        result.located[listed_ids[i]] = static_cast<long long>(res[i]);
-    result.unlocated = static_cast<long long>(res[N]);
-    for (int nu = 0; nu < t; nu++)
-        result.weights[nu] = static_cast<long long>(res[N + 2 + nu]);
-    for (size_t e = 0; e < nfix; e++)
-        result.fixes.push_back(LocateFix{fx[3 * e], listed_ids[fx[3 * e + 1]], fx[3 * e + 2]});
+        listed_ids, result, "syndrome locate");
 }
 
 long long RsFnt::apply_deltas(const std::vector<int>& fragment_ids, std::vector<uint8_t*>& bufs,
@@ -1354,10 +1285,7 @@ int RsFnt::scrub_blocks_vertical(std::vector<uint8_t*>& data_bufs,
         throw std::invalid_argument("RsFnt::scrub_blocks_vertical: max_errors");
     const stage::FragMap map = frag_map(*this);
     const std::vector<int> present = map.present(missing_idxs);
-    result.located.assign(code_len, -1);
-    result.unlocated = 0;
-    result.fixes.clear();
-    result.weights.assign(max_errors, 0);
+    stage::reset_locate(result, code_len, max_errors);
     const std::vector<int> ids = map.select_upto(present, n_data + QI_SYNDROME_MAX_CHECKS);
     if (ids.size() < n_data + std::max(1, 2 * max_errors))
         return 0;
@@ -2149,6 +2077,26 @@ struct FlatFragments {
     }
 };
 
+// the two shares on flat arrays: n_listed listed ids, n_held held rows with
+// their marks (oor_count null: none), n_out output rows whose marks are read
+// first when acc; share(listed, held, rows, marks, out rows, out marks)
+template <typename Share>
+int share_blocks_flat(const int* listed, size_t n_listed, const int* held_ids, int n_held,
+                      uint8_t** rows, const uint32_t* oor, const uint32_t* oor_count, uint32_t cap,
+                      int n_out, int acc, uint8_t** out, uint32_t* out_oor, uint32_t* out_count,
+                      uint32_t out_cap, Share share)
+{
+    std::vector<int> iv(listed, listed + n_listed), hv(held_ids, held_ids + n_held);
+    std::vector<uint8_t*> rv(rows, rows + n_held), ov(out, out + n_out);
+    std::vector<qi::Properties> hp(static_cast<size_t>(n_held)), op(static_cast<size_t>(n_out));
+    stage::props_from_flat(hp, oor, nullptr, oor_count, cap);
+    if (acc)
+        stage::props_from_flat(op, out_oor, nullptr, out_count, out_cap);
+    share(iv, hv, rv, hp, ov, op);
+    stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
+    return 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2272,9 +2220,7 @@ int qi_fec_locate_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t
         const int rc = f.locate_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res,
                                                 correct != 0, block_bytes,
                                                 oor_count ? cap : 0);
-        for (unsigned i = 0; i < f.code_len; i++)
-            result[i] = res.located[i];
-        result[f.code_len] = res.unlocated;
+        stage::locate_to_flat(res, result);
         if (rc == 2 && oor_count)
             stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
         return rc;
@@ -2301,11 +2247,7 @@ int qi_fec_locate_multi_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, ui
         const int rc = f.locate_multi_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res,
                                                       max_errors, correct != 0, block_bytes,
                                                       oor_count ? cap : 0);
-        for (unsigned i = 0; i < f.code_len; i++)
-            result[i] = res.located[i];
-        result[f.code_len] = res.unlocated;
-        for (int nu = 0; nu < max_errors; nu++)
-            result[f.code_len + 1 + nu] = res.weights[nu];
+        stage::locate_to_flat(res, result);
         if (rc == 2 && oor_count)
             stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
         return rc;
@@ -2395,18 +2337,14 @@ int qi_fec_partial_repair_blocks(qi_fec* h, const int* ids, const int* held_ids,
         if (!f.partial_supported(static_cast<size_t>(n_held), static_cast<size_t>(n_targets),
                                  block_bytes))
             return -2;
-        std::vector<int> iv(ids, ids + f.n_data), hv(held_ids, held_ids + n_held),
-            tv(targets, targets + n_targets);
-        std::vector<uint8_t*> rv(rows, rows + n_held), ov(out, out + n_targets);
-        // (oor_count null: no marks)
-        std::vector<qi::Properties> hp(static_cast<size_t>(n_held)),
-            op(static_cast<size_t>(n_targets));
-        qi::fec::stage::props_from_flat(hp, oor, nullptr, oor_count, cap);
-        if (acc)
-            qi::fec::stage::props_from_flat(op, out_oor, nullptr, out_count, out_cap);
-        f.partial_repair_blocks_vertical(iv, hv, rv, hp, tv, acc != 0, ov, op, block_bytes);
-        qi::fec::stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
-        return 1;
+        const std::vector<int> tv(targets, targets + n_targets);
+        return share_blocks_flat(
+            ids, f.n_data, held_ids, n_held, rows, oor, oor_count, cap, n_targets, acc, out,
+            out_oor, out_count, out_cap,
+            [&](auto& iv, auto& hv, auto& rv, auto& hp, auto& ov, auto& op) {
+                f.partial_repair_blocks_vertical(iv, hv, rv, hp, tv, acc != 0, ov, op,
+                                                 block_bytes);
+            });
     } catch (...) {
         return -1;
     }
@@ -2427,17 +2365,13 @@ int qi_fec_syndrome_blocks(qi_fec* h, const int* listed_ids, int n_listed, const
                                   block_bytes) ||
             static_cast<size_t>(n_listed) != f.n_data + static_cast<size_t>(n_checks))
             return -2;
-        std::vector<int> iv(listed_ids, listed_ids + n_listed), hv(held_ids, held_ids + n_held);
-        std::vector<uint8_t*> rv(rows, rows + n_held), ov(out, out + n_checks);
-        // (oor_count null: no marks)
-        std::vector<qi::Properties> hp(static_cast<size_t>(n_held)),
-            op(static_cast<size_t>(n_checks));
-        qi::fec::stage::props_from_flat(hp, oor, nullptr, oor_count, cap);
-        if (acc)
-            qi::fec::stage::props_from_flat(op, out_oor, nullptr, out_count, out_cap);
-        f.syndrome_blocks_vertical(iv, hv, rv, hp, n_checks, acc != 0, ov, op, block_bytes);
-        qi::fec::stage::props_to_flat(op, out_oor, nullptr, out_count, out_cap);
-        return 1;
+        return share_blocks_flat(
+            listed_ids, n_listed, held_ids, n_held, rows, oor, oor_count, cap, n_checks, acc, out,
+            out_oor, out_count, out_cap,
+            [&](auto& iv, auto& hv, auto& rv, auto& hp, auto& ov, auto& op) {
+                f.syndrome_blocks_vertical(iv, hv, rv, hp, n_checks, acc != 0, ov, op,
+                                           block_bytes);
+            });
     } catch (...) {
         return -1;
     }
@@ -2463,11 +2397,7 @@ int qi_fec_locate_syndromes(qi_fec* h, const int* listed_ids, int n_listed, uint
         qi::fec::stage::props_from_flat(sp, oor, nullptr, oor_count, cap);
         qi::fec::LocateResult res;
         f.locate_syndromes(iv, rv, sp, max_errors, res, block_bytes);
-        for (unsigned i = 0; i < f.code_len; i++)
-            result[i] = res.located[i];
-        result[f.code_len] = res.unlocated;
-        for (int nu = 0; nu < max_errors; nu++)
-            result[f.code_len + 1 + nu] = res.weights[nu];
+        stage::locate_to_flat(res, result);
         *n_fixes = static_cast<uint32_t>(res.fixes.size());
         for (size_t e = 0; e < res.fixes.size() && e < fix_cap; e++) {
             fixes[3 * e] = res.fixes[e].column;
@@ -2524,11 +2454,7 @@ int qi_fec_scrub_blocks(qi_fec* h, uint8_t** data, uint8_t** parities, uint32_t*
         qi::fec::LocateResult res;
         const int rc = f.scrub_blocks_vertical(fr.dv, fr.pv, fr.props, fr.miss, res, max_errors,
                                                correct != 0, block_bytes, oor_count ? cap : 0);
-        for (unsigned i = 0; i < f.code_len; i++)
-            result[i] = res.located[i];
-        result[f.code_len] = res.unlocated;
-        for (int nu = 0; nu < max_errors; nu++)
-            result[f.code_len + 1 + nu] = res.weights[nu];
+        stage::locate_to_flat(res, result);
         if (rc == 2 && oor_count)
             stage::props_to_flat(fr.props, oor, nullptr, oor_count, cap);
         return rc;

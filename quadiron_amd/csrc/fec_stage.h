@@ -1,7 +1,8 @@
 // fec_stage.h -- the host facade's staging steps that need no device: which
 // fragments a decode uses and where each one lives, OOR marks packed into the
 // device's counts + entries[cap] form, the layout of the small device buffer,
-// the bounded capacity retry, and the flat C arrays <-> Properties.  No HIP,
+// the bounded capacity retry, the held ids of a share as list positions, a
+// locate's result words, and the flat C arrays <-> Properties.  No HIP,
 // no plan: fec.cpp and quadiron_c.cpp build on it, and
 // tests/host/test_fec_stage.cpp checks it on the CPU.
 #pragma once
@@ -312,6 +313,78 @@ inline long long apply_deltas(const FragMap& map, const std::vector<int>& fragme
             props[h] = coded_props[fs.slot];
     }
     return static_cast<long long>(fixes.size());
+}
+
+// ---- held ids -> list positions ----------------------------------------------
+// A share (partial repair, syndrome) names the fragments its context lists,
+// the fragments to rebuild and the fragments the caller holds.  Checked in
+// this order, the first failure reported: every listed id is below code_len
+// and listed once (bad_id); every target is below code_len, not listed and
+// named once (bad_target); every held id is listed and held once (bad_held).
+// pos[h]: the position of held[h] in `listed`.
+enum class HeldCheck { ok, bad_id, bad_target, bad_held };
+
+inline HeldCheck held_positions(unsigned code_len, const std::vector<int>& listed,
+                                const std::vector<int>& targets, const std::vector<int>& held,
+                                std::vector<uint16_t>& pos)
+{
+    const auto in_range = [&](int f) { return f >= 0 && static_cast<unsigned>(f) < code_len; };
+    std::vector<int> where(code_len, -1);  // fragment id -> position in listed, -2: a target
+    for (size_t i = 0; i < listed.size(); i++) {
+        if (!in_range(listed[i]) || where[listed[i]] != -1)
+            return HeldCheck::bad_id;
+        where[listed[i]] = static_cast<int>(i);
+    }
+    for (int t : targets) {
+        if (!in_range(t) || where[t] != -1)
+            return HeldCheck::bad_target;
+        where[t] = -2;
+    }
+    pos.clear();
+    std::vector<char> taken(listed.size(), 0);
+    for (int f : held) {
+        if (!in_range(f) || where[f] < 0 || taken[where[f]])
+            return HeldCheck::bad_held;
+        taken[where[f]] = 1;
+        pos.push_back(static_cast<uint16_t>(where[f]));
+    }
+    return HeldCheck::ok;
+}
+
+// ---- locate results -----------------------------------------------------------
+// What a locate starts from: no fragment listed, nothing found, t weights.
+inline void reset_locate(LocateResult& r, unsigned code_len, int t)
+{
+    r.located.assign(code_len, -1);
+    r.unlocated = 0;
+    r.fixes.clear();
+    r.weights.assign(t, 0);
+}
+
+// The device's result words over the N = ids.size() listed fragments --
+// located[N], unlocated, the fix count, then the weights -- and its nfix fix
+// triples {column, list position, symbol} into a reset LocateResult of t
+// weights: positions become fragment ids through `ids`.
+inline void fill_locate(LocateResult& r, const std::vector<int>& ids, const uint32_t* res,
+                        const uint32_t* fx, size_t nfix)
+{
+    const size_t N = ids.size();
+    for (size_t i = 0; i < N; i++)
+        r.located[ids[i]] = static_cast<long long>(res[i]);
+    r.unlocated = static_cast<long long>(res[N]);
+    for (size_t nu = 0; nu < r.weights.size(); nu++)
+        r.weights[nu] = static_cast<long long>(res[N + 2 + nu]);
+    for (size_t e = 0; e < nfix; e++)
+        r.fixes.push_back(LocateFix{fx[3 * e], ids[fx[3 * e + 1]], fx[3 * e + 2]});
+}
+
+// LocateResult -> the C views' result words: located per fragment id,
+// unlocated, then the weights
+inline void locate_to_flat(const LocateResult& r, long long* result)
+{
+    long long* at = std::copy(r.located.begin(), r.located.end(), result);
+    *at++ = r.unlocated;
+    std::copy(r.weights.begin(), r.weights.end(), at);
 }
 
 // ---- flat C arrays <-> Properties ---------------------------------------

@@ -711,20 +711,23 @@ int qi_gpu_partial_ctx(qi_plan* p, const uint16_t* d_ids, const uint16_t* d_held
                               static_cast<int32_t*>(d_ctx), p->d_err, st(stream));
 }
 
-int qi_gpu_partial(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t* d_rows,
-                   long long rss, long long rrs, const uint32_t* d_in_counts,
-                   const uint32_t* d_in_entries, int in_cap, const uint16_t* d_acc, long long ass,
-                   long long ars, const uint32_t* d_acc_counts, const uint32_t* d_acc_entries,
-                   int acc_cap, uint16_t* d_out, long long oss, long long ors,
-                   uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap, long long words,
-                   int n_stripes, void* stream)
+// the accumulating row call of a partial repair and of a syndrome share: they
+// differ in which counts `ok` admits
+static int accumulate_rows(bool (*ok)(const qi_plan*, int, int), qi_plan* p, const void* d_ctx,
+                           int H, int R, const uint16_t* d_rows, long long rss, long long rrs,
+                           const uint32_t* d_in_counts, const uint32_t* d_in_entries, int in_cap,
+                           const uint16_t* d_acc, long long ass, long long ars,
+                           const uint32_t* d_acc_counts, const uint32_t* d_acc_entries,
+                           int acc_cap, uint16_t* d_out, long long oss, long long ors,
+                           uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
+                           long long words, int n_stripes, void* stream)
 {
     if (!p || !d_ctx || !d_rows || !d_out || n_stripes < 0 || words < 0 || in_cap < 0 ||
         acc_cap < 0 || out_cap < 0 || (d_in_counts && in_cap > 0 && !d_in_entries) ||
         (d_acc_counts && acc_cap > 0 && !d_acc_entries) ||
         (d_out_counts && out_cap > 0 && !d_out_entries))
         return -1;
-    if (!partial_ok(p, H, R))
+    if (!ok(p, H, R))
         return -1;
     if (n_stripes == 0 || words == 0)
         return 0;
@@ -737,6 +740,20 @@ int qi_gpu_partial(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t* 
     return launch_partial(static_cast<const int32_t*>(d_ctx), H, R, p->sys ? p->k : 0, d_rows, rss,
                           rrs, in, d_acc, ass, ars, accm, d_out, oss, ors, outm, words, n_stripes,
                           p->d_err, st(stream));
+}
+
+int qi_gpu_partial(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t* d_rows,
+                   long long rss, long long rrs, const uint32_t* d_in_counts,
+                   const uint32_t* d_in_entries, int in_cap, const uint16_t* d_acc, long long ass,
+                   long long ars, const uint32_t* d_acc_counts, const uint32_t* d_acc_entries,
+                   int acc_cap, uint16_t* d_out, long long oss, long long ors,
+                   uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap, long long words,
+                   int n_stripes, void* stream)
+{
+    return accumulate_rows(partial_ok, p, d_ctx, H, R, d_rows, rss, rrs, d_in_counts, d_in_entries,
+                           in_cap, d_acc, ass, ars, d_acc_counts, d_acc_entries, acc_cap, d_out,
+                           oss, ors, d_out_counts, d_out_entries, out_cap, words, n_stripes,
+                           stream);
 }
 
 const char* qi_gpu_partial_kernels(const qi_plan* p, int H, int R, long long words)
@@ -798,24 +815,10 @@ int qi_gpu_syndrome(qi_plan* p, const void* d_ctx, int H, int R, const uint16_t*
                     long long ors, uint32_t* d_out_counts, uint32_t* d_out_entries, int out_cap,
                     long long words, int n_stripes, void* stream)
 {
-    if (!p || !d_ctx || !d_rows || !d_out || n_stripes < 0 || words < 0 || in_cap < 0 ||
-        acc_cap < 0 || out_cap < 0 || (d_in_counts && in_cap > 0 && !d_in_entries) ||
-        (d_acc_counts && acc_cap > 0 && !d_acc_entries) ||
-        (d_out_counts && out_cap > 0 && !d_out_entries))
-        return -1;
-    if (!syndrome_ok(p, H, R))
-        return -1;
-    if (n_stripes == 0 || words == 0)
-        return 0;
-    const Oor in{const_cast<uint32_t*>(d_in_counts), const_cast<uint32_t*>(d_in_entries), H,
-                 in_cap};
-    // (no acc rows: no acc marks)
-    const Oor accm{d_acc ? const_cast<uint32_t*>(d_acc_counts) : nullptr,
-                   const_cast<uint32_t*>(d_acc_entries), R, acc_cap};
-    const Oor outm{d_out_counts, d_out_entries, R, out_cap};
-    return launch_partial(static_cast<const int32_t*>(d_ctx), H, R, p->sys ? p->k : 0, d_rows, rss,
-                          rrs, in, d_acc, ass, ars, accm, d_out, oss, ors, outm, words, n_stripes,
-                          p->d_err, st(stream));
+    return accumulate_rows(syndrome_ok, p, d_ctx, H, R, d_rows, rss, rrs, d_in_counts,
+                           d_in_entries, in_cap, d_acc, ass, ars, d_acc_counts, d_acc_entries,
+                           acc_cap, d_out, oss, ors, d_out_counts, d_out_entries, out_cap, words,
+                           n_stripes, stream);
 }
 
 const char* qi_gpu_syndrome_kernels(const qi_plan* p, int H, int R, long long words)

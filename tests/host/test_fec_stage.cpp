@@ -194,6 +194,78 @@ static void test_entries_and_flat()
     CHECK(rc[0] == 2 && rc[1] == 0);
 }
 
+static void test_held_positions()
+{
+    using H = std::vector<uint16_t>;
+    const unsigned code_len = 8;
+    const V listed{5, 0, 7, 2};
+    H pos{9};
+    // positions in list order of the held ids; targets are the ids not listed
+    CHECK(held_positions(code_len, listed, {1, 6}, {2, 5}, pos) == HeldCheck::ok);
+    CHECK(pos == (H{3, 0}));
+    CHECK(held_positions(code_len, listed, {}, {7, 2, 0, 5}, pos) == HeldCheck::ok);
+    CHECK(pos == (H{2, 3, 1, 0}));
+    CHECK(held_positions(code_len, listed, {}, {}, pos) == HeldCheck::ok && pos.empty());
+    // a listed id: repeated, == code_len, negative
+    CHECK(held_positions(code_len, {5, 0, 5, 2}, {}, {0}, pos) == HeldCheck::bad_id);
+    CHECK(held_positions(code_len, {5, 0, 8, 2}, {}, {0}, pos) == HeldCheck::bad_id);
+    CHECK(held_positions(code_len, {5, 0, -1, 2}, {}, {0}, pos) == HeldCheck::bad_id);
+    // a target: listed, repeated, == code_len
+    CHECK(held_positions(code_len, listed, {1, 7}, {0}, pos) == HeldCheck::bad_target);
+    CHECK(held_positions(code_len, listed, {1, 1}, {0}, pos) == HeldCheck::bad_target);
+    CHECK(held_positions(code_len, listed, {8}, {0}, pos) == HeldCheck::bad_target);
+    // a held id: not listed, repeated, == code_len, a target
+    CHECK(held_positions(code_len, listed, {}, {3}, pos) == HeldCheck::bad_held);
+    CHECK(held_positions(code_len, listed, {}, {0, 2, 0}, pos) == HeldCheck::bad_held);
+    CHECK(held_positions(code_len, listed, {}, {8}, pos) == HeldCheck::bad_held);
+    CHECK(held_positions(code_len, listed, {1, 6}, {0, 6}, pos) == HeldCheck::bad_held);
+    // the first failing check is the one reported
+    CHECK(held_positions(code_len, {5, 5}, {5}, {3}, pos) == HeldCheck::bad_id);
+    CHECK(held_positions(code_len, listed, {0}, {3}, pos) == HeldCheck::bad_target);
+}
+
+static void test_locate_results()
+{
+    using LL = std::vector<long long>;
+    // N = 3 listed fragments of a code of 6: located[3], unlocated, nfix, weights[t]
+    const V ids{4, 0, 3};
+    const uint32_t res[3 + 2 + 4] = {7, 0, 2, 5, 2, 6, 1, 99, 99};
+    const uint32_t fx[6] = {10, 2, 65536, 11, 0, 0};
+    LocateResult r;
+    r.located = {1, 2};
+    r.unlocated = 9;
+    r.fixes.push_back(LocateFix{1, 1, 1});
+    r.weights = {3};
+    reset_locate(r, 6, 2);
+    CHECK(r.located == (LL{-1, -1, -1, -1, -1, -1}) && r.unlocated == 0 && r.fixes.empty() &&
+          r.weights == (LL{0, 0}));
+    fill_locate(r, ids, res, fx, 2);
+    CHECK(r.located == (LL{0, -1, -1, 2, 7, -1}) && r.unlocated == 5 && r.weights == (LL{6, 1}));
+    // positions 2 and 0 of the list are fragments 3 and 4
+    CHECK(r.fixes.size() == 2 && r.fixes[0].column == 10 && r.fixes[0].fragment == 3 &&
+          r.fixes[0].symbol == 65536 && r.fixes[1].column == 11 && r.fixes[1].fragment == 4 &&
+          r.fixes[1].symbol == 0);
+    long long flat[10];
+    for (auto& v : flat)
+        v = 77;
+    locate_to_flat(r, flat);
+    CHECK((LL(flat, flat + 10)) == (LL{0, -1, -1, 2, 7, -1, 5, 6, 1, 77}));
+    // t = 0: no weight is read or written; nfix = 0: no fix, a null list
+    reset_locate(r, 6, 0);
+    fill_locate(r, ids, res, nullptr, 0);
+    CHECK(r.located == (LL{0, -1, -1, 2, 7, -1}) && r.unlocated == 5 && r.weights.empty() &&
+          r.fixes.empty());
+    for (auto& v : flat)
+        v = 77;
+    locate_to_flat(r, flat);
+    CHECK((LL(flat, flat + 10)) == (LL{0, -1, -1, 2, 7, -1, 5, 77, 77, 77}));
+    // t = 0 on exactly N + 2 words (what the single locate reads back)
+    const uint32_t short_res[5] = {1, 2, 3, 4, 0};
+    reset_locate(r, 6, 0);
+    fill_locate(r, ids, short_res, nullptr, 0);
+    CHECK(r.located == (LL{2, -1, -1, 3, 1, -1}) && r.unlocated == 4);
+}
+
 static void test_nf4_marks()
 {
     // 4 lanes per word: lanes 0, 1 -> word 0 mask 0b0011; 5 -> word 1 mask
@@ -219,6 +291,8 @@ int main()
     test_layout();
     test_retry();
     test_entries_and_flat();
+    test_held_positions();
+    test_locate_results();
     test_nf4_marks();
     std::printf("ALL OK\n");
     return 0;

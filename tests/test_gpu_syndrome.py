@@ -654,9 +654,78 @@ def test_fix_list_overflow(hip_lib):
         assert set(tuple(int(v) for v in f) for f in fixes) == want
 
 
+def test_syndrome_blocks_retry(hip_lib):
+    """Fec.syndrome_blocks with an accumulator, second attempt: the last link's
+    row makes syndrome 0 of the sum 65536 in 100 columns against a
+    first-attempt capacity of 64 + 512 // 512 = 65, so the share runs again,
+    from the acc rows (and their marks) as they were."""
+    import quadiron_amd as qa
+    k = m = 4
+    R, P = 2, 512
+    cap0 = 64 + P // 512
+    n_hot = 100
+    assert n_hot > cap0
+    fec = qa.Fec(k, m, False)
+    rng = np.random.default_rng(8)
+    listed = [int(f) for f in rng.permutation(k + m)[:k + R]]
+    N = len(listed)
+    x, w = _points(k, m, listed)
+    winv = [pow(int(v), Q - 2, Q) for v in w]
+    y = rng.integers(0, 65536, (N, P)).astype(np.int64)
+    for p in range(N - 1):          # marks on link 1's rows
+        y[p, rng.choice(P, 3, replace=False)] = MARK
+
+    def syndromes(pos):
+        e = np.zeros((R, P), np.int64)
+        for p in pos:
+            for j in range(R):
+                e[j] = (e[j] + y[p] * pow(int(x[p]), j, Q) % Q * winv[p]) % Q
+        return e
+
+    # link 1's own sum holds marks too: three columns of its last row are crafted
+    acc_cols = rng.choice(P, 3, replace=False)
+    part = syndromes(range(N - 2))[0]
+    y[N - 2, acc_cols] = (MARK - part[acc_cols]) % Q * int(w[N - 2]) % Q
+    a0 = syndromes(range(N - 1))[0]
+    assert (a0[acc_cols] == MARK).all()
+    hot = np.sort(np.concatenate([[0, P - 1], 1 + rng.choice(P - 2, n_hot - 2, replace=False)]))
+    assert len(set(hot.tolist())) == n_hot
+    y[N - 1, hot] = (MARK - a0[hot]) % Q * int(w[N - 1]) % Q
+    exp1, exp = syndromes(range(N - 1)), syndromes(range(N))
+    assert (exp[0, hot] == MARK).all() and (exp[0] == MARK).sum() >= n_hot > cap0
+
+    def link(pos, acc):
+        rows, marks = _split(y[pos])
+        oor = np.zeros((len(pos), CAP), np.uint32)
+        cnt = np.zeros(len(pos), np.uint32)
+        for h, mk in enumerate(marks):
+            cnt[h] = len(mk)
+            oor[h, :len(mk)] = mk
+        rows = [np.ascontiguousarray(r).view(np.uint8) for r in rows]
+        return fec.syndrome_blocks(listed, [listed[p] for p in pos], rows, oor, cnt, R, acc=acc,
+                                   out_cap=128)
+
+    def check(got, want):
+        rows, oor, cnt = got
+        for j in range(R):
+            em = [int(c) for c in np.flatnonzero(want[j] == MARK)]
+            assert (rows[j].view(np.uint16) == (want[j] & 0xffff)).all(), j
+            assert cnt[j] == len(em), (j, cnt[j], len(em))
+            assert [int(c) for c in oor[j, :cnt[j]]] == em, j
+
+    acc = link(list(range(N - 1)), None)
+    check(acc, exp1)
+    assert acc[2][0] >= 3
+    before = [r.copy() for r in acc[0]], acc[1].copy(), acc[2].copy()
+    check(link([N - 1], acc), exp)
+    # the accumulator handed in is the caller's: left as it was
+    assert all((a == b).all() for a, b in zip(acc[0], before[0]))
+    assert (acc[1] == before[1]).all() and (acc[2] == before[2]).all()
+
+
 # ---- 7. errors ----------------------------------------------------------------
 
-BAD = ["id_repeated", "id_high", "pos_repeated", "pos_high"]
+BAD =["id_repeated", "id_high", "pos_repeated", "pos_high"]
 
 
 @pytest.mark.parametrize("what", BAD)
