@@ -56,8 +56,10 @@
 
 #include "fnt_codelets.h"
 #include "gf65537.h"
+#include "ntt_geom.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
+#include "row_tile.h"  // tile_record_oor
 
 namespace qi {
 
@@ -451,16 +453,6 @@ __global__ __launch_bounds__(kNttBlock) void ntt_fix_kernel(NttFixArgs a)
 // pass is needed (src/fec_base.h:1418-1448 in this order).
 // ---------------------------------------------------------------------------
 constexpr int kLdsThreads = 512;
-constexpr int kLdsMaxN = 2048;
-constexpr int kLdsMaxPasses = 6;
-
-struct XfPlan {
-    int N, np;
-    int lgr[kLdsMaxPasses];  // log2 radix of pass q
-    int sh[kLdsMaxPasses];   // log2 s_q = log2(N / (R_0 ... R_q))
-    int tw[kLdsMaxPasses];   // pass q's twiddles in the LDS table: entry
-                             // j R_q + u = w_{L_q}^{+-j u}, j < s_q
-};
 
 // x[t] of a transform lives at pos(t) (DIF output / DIT input order)
 __device__ __forceinline__ int xf_pos(const XfPlan& P, int t)
@@ -486,22 +478,6 @@ __device__ __forceinline__ int xf_index(const XfPlan& P, int p)
     return t;
 }
 
-// Image row of transform position p: one empty row after every 32.  A
-// wave holds 64 / T tasks of a pass; in the short-stride passes (the unit
-// pass: 32 consecutive positions per task) those tasks sat 32 T words
-// apart, i.e. on the same banks (k1000 encode: 72 % of the LDS cycles were
-// bank conflicts); one row per 32 moves task tt by tt T banks.  A pass
-// task's positions b + j + q s (b a multiple of 32 or the task inside one
-// aligned 32-block, j < s) never carry into bit 5, so
-// prow(b + j + q s) = prow(b + j) + prow(q s): a per-task base plus a
-// per-q uniform offset, as before.
-__host__ __device__ __forceinline__ int prow(int p)
-{
-    return p + (p >> 5);
-}
-
-enum : int { kLdsEnc = 0, kLdsSysEnc = 1, kLdsDec = 2, kLdsSysDec = 3 };
-
 struct NttLdsArgs {
     int mode;
     int k, n, len2k, nmax;
@@ -524,7 +500,7 @@ struct NttLdsArgs {
     Oor out_oor;
     uint32_t* err;
     int wide;  // 16-byte row pieces: every row base and stride 8-word
-               // aligned and words % 8 == 0 (lds_launch checks)
+               // aligned and words % 8 == 0 (rows_wide)
     // erasure decode (ntt_eras_kernel): e erased positions, their list and
     // the e x e solve in the context, n^-1 (balanced)
     int eras_e, eras_eid, eras_b;
@@ -598,6 +574,35 @@ __device__ __forceinline__ void lds_pass(int32_t* buf, const int32_t* twp, int N
                                                  nullptr, 0, cp, lgnb);
 }
 
+// Pass q of a transform, then the barrier: the radix is data (P.lgr[q]), its
+// codelet a template argument.  cm, cb, lgnb: see lds_transform
+template <bool DIF, bool INV, bool CANON = false>
+__device__ __forceinline__ void lds_pass_r(int32_t* buf, const int32_t* tw, const XfPlan& P, int q,
+                                           int lgT, int col, int g, int G,
+                                           const int32_t* cm = nullptr, int cb = 0, int lgnb = 0)
+{
+    const int lgs = P.sh[q], lgL = lgs + P.lgr[q];
+    const int32_t* twp = tw + P.tw[q];
+    switch (P.lgr[q]) {
+    case 1:
+        lds_pass<2, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, cm, cb, &P, lgnb);
+        break;
+    case 2:
+        lds_pass<4, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, cm, cb, &P, lgnb);
+        break;
+    case 3:
+        lds_pass<8, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, cm, cb, &P, lgnb);
+        break;
+    case 4:
+        lds_pass<16, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, cm, cb, &P, lgnb);
+        break;
+    default:
+        lds_pass<32, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, cm, cb, &P, lgnb);
+        break;
+    }
+    __syncthreads();
+}
+
 // cm (DIF only): the output scale of the last (s = 1) pass, indexed by the
 // natural output index (see lds_pass_body).  2^lgnb transforms of P.N
 // points back to back (image rows bi N ..), the same passes over all: the
@@ -609,42 +614,311 @@ __device__ void lds_transform(int32_t* buf, const int32_t* tw, const XfPlan& P, 
     const int cb = P.N == 1 ? 0 : ilog2_dev(P.N) - P.lgr[P.np - 1];
     for (int i = 0; i < P.np; i++) {
         const int q = DIF ? i : P.np - 1 - i;  // DIT: the passes in reverse
-        const int lgs = P.sh[q], lgL = lgs + P.lgr[q];
-        const int32_t* twp = tw + P.tw[q];
-        const int32_t* c = DIF && i == P.np - 1 ? cm : nullptr;
-        switch (P.lgr[q]) {
-        case 1:
-            lds_pass<2, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, c, cb, &P,
-                                           lgnb);
-            break;
-        case 2:
-            lds_pass<4, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, c, cb, &P,
-                                           lgnb);
-            break;
-        case 3:
-            lds_pass<8, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, c, cb, &P,
-                                           lgnb);
-            break;
-        case 4:
-            lds_pass<16, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, c, cb, &P,
-                                           lgnb);
-            break;
-        default:
-            lds_pass<32, DIF, INV, CANON>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, c, cb, &P,
-                                           lgnb);
-            break;
-        }
-        __syncthreads();
+        lds_pass_r<DIF, INV, CANON>(buf, tw, P, q, lgT, col, g, G,
+                                    DIF && i == P.np - 1 ? cm : nullptr, cb, lgnb);
     }
 }
 
-// LDS side arrays behind the nmax x T image (int32 words)
-__host__ __device__ inline int lds_side_words(int tw_words, int k, int len2k, bool twg)
+constexpr int kLdsBatch = 8;  // row loads in flight per thread
+
+// The tile of a workgroup of ntt_lds_kernel / ntt_eras_kernel: T = 2^lgT
+// columns from c0 of stripe s.
+// XCD-aware map: workgroups go round-robin over the 8 XCDs (b % 8), and a
+// tile is only T = 8..64 columns (16..128 bytes of a row), so in
+// stripe-major order the tiles sharing a 128-byte line ran on different
+// XCDs (each L2 fetching and partially writing the same lines).  XCD x
+// walks the contiguous eighth x of the (stripe, tile) order instead.
+// In the transforms and on narrow rows a lane is column col of row group g
+// of G: it moves one u16 column and a wave 64 / T rows of T columns, i.e.
+// 16..128-byte pieces per wave instruction and few bytes in flight.  On
+// wide rows (a.wide) lane (rl, cj) moves columns 8 cj .. 8 cj + 7 of a row
+// as one 16-byte access, RPP rows per sweep of the workgroup.
+struct LdsTile {
+    int s, lgT, col, g, G;
+    long long c0, cg;  // the tile's first column; the lane's column
+    bool valid;        // cg inside the row
+    int wide, rl, cj, RPP;
+    long long cw;      // first column of the lane's piece
+    bool wvalid;
+    __device__ __forceinline__ explicit LdsTile(const NttLdsArgs& a)
+    {
+        int b = blockIdx.x;
+        if ((gridDim.x & 7) == 0)
+            b = (b & 7) * static_cast<int>(gridDim.x >> 3) + (b >> 3);
+        const int tid = threadIdx.x, lgL = a.lgT - 3;
+        lgT = a.lgT;
+        s = b / a.tiles;
+        c0 = static_cast<long long>(b - s * a.tiles) << lgT;
+        col = tid & ((1 << lgT) - 1);
+        g = tid >> lgT;
+        G = kLdsThreads >> lgT;
+        cg = c0 + col;
+        valid = cg < a.words;
+        wide = a.wide;
+        rl = tid >> lgL;
+        cj = tid & ((1 << lgL) - 1);
+        RPP = kLdsThreads >> lgL;
+        cw = c0 + 8 * cj;
+        wvalid = cw < a.words;
+    }
+};
+
+__device__ __forceinline__ const uint16_t* row_ptr(const RowSrc& src, int s, int id)
 {
-    return twg ? 2 * k : tw_words + 2 * k + len2k;
+    return id < src.split ? src.base0 + s * src.ss0 + id * src.rs0
+                          : src.base1 + s * src.ss1 + (id - src.split) * src.rs1;
 }
 
-constexpr int kLdsBatch = 8;  // row loads in flight per thread
+// a 16-byte row piece <-> its 8 words
+__device__ __forceinline__ void unpack8(uint4 x, int32_t (&e)[8])
+{
+    const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        e[2 * q] = static_cast<int32_t>(xs[q] & 0xffffu);
+        e[2 * q + 1] = static_cast<int32_t>(xs[q] >> 16);
+    }
+}
+__device__ __forceinline__ uint4 pack8(const uint32_t (&cv)[8])
+{
+    uint4 v;
+    v.x = (cv[0] & 0xffffu) | (cv[1] << 16);
+    v.y = (cv[2] & 0xffffu) | (cv[3] << 16);
+    v.z = (cv[4] & 0xffffu) | (cv[5] << 16);
+    v.w = (cv[6] & 0xffffu) | (cv[7] << 16);
+    return v;
+}
+
+// The rows a kernel loads (lds_load_rows): row i is row id(i) of the source
+// and lands at image position pos(i).  The encode's data rows sit at their
+// natural positions (DIF input); received row i, sequence index z_i =
+// s_id[i], at INTT_n's pos(z_i) (DIT input)
+struct DataRows {
+    __device__ __forceinline__ int id(int i) const { return i; }
+    __device__ __forceinline__ int pos(int i) const { return i; }
+};
+struct RecvRows {
+    const int32_t* s_id;
+    const XfPlan& P;
+    int by_pos;
+    __device__ __forceinline__ int id(int i) const { return by_pos ? i : s_id[i]; }
+    __device__ __forceinline__ int pos(int i) const { return xf_pos(P, s_id[i]); }
+};
+
+// Rows i < n_rows (>= 1) of the source into the tile's image, times scale[i]
+// (balanced) when given; rows up to n_fill are written as zero.  kLdsBatch
+// row loads in flight per thread: every load is unconditional, from an
+// address that always lies inside the source -- a lane past the row's end
+// reads the tile's first columns, a lane past the last row in the last
+// sweep reads row n_rows - 1 again -- and what it fetched is dropped
+// afterwards; a sweep wholly past the last row is skipped by every lane
+// alike.  (A load under a per-lane condition is followed by its own wait in
+// the gfx950 code: one row in flight.)
+template <class Rows>
+__device__ __forceinline__ void lds_load_rows(int32_t* buf, const LdsTile& t, const RowSrc& asrc,
+                                              const Rows& rows, int n_rows, int n_fill,
+                                              const int32_t* scale)
+{
+    // a copy in registers: read through the kernel's argument block, the
+    // bases were fetched again before every row load
+    const RowSrc src = asrc;
+    const int last = n_rows - 1;
+    if (t.wide) {
+        const long long cw = t.wvalid ? t.cw : t.c0;
+        for (int b0 = 0; b0 < n_rows; b0 += t.RPP * kLdsBatch) {
+            uint4 x[kLdsBatch];
+#pragma unroll
+            for (int u = 0; u < kLdsBatch; u++) {
+                x[u] = uint4{0, 0, 0, 0};
+                if (b0 + u * t.RPP < n_rows) {  // (the same in every lane)
+                    const int i = min(b0 + u * t.RPP + t.rl, last);
+                    x[u] = *reinterpret_cast<const uint4*>(row_ptr(src, t.s, rows.id(i)) + cw);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kLdsBatch; u++) {
+                const int i = b0 + u * t.RPP + t.rl;
+                if (i < n_rows) {
+                    int32_t e[8];
+                    unpack8(x[u], e);
+                    const int32_t sc = scale ? scale[i] : 0;
+#pragma unroll
+                    for (int q = 0; q < 8; q++) {
+                        e[q] = t.wvalid ? e[q] : 0;
+                        if (scale)
+                            e[q] = mul_rt(e[q], sc);
+                    }
+                    int4* d = reinterpret_cast<int4*>(buf + (prow(rows.pos(i)) << t.lgT) +
+                                                      8 * t.cj);
+                    d[0] = int4{e[0], e[1], e[2], e[3]};
+                    d[1] = int4{e[4], e[5], e[6], e[7]};
+                }
+            }
+        }
+        for (int i = n_rows + t.rl; i < n_fill; i += t.RPP) {
+            int4* d = reinterpret_cast<int4*>(buf + (prow(rows.pos(i)) << t.lgT) + 8 * t.cj);
+            d[0] = d[1] = int4{0, 0, 0, 0};
+        }
+        return;
+    }
+    const long long cg = t.valid ? t.cg : t.c0;
+    for (int b0 = 0; b0 < n_rows; b0 += t.G * kLdsBatch) {
+        int32_t x[kLdsBatch];
+#pragma unroll
+        for (int u = 0; u < kLdsBatch; u++) {
+            x[u] = 0;
+            if (b0 + u * t.G < n_rows) {  // (the same in every lane)
+                const int i = min(b0 + u * t.G + t.g, last);
+                x[u] = row_ptr(src, t.s, rows.id(i))[cg];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kLdsBatch; u++) {
+            const int i = b0 + u * t.G + t.g;
+            if (i < n_rows) {
+                const int32_t v = t.valid ? x[u] : 0;
+                buf[(prow(rows.pos(i)) << t.lgT) + t.col] = scale ? mul_rt(v, scale[i]) : v;
+            }
+        }
+    }
+    for (int i = n_rows + t.g; i < n_fill; i += t.G)
+        buf[(prow(rows.pos(i)) << t.lgT) + t.col] = 0;
+}
+
+// decode_prepare (src/fec_base.h:1361-1404): a marked symbol is 65536 = -1
+// whatever was stored, so the marks of the received rows inside this tile
+// become -scale[i] (-1 without a scale), then the barrier
+__device__ __forceinline__ void lds_restore_marks(int32_t* buf, const LdsTile& t,
+                                                  const NttLdsArgs& a, const XfPlan& P,
+                                                  const int32_t* s_id, const int32_t* scale)
+{
+    if (!a.in_oor.counts)
+        return;
+    for (int i = threadIdx.x; i < a.k; i += kLdsThreads) {
+        const int id = s_id[i];  // sequence index z_i
+        const int slot = a.src.by_pos ? i : id - a.slot_base;
+        if (slot < 0)
+            continue;  // systematic data row: no marks
+        const long long bk = static_cast<long long>(t.s) * a.in_oor.slots + slot;
+        uint32_t cnt = a.in_oor.counts[bk];
+        if (cnt > static_cast<uint32_t>(a.in_oor.cap)) {
+            atomicOr(a.err, kErrOorTruncated);
+            cnt = static_cast<uint32_t>(a.in_oor.cap);
+        }
+        const int p = xf_pos(P, id);
+        const int32_t y = scale ? -scale[i] : -1;
+        for (uint32_t e = 0; e < cnt; e++) {
+            const long long c =
+                static_cast<long long>(a.in_oor.entries[bk * a.in_oor.cap + e]) - t.c0;
+            if (c >= 0 && c < (1 << t.lgT))
+                buf[(prow(p) << t.lgT) + static_cast<int>(c)] = y;
+        }
+    }
+    __syncthreads();
+}
+
+// The rows a kernel writes (lds_write_rows): words(r) points at the T
+// V-range words of output row r and value() maps each before canon_vr.
+// ImageRows: sequence element first + r of the image, at position t (DIT
+// output: natural order) or pos(t) (DIF output); SCALE: times scale
+// (balanced)
+template <bool SCALE>
+struct ImageRows {
+    static constexpr bool kCopies = false;
+    const int32_t* buf;
+    const XfPlan& P;
+    int lgT, first;
+    bool natural;
+    int32_t scale;
+    __device__ __forceinline__ const int32_t* words(int r) const
+    {
+        const int t = first + r;
+        return buf + (prow(natural ? t : xf_pos(P, t)) << lgT);
+    }
+    __device__ __forceinline__ int32_t value(int32_t x) const
+    {
+        return SCALE ? fold(mul_rt(x, scale)) : x;
+    }
+};
+// CodewordRows (the erasure kernel's systematic outputs): codeword symbol
+// t = first + r, an erased one from c_E, a received one (words() null)
+// copied through from source row copy_row(r)
+struct CodewordRows {
+    static constexpr bool kCopies = true;
+    const int32_t *s_pos, *s_cE;
+    int lgT, first, by_pos;
+    __device__ __forceinline__ const int32_t* words(int r) const
+    {
+        const int pm = s_pos[first + r];
+        return pm >= 0 ? nullptr : s_cE + ((-1 - pm) << lgT);
+    }
+    __device__ __forceinline__ int copy_row(int r) const
+    {
+        return by_pos ? s_pos[first + r] : first + r;
+    }
+    __device__ __forceinline__ int32_t value(int32_t x) const { return x; }
+};
+
+// Output rows r < a.out_rows of the tile as canonical u16; RECORD: the
+// 65536s (stored as 0) go into a.out_oor's bucket r.  Ends the lanes past
+// the row's end: nothing but the kernel's return may follow
+template <bool RECORD, class Rows>
+__device__ __forceinline__ void lds_write_rows(const LdsTile& t, const NttLdsArgs& a,
+                                               const Rows& rows)
+{
+    const bool record = RECORD && a.out_oor.counts;
+    if (t.wide) {
+        if (!t.wvalid)
+            return;
+        for (int r = t.rl; r < a.out_rows; r += t.RPP) {
+            uint16_t* o = a.out + t.s * a.oss + r * a.ors + t.cw;
+            const int32_t* w = rows.words(r);
+            if constexpr (Rows::kCopies) {
+                if (!w) {
+                    *reinterpret_cast<uint4*>(o) = *reinterpret_cast<const uint4*>(
+                        row_ptr(a.src, t.s, rows.copy_row(r)) + t.cw);
+                    continue;
+                }
+            }
+            const int4* sp = reinterpret_cast<const int4*>(w + 8 * t.cj);
+            const int4 lo = sp[0], hi = sp[1];
+            const int32_t e[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            uint32_t cv[8];
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                cv[q] = canon_vr(rows.value(e[q]));
+                any |= cv[q] == 65536u;
+            }
+            *reinterpret_cast<uint4*>(o) = pack8(cv);
+            if (any && record) {
+#pragma unroll
+                for (int q = 0; q < 8; q++)
+                    if (cv[q] == 65536u)
+                        tile_record_oor(a.out_oor, t.s, r, t.cw + q);
+            }
+        }
+        return;
+    }
+    if (!t.valid)
+        return;
+    for (int r = t.g; r < a.out_rows; r += t.G) {
+        const int32_t* w = rows.words(r);
+        uint32_t cv = 0;
+        bool copied = false;
+        if constexpr (Rows::kCopies) {
+            copied = !w;
+            if (copied)
+                cv = row_ptr(a.src, t.s, rows.copy_row(r))[t.cg];
+        }
+        if (!copied) {
+            cv = canon_vr(rows.value(w[t.col]));
+            if (cv == 65536u && record)
+                tile_record_oor(a.out_oor, t.s, r, t.cg);
+        }
+        a.out[t.s * a.oss + r * a.ors + t.cg] = static_cast<uint16_t>(cv);
+    }
+}
 
 // TWG: the pass twiddle tables and C are read from global memory (L1/L2
 // hits) instead of being staged in LDS, so that two workgroups fit a CU
@@ -657,30 +931,19 @@ template <bool TWG>
 __global__ __launch_bounds__(kLdsThreads) void ntt_lds_kernel(NttLdsArgs a)
 {
     extern __shared__ int32_t qi_ntt_lds[];
-    const int nmax = a.nmax, lgT = a.lgT, T = 1 << lgT, k = a.k;
+    const int nmax = a.nmax, k = a.k;
+    const LdsTile tile(a);
+    const int lgT = tile.lgT, col = tile.col, g = tile.g, G = tile.G, tid = threadIdx.x;
     int32_t* buf = qi_ntt_lds;
     int32_t* tw_l = qi_ntt_lds + (prow(nmax) << lgT);  // pass twiddle tables
     const int32_t* tw = TWG ? a.tw : tw_l;
     int32_t* s_inv = TWG ? tw_l : tw_l + a.tw_words;  // inv_A_i (balanced)
     int32_t* s_id = s_inv + k;                 // received ids z_i
     int32_t* s_c = s_id + k;                   // C[j] (balanced), natural order
-    // XCD-aware map: workgroups go round-robin over the 8 XCDs (b % 8), and
-    // a tile is only T = 8..64 columns (16..128 bytes of a row), so in
-    // stripe-major order the tiles sharing a 128-byte line ran on different
-    // XCDs (each L2 fetching and partially writing the same lines).  XCD x
-    // walks the contiguous eighth x of the (stripe, tile) order instead.
-    int b = blockIdx.x;
-    if ((gridDim.x & 7) == 0)
-        b = (b & 7) * static_cast<int>(gridDim.x >> 3) + (b >> 3);
-    const int s = b / a.tiles;
-    const long long c0 = static_cast<long long>(b - s * a.tiles) << lgT;
-    const int tid = threadIdx.x, col = tid & (T - 1), g = tid >> lgT, G = kLdsThreads >> lgT;
-    const long long cg = c0 + col;
-    const bool valid = cg < a.words;
     const bool dec = a.mode != kLdsEnc;
     // every per-stripe constant into LDS first (one round of independent
     // loads), so the hot loops below wait on nothing but their row loads
-    const int32_t* ctx = a.ctx + s * a.cs;
+    const int32_t* ctx = a.ctx + tile.s * a.cs;
     if (!TWG)
         for (int e = tid; e < a.tw_words; e += kLdsThreads)
             tw_l[e] = a.tw[e];
@@ -693,79 +956,9 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_lds_kernel(NttLdsArgs a)
             for (int j = tid; j < a.len2k; j += kLdsThreads)
                 s_c[j] = balanced(static_cast<uint32_t>(ctx[a.c_off + j]));
     }
-    const RowSrc& src = a.src;
-    auto row_ptr = [&](int id) {
-        return id < src.split ? src.base0 + s * src.ss0 + id * src.rs0
-                              : src.base1 + s * src.ss1 + (id - src.split) * src.rs1;
-    };
-    // wide row pieces: lane (rl, cj) moves columns 8 cj .. 8 cj + 7 of a
-    // row as one 16-byte access (a wave covers 64 / LPR rows); otherwise a
-    // lane moves one u16 column and a wave 64 / T rows of T columns, i.e.
-    // 16..128-byte pieces per wave instruction and few bytes in flight
-    const int lgL = lgT - 3, rl = tid >> lgL, cj = tid & ((1 << lgL) - 1);
-    const int RPP = kLdsThreads >> lgL;  // rows per sweep
-    const long long cw = c0 + 8 * cj;    // first column of the lane's piece
-    const bool wvalid = cw < a.words;
-    auto ld_piece = [&](int id) {
-        const uint16_t* r = row_ptr(id) + cw;
-        return *reinterpret_cast<const uint4*>(r);
-    };
-    // 8 u16 (a uint4) -> int32 words at image row p, columns 8 cj ..
-    auto put_piece = [&](int p, uint4 x, int32_t scale, bool sc) {
-        int4 lo, hi;
-        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-        int32_t e[8];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            e[2 * q] = static_cast<int32_t>(xs[q] & 0xffffu);
-            e[2 * q + 1] = static_cast<int32_t>(xs[q] >> 16);
-        }
-        if (sc) {
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                e[q] = mul_rt(e[q], scale);
-        }
-        lo = int4{e[0], e[1], e[2], e[3]};
-        hi = int4{e[4], e[5], e[6], e[7]};
-        int4* d = reinterpret_cast<int4*>(buf + (prow(p) << lgT) + 8 * cj);
-        d[0] = lo;
-        d[1] = hi;
-    };
-    if (!dec && a.wide) {
+    if (!dec) {
         // data rows t < k at natural positions, zero above (DIF input)
-        for (int p0 = rl; p0 < a.n; p0 += RPP * kLdsBatch) {
-            uint4 x[kLdsBatch];
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int p = p0 + u * RPP;
-                x[u] = (p < k && wvalid) ? ld_piece(p) : uint4{0, 0, 0, 0};
-            }
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int p = p0 + u * RPP;
-                if (p < a.n)
-                    put_piece(p, x[u], 0, false);
-            }
-        }
-        __syncthreads();
-        lds_transform<true, false>(buf, tw, a.pnf, lgT, col, g, G);
-    } else if (!dec) {
-        // data rows t < k at natural positions, zero above (DIF input);
-        // kLdsBatch row loads in flight per thread
-        for (int p0 = g; p0 < a.n; p0 += G * kLdsBatch) {
-            int32_t x[kLdsBatch];
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int p = p0 + u * G;
-                x[u] = (p < k && valid) ? row_ptr(p)[cg] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int p = p0 + u * G;
-                if (p < a.n)
-                    buf[(prow(p) << lgT) + col] = x[u];
-            }
-        }
+        lds_load_rows(buf, tile, a.src, DataRows{}, k, a.n, nullptr);
         __syncthreads();
         lds_transform<true, false>(buf, tw, a.pnf, lgT, col, g, G);
     } else {
@@ -773,65 +966,9 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_lds_kernel(NttLdsArgs a)
         for (int p = g; p < a.n; p += G)
             buf[(prow(p) << lgT) + col] = 0;
         __syncthreads();
-        if (a.wide) {
-            for (int i0 = rl; i0 < k; i0 += RPP * kLdsBatch) {
-                uint4 x[kLdsBatch];
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * RPP;
-                    x[u] = (i < k && wvalid) ? ld_piece(src.by_pos ? i : s_id[i])
-                                             : uint4{0, 0, 0, 0};
-                }
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * RPP;
-                    if (i < k)
-                        put_piece(xf_pos(a.pnf, s_id[i]), x[u], s_inv[i], true);
-                }
-            }
-        } else
-        for (int i0 = g; i0 < k; i0 += G * kLdsBatch) {
-            int32_t x[kLdsBatch];
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int i = i0 + u * G;
-                x[u] = 0;
-                if (i < k && valid)
-                    x[u] = row_ptr(src.by_pos ? i : s_id[i])[cg];
-            }
-#pragma unroll
-            for (int u = 0; u < kLdsBatch; u++) {
-                const int i = i0 + u * G;
-                if (i < k)
-                    buf[(prow(xf_pos(a.pnf, s_id[i])) << lgT) + col] = mul_rt(x[u], s_inv[i]);
-            }
-        }
+        lds_load_rows(buf, tile, a.src, RecvRows{s_id, a.pnf, a.src.by_pos}, k, k, s_inv);
         __syncthreads();
-        if (a.in_oor.counts) {
-            // decode_prepare (src/fec_base.h:1361-1404): a marked symbol is
-            // 65536 = -1, so y = -inv_A_i at the marks inside this tile
-            for (int i = tid; i < k; i += kLdsThreads) {
-                const int id = s_id[i];  // sequence index z_i
-                const int slot = src.by_pos ? i : id - a.slot_base;
-                if (slot < 0)
-                    continue;  // systematic data row: no marks
-                const long long bk = static_cast<long long>(s) * a.in_oor.slots + slot;
-                uint32_t cnt = a.in_oor.counts[bk];
-                if (cnt > static_cast<uint32_t>(a.in_oor.cap)) {
-                    atomicOr(a.err, kErrOorTruncated);
-                    cnt = static_cast<uint32_t>(a.in_oor.cap);
-                }
-                const int p = xf_pos(a.pnf, id);
-                const int32_t y = -s_inv[i];  // -inv_A_i, balanced
-                for (uint32_t e = 0; e < cnt; e++) {
-                    const long long c = static_cast<long long>(
-                                            a.in_oor.entries[bk * a.in_oor.cap + e]) - c0;
-                    if (c >= 0 && c < T)
-                        buf[(prow(p) << lgT) + static_cast<int>(c)] = y;
-                }
-            }
-            __syncthreads();
-        }
+        lds_restore_marks(buf, tile, a, a.pnf, s_id, s_inv);
         lds_transform<false, true>(buf, tw, a.pni, lgT, col, g, G);
         // NTT_2k of the first k outputs (zero from k, k <= h = len_2k / 2),
         // x C, INTT_2k, split in halves (no pass touches the zero half):
@@ -866,60 +1003,8 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_lds_kernel(NttLdsArgs a)
             lds_transform<true, false>(buf, tw, a.pnf, lgT, col, g, G);
         }
     }
-    // output rows: sequence index t = out_first + r, at position t (DIT
-    // output: natural order) or pos_n(t) (DIF output)
-    const bool natural = a.mode == kLdsDec;
-    if (a.wide) {
-        if (!wvalid)
-            return;
-        for (int r = rl; r < a.out_rows; r += RPP) {
-            const int t = a.out_first + r;
-            const int p = natural ? t : xf_pos(a.pnf, t);
-            const int4* sp = reinterpret_cast<const int4*>(buf + (prow(p) << lgT) + 8 * cj);
-            const int4 lo = sp[0], hi = sp[1];
-            const int32_t e[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            uint32_t cv[8];
-            bool any = false;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                cv[q] = canon_vr(e[q]);
-                any |= cv[q] == 65536u;
-            }
-            uint4 o;
-            o.x = (cv[0] & 0xffffu) | (cv[1] << 16);
-            o.y = (cv[2] & 0xffffu) | (cv[3] << 16);
-            o.z = (cv[4] & 0xffffu) | (cv[5] << 16);
-            o.w = (cv[6] & 0xffffu) | (cv[7] << 16);
-            *reinterpret_cast<uint4*>(a.out + s * a.oss + r * a.ors + cw) = o;
-            if (any && a.out_oor.counts) {
-                const long long bk = static_cast<long long>(s) * a.out_oor.slots + r;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    if (cv[q] == 65536u) {
-                        const uint32_t en = atomicAdd(&a.out_oor.counts[bk], 1u);
-                        if (en < static_cast<uint32_t>(a.out_oor.cap))
-                            a.out_oor.entries[bk * a.out_oor.cap + en] =
-                                static_cast<uint32_t>(cw + q);
-                    }
-                }
-            }
-        }
-        return;
-    }
-    if (!valid)
-        return;
-    for (int r = g; r < a.out_rows; r += G) {
-        const int t = a.out_first + r;
-        const int p = natural ? t : xf_pos(a.pnf, t);
-        const uint32_t cv = canon_vr(buf[(prow(p) << lgT) + col]);
-        a.out[s * a.oss + r * a.ors + cg] = static_cast<uint16_t>(cv);
-        if (cv == 65536u && a.out_oor.counts) {
-            const long long bk = static_cast<long long>(s) * a.out_oor.slots + r;
-            const uint32_t e = atomicAdd(&a.out_oor.counts[bk], 1u);
-            if (e < static_cast<uint32_t>(a.out_oor.cap))
-                a.out_oor.entries[bk * a.out_oor.cap + e] = static_cast<uint32_t>(cg);
-        }
-    }
+    lds_write_rows<true>(tile, a,
+                         ImageRows<false>{buf, a.pnf, lgT, a.out_first, a.mode == kLdsDec, 0});
 }
 
 // INTT_n (DIT, as lds_transform<false, true>) computing only the outputs
@@ -935,34 +1020,8 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_lds_kernel(NttLdsArgs a)
 __device__ void lds_intt_top(int32_t* buf, const int32_t* tw, const XfPlan& P, int lgT, int col,
                              int g, int G, int k, const int32_t* rinv, int32_t* syn)
 {
-    for (int i = 0; i + 1 < P.np; i++) {
-        const int q = P.np - 1 - i;
-        const int lgs = P.sh[q], lgL = lgs + P.lgr[q];
-        const int32_t* twp = tw + P.tw[q];
-        switch (P.lgr[q]) {
-        case 1:
-            lds_pass<2, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr, 0,
-                                            &P, 0);
-            break;
-        case 2:
-            lds_pass<4, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr, 0,
-                                            &P, 0);
-            break;
-        case 3:
-            lds_pass<8, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr, 0,
-                                            &P, 0);
-            break;
-        case 4:
-            lds_pass<16, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr,
-                                             0, &P, 0);
-            break;
-        default:
-            lds_pass<32, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr,
-                                             0, &P, 0);
-            break;
-        }
-        __syncthreads();
-    }
+    for (int q = P.np - 1; q > 0; q--)
+        lds_pass_r<false, true>(buf, tw, P, q, lgT, col, g, G);
     const int lgR = P.lgr[0], R = 1 << lgR, lgs = P.sh[0], sN = 1 << lgs;
     const int32_t* twp = tw + P.tw[0];
     for (int j = g; j < sN; j += G) {
@@ -1016,8 +1075,6 @@ __device__ void lds_intt_top(int32_t* buf, const int32_t* tw, const XfPlan& P, i
 // encode is the same solve with E = [k, n) (the plan's constant context).
 // The math is emulated in tests/test_ntt_plan.py::test_erasure_decode_math.
 // ---------------------------------------------------------------------------
-constexpr int kErasMax = 64;
-
 struct ErasCtxLayout {
     int k, n, e;
     __host__ __device__ long long ids_off() const { return 0; }
@@ -1126,42 +1183,51 @@ __global__ __launch_bounds__(64) void eras_ctx_kernel(ErasCtxArgs a)
     }
 }
 
+// INTT_n's input of the erasure decode: the received rows at pos(id), the
+// erased positions zero or, when given, `fill` (c_E), the marked symbols as
+// 65536 = -1
+__device__ __forceinline__ void eras_load(int32_t* buf, const LdsTile& t, const NttLdsArgs& a,
+                                          const int32_t* s_id, const int32_t* s_eid,
+                                          const int32_t* fill)
+{
+    lds_load_rows(buf, t, a.src, RecvRows{s_id, a.pni, a.src.by_pos}, a.k, a.k, nullptr);
+    for (int it = threadIdx.x; it < (a.eras_e << t.lgT); it += kLdsThreads) {
+        const int j = it >> t.lgT, c = it & ((1 << t.lgT) - 1);
+        buf[(prow(xf_pos(a.pni, s_eid[j])) << t.lgT) + c] = fill ? fill[it] : 0;
+    }
+    __syncthreads();
+    lds_restore_marks(buf, t, a, a.pni, s_id, nullptr);
+}
+
 // The erasure decode of a tile of T columns of one stripe (and the
-// systematic encode, E = [k, n)), in LDS: image n x T, then the tables
-// (unless TWG), ids, the position map, E, B and c_E (e x T).
+// systematic encode, E = [k, n)), in LDS: image n x T, then INTT_n's pass
+// tables, ids, the position map, E, B and c_E (e x T).
 // C2: the non-systematic decode of a two-pass INTT_n (np = 2), completed
 // from the image (see below); otherwise the second load + INTT_n.  Separate
 // instantiations: one kernel holding both completions kept more registers
 // live (150 VGPRs, 3 waves per SIMD: one 512-thread block per CU).
-template <bool TWG, bool C2>
+template <bool C2>
 __global__ __launch_bounds__(kLdsThreads) void ntt_eras_kernel(NttLdsArgs a)
 {
     extern __shared__ int32_t qi_ntt_lds[];
-    const int n = a.n, lgT = a.lgT, T = 1 << lgT, k = a.k, e = a.eras_e;
+    const int n = a.n, k = a.k, e = a.eras_e;
+    const LdsTile tile(a);
+    const int lgT = tile.lgT, T = 1 << lgT, col = tile.col, g = tile.g, G = tile.G;
+    const int tid = threadIdx.x;
     int32_t* buf = qi_ntt_lds;
-    int32_t* tw_l = buf + (prow(n) << lgT);
-    const int32_t* tw = TWG ? a.tw : tw_l;
-    int32_t* s_id = TWG ? tw_l : tw_l + a.tw_words;
+    int32_t* tw = buf + (prow(n) << lgT);
+    int32_t* s_id = tw + a.tw_words;
     int32_t* s_pos = s_id + k;  // C2: e x T words of syndromes instead
     int32_t* s_eid = s_pos + (C2 ? (e << lgT) : n);
     int32_t* s_B = s_eid + e;
     int32_t* s_cE = s_B + e * e;
     int32_t* s_rinv = s_cE + (e << lgT);  // w_32^-x (INTT_n's passes' inverse roots)
-    // C2: the syndromes y'_[k, n) (e x T <= n words, eras_launch) in the
+    // C2: the syndromes y'_[k, n) (e x T words, eras_bytes) in the
     // position map's place (a non-systematic decode reads it no more)
     int32_t* s_syn = C2 ? s_pos : nullptr;
-    int b = blockIdx.x;  // XCD-contiguous tiles, as ntt_lds_kernel
-    if ((gridDim.x & 7) == 0)
-        b = (b & 7) * static_cast<int>(gridDim.x >> 3) + (b >> 3);
-    const int s = b / a.tiles;
-    const long long c0 = static_cast<long long>(b - s * a.tiles) << lgT;
-    const int tid = threadIdx.x, col = tid & (T - 1), g = tid >> lgT, G = kLdsThreads >> lgT;
-    const long long cg = c0 + col;
-    const bool valid = cg < a.words;
-    const int32_t* ctx = a.ctx + s * a.cs;
-    if (!TWG)
-        for (int i = tid; i < a.tw_words; i += kLdsThreads)
-            tw_l[i] = a.tw[i];
+    const int32_t* ctx = a.ctx + tile.s * a.cs;
+    for (int i = tid; i < a.tw_words; i += kLdsThreads)
+        tw[i] = a.tw[i];
     for (int i = tid; i < k; i += kLdsThreads)
         s_id[i] = ctx[a.ids_off + i];
     if (!C2)
@@ -1174,91 +1240,7 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_eras_kernel(NttLdsArgs a)
     if (tid < 32)
         s_rinv[tid] = a.rinv[tid];
     __syncthreads();
-    const RowSrc& src = a.src;
-    auto row_ptr = [&](int id) {
-        return id < src.split ? src.base0 + s * src.ss0 + id * src.rs0
-                              : src.base1 + s * src.ss1 + (id - src.split) * src.rs1;
-    };
-    const int lgL = lgT - 3, rl = tid >> lgL, cj = tid & ((1 << lgL) - 1);
-    const int RPP = kLdsThreads >> lgL;
-    const long long cw = c0 + 8 * cj;
-    const bool wvalid = cw < a.words;
-    // the received rows at pos(id) (+ c_E at pos(E_j) when `fill`), the
-    // marked symbols as 65536 = -1 (decode_prepare, src/fec_base.h:1361-1404)
-    auto load = [&](bool fill) {
-        if (a.wide) {
-            for (int i0 = rl; i0 < k; i0 += RPP * kLdsBatch) {
-                uint4 x[kLdsBatch];
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * RPP;
-                    x[u] = (i < k && wvalid) ? *reinterpret_cast<const uint4*>(
-                                                   row_ptr(src.by_pos ? i : s_id[i]) + cw)
-                                             : uint4{0, 0, 0, 0};
-                }
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * RPP;
-                    if (i < k) {
-                        const uint32_t xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
-                        int4* d = reinterpret_cast<int4*>(
-                            buf + (prow(xf_pos(a.pni, s_id[i])) << lgT) + 8 * cj);
-                        d[0] = int4{static_cast<int32_t>(xs[0] & 0xffffu),
-                                    static_cast<int32_t>(xs[0] >> 16),
-                                    static_cast<int32_t>(xs[1] & 0xffffu),
-                                    static_cast<int32_t>(xs[1] >> 16)};
-                        d[1] = int4{static_cast<int32_t>(xs[2] & 0xffffu),
-                                    static_cast<int32_t>(xs[2] >> 16),
-                                    static_cast<int32_t>(xs[3] & 0xffffu),
-                                    static_cast<int32_t>(xs[3] >> 16)};
-                    }
-                }
-            }
-        } else {
-            for (int i0 = g; i0 < k; i0 += G * kLdsBatch) {
-                int32_t x[kLdsBatch];
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * G;
-                    x[u] = (i < k && valid) ? row_ptr(src.by_pos ? i : s_id[i])[cg] : 0;
-                }
-#pragma unroll
-                for (int u = 0; u < kLdsBatch; u++) {
-                    const int i = i0 + u * G;
-                    if (i < k)
-                        buf[(prow(xf_pos(a.pni, s_id[i])) << lgT) + col] = x[u];
-                }
-            }
-        }
-        for (int it = tid; it < (e << lgT); it += kLdsThreads) {
-            const int j = it >> lgT, c = it & (T - 1);
-            buf[(prow(xf_pos(a.pni, s_eid[j])) << lgT) + c] = fill ? s_cE[it] : 0;
-        }
-        __syncthreads();
-        if (a.in_oor.counts) {
-            for (int i = tid; i < k; i += kLdsThreads) {
-                const int id = s_id[i];
-                const int slot = src.by_pos ? i : id - a.slot_base;
-                if (slot < 0)
-                    continue;  // systematic data row: no marks
-                const long long bk = static_cast<long long>(s) * a.in_oor.slots + slot;
-                uint32_t cnt = a.in_oor.counts[bk];
-                if (cnt > static_cast<uint32_t>(a.in_oor.cap)) {
-                    atomicOr(a.err, kErrOorTruncated);
-                    cnt = static_cast<uint32_t>(a.in_oor.cap);
-                }
-                const int p = xf_pos(a.pni, id);
-                for (uint32_t f = 0; f < cnt; f++) {
-                    const long long c = static_cast<long long>(
-                                            a.in_oor.entries[bk * a.in_oor.cap + f]) - c0;
-                    if (c >= 0 && c < T)
-                        buf[(prow(p) << lgT) + static_cast<int>(c)] = -1;
-                }
-            }
-            __syncthreads();
-        }
-    };
-    load(false);
+    eras_load(buf, tile, a, s_id, s_eid, nullptr);
     // only the syndromes y'_[k, n) are needed from this transform
     lds_intt_top(buf, tw, a.pni, lgT, col, g, G, k, s_rinv, s_syn);
     // c_E = B y'_[k, n): e lazy products per (erasure, column) item
@@ -1271,149 +1253,44 @@ __global__ __launch_bounds__(kLdsThreads) void ntt_eras_kernel(NttLdsArgs a)
         s_cE[it] = fold(fold(acc));  // [-1, 65536]
     }
     __syncthreads();
-    auto store8 = [&](uint16_t* o, const uint32_t (&cv)[8]) {
-        uint4 v;
-        v.x = (cv[0] & 0xffffu) | (cv[1] << 16);
-        v.y = (cv[2] & 0xffffu) | (cv[3] << 16);
-        v.z = (cv[4] & 0xffffu) | (cv[5] << 16);
-        v.w = (cv[6] & 0xffffu) | (cv[7] << 16);
-        *reinterpret_cast<uint4*>(o) = v;
-    };
-    auto record = [&](int r, long long c) {
-        const long long bk = static_cast<long long>(s) * a.out_oor.slots + r;
-        const uint32_t en = atomicAdd(&a.out_oor.counts[bk], 1u);
-        if (en < static_cast<uint32_t>(a.out_oor.cap))
-            a.out_oor.entries[bk * a.out_oor.cap + en] = static_cast<uint32_t>(c);
-    };
-    if (a.mode == kLdsDec) {
-        // the completed codeword -> INTT_n -> the k coefficients (x n^-1)
-        const XfPlan& P = a.pni;
-        if constexpr (C2) {
-            // By linearity, INTT_n's first (unit) pass of the completed
-            // codeword is the image (that pass of the zero-filled one) plus
-            // its response to c_E: erased symbol t sits at element
-            // q0 = t >> lgr[0] of group t & (R0 - 1), and that group's
-            // output u gains c_E w_R1^(-q0 u).  Then only the last pass
-            // runs -- no second load of the received rows, no second unit
-            // pass.  Thread (u, c) owns output u of every group in column c,
-            // so erasures sharing a group add in turn.
-            const int lg0 = P.lgr[0], lg1 = P.lgr[1], m0 = (1 << lg0) - 1;
-            for (int it = tid; it < (1 << (lg1 + lgT)); it += kLdsThreads) {
-                const int u = it >> lgT, c = it & (T - 1);
-                for (int j = 0; j < e; j++) {
-                    const int t = s_eid[j], q0 = t >> lg0;
-                    int32_t* d = buf + (prow(((t & m0) << lg1) + u) << lgT) + c;
-                    // w_R1^-x = w_32^(-x 32 / R1)
-                    const int32_t w = s_rinv[((q0 * u) << (5 - lg1)) & 31];
-                    *d = fold(fold(*d + mul_rt(s_cE[(j << lgT) + c], w)));
-                }
-            }
-            __syncthreads();
-            const int lgs = P.sh[0], lgL = lgs + lg0;
-            const int32_t* twp = tw + P.tw[0];
-            switch (lg0) {
-            case 1:
-                lds_pass<2, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr,
-                                                0, &P, 0);
-                break;
-            case 2:
-                lds_pass<4, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr,
-                                                0, &P, 0);
-                break;
-            case 3:
-                lds_pass<8, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G, nullptr,
-                                                0, &P, 0);
-                break;
-            case 4:
-                lds_pass<16, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G,
-                                                 nullptr, 0, &P, 0);
-                break;
-            default:
-                lds_pass<32, false, true, false>(buf, twp, P.N, lgs, lgL, lgT, col, g, G,
-                                                 nullptr, 0, &P, 0);
-                break;
-            }
-            __syncthreads();
-        } else {
-            load(true);
-            lds_transform<false, true>(buf, tw, P, lgT, col, g, G);
-        }
-        if (a.wide) {
-            if (!wvalid)
-                return;
-            for (int r = rl; r < a.out_rows; r += RPP) {
-                const int4* sp = reinterpret_cast<const int4*>(buf + (prow(r) << lgT) + 8 * cj);
-                const int4 lo = sp[0], hi = sp[1];
-                const int32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                uint32_t cv[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++)
-                    cv[q] = canon_vr(fold(mul_rt(v[q], a.inv_n)));
-                store8(a.out + s * a.oss + r * a.ors + cw, cv);
-            }
-            return;
-        }
-        if (!valid)
-            return;
-        for (int r = g; r < a.out_rows; r += G)
-            a.out[s * a.oss + r * a.ors + cg] = static_cast<uint16_t>(
-                canon_vr(fold(mul_rt(buf[(prow(r) << lgT) + col], a.inv_n))));
+    if (a.mode != kLdsDec) {
+        // systematic (decode: the data rows t < k; encode: the parities
+        // t >= k): codeword symbols, received ones copied, erased ones from c_E
+        lds_write_rows<true>(tile, a, CodewordRows{s_pos, s_cE, lgT, a.out_first, a.src.by_pos});
         return;
     }
-    // systematic (decode: the data rows t < k; encode: the parities t >= k):
-    // codeword symbols, received ones copied, erased ones from c_E
-    if (a.wide) {
-        if (!wvalid)
-            return;
-        for (int r = rl; r < a.out_rows; r += RPP) {
-            const int t = a.out_first + r, pm = s_pos[t];
-            uint16_t* o = a.out + s * a.oss + r * a.ors + cw;
-            if (pm >= 0) {
-                *reinterpret_cast<uint4*>(o) =
-                    *reinterpret_cast<const uint4*>(row_ptr(src.by_pos ? pm : t) + cw);
-                continue;
+    // the completed codeword -> INTT_n -> the k coefficients (x n^-1)
+    const XfPlan& P = a.pni;
+    if constexpr (C2) {
+        // By linearity, INTT_n's first (unit) pass of the completed
+        // codeword is the image (that pass of the zero-filled one) plus
+        // its response to c_E: erased symbol t sits at element
+        // q0 = t >> lgr[0] of group t & (R0 - 1), and that group's
+        // output u gains c_E w_R1^(-q0 u).  Then only the last pass
+        // runs -- no second load of the received rows, no second unit
+        // pass.  Thread (u, c) owns output u of every group in column c,
+        // so erasures sharing a group add in turn.
+        const int lg0 = P.lgr[0], lg1 = P.lgr[1], m0 = (1 << lg0) - 1;
+        for (int it = tid; it < (1 << (lg1 + lgT)); it += kLdsThreads) {
+            const int u = it >> lgT, c = it & (T - 1);
+            for (int j = 0; j < e; j++) {
+                const int t = s_eid[j], q0 = t >> lg0;
+                int32_t* d = buf + (prow(((t & m0) << lg1) + u) << lgT) + c;
+                // w_R1^-x = w_32^(-x 32 / R1)
+                const int32_t w = s_rinv[((q0 * u) << (5 - lg1)) & 31];
+                *d = fold(fold(*d + mul_rt(s_cE[(j << lgT) + c], w)));
             }
-            const int32_t* ce = s_cE + ((-1 - pm) << lgT) + 8 * cj;
-            uint32_t cv[8];
-            bool any = false;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                cv[q] = canon_vr(ce[q]);
-                any |= cv[q] == 65536u;
-            }
-            store8(o, cv);
-            if (any && a.out_oor.counts)
-                for (int q = 0; q < 8; q++)
-                    if (cv[q] == 65536u)
-                        record(r, cw + q);
         }
-        return;
+        __syncthreads();
+        lds_pass_r<false, true>(buf, tw, P, 0, lgT, col, g, G);
+    } else {
+        eras_load(buf, tile, a, s_id, s_eid, s_cE);
+        lds_transform<false, true>(buf, tw, P, lgT, col, g, G);
     }
-    if (!valid)
-        return;
-    for (int r = g; r < a.out_rows; r += G) {
-        const int t = a.out_first + r, pm = s_pos[t];
-        uint32_t cv;
-        if (pm >= 0) {
-            cv = row_ptr(src.by_pos ? pm : t)[cg];
-        } else {
-            cv = canon_vr(s_cE[((-1 - pm) << lgT) + col]);
-            if (cv == 65536u && a.out_oor.counts)
-                record(r, cg);
-        }
-        a.out[s * a.oss + r * a.ors + cg] = static_cast<uint16_t>(cv);
-    }
+    lds_write_rows<false>(tile, a, ImageRows<true>{buf, P, lgT, 0, true, a.inv_n});
 }
 
 namespace {
-
-int ilog2i(long long v)
-{
-    int l = 0;
-    while ((1LL << l) < v)
-        l++;
-    return l;
-}
 
 // radices <= 32, as even as possible
 std::vector<int> radices(int N)
@@ -1512,155 +1389,56 @@ NttCtxLayout ctx_layout_of(const qi_plan* p)
     return NttCtxLayout{p->k, p->n, p->len2k};
 }
 
-// radices <= 32 for the LDS passes, as even as possible (fewest twiddled
-// passes)
-XfPlan xf_plan(int N)
+// The LDS engine's twiddle tables (qi_plan::d_ldstw), by lds_table_layout:
+// pass q of a length-N transform holds w_{L_q}^{+-j u} at j R_q + u, with
+// w_L = w_nmax^{nmax / L}
+std::vector<int32_t> lds_tables(const qi_plan* p)
 {
-    // radices <= 32 as even as possible (2048: 16, 16, 8).  Round 6 tried the
-    // radix-32 unit pass the image's row padding keeps conflict-free (2048:
-    // 8, 8, 32; the k600 encode had 58 % of its LDS cycles in bank
-    // conflicts): 2.06-2.09 -> 2.17-2.26 ms, the radix-8 passes cost more
-    // than the conflicts (profiles/r6_ab_notes.txt), so the plan stays
-    XfPlan P{};
-    P.N = N;
-    const int bits = ilog2i(N);
-    P.np = std::max(1, (bits + 4) / 5);
-    int left = bits, sh = bits;
-    for (int q = 0; q < P.np; q++) {
-        const int b = (left + (P.np - q) - 1) / (P.np - q);
-        P.lgr[q] = b;
-        sh -= b;
-        P.sh[q] = sh;
-        left -= b;
-    }
-    return P;
-}
-
-// The four transforms' pass twiddle tables, back to back (offsets kept 4-
-// aligned for the vector LDS reads): pass q of a length-N transform holds
-// w_{L_q}^{+-j u} at j R_q + u, with w_L = w_nmax^{nmax / L}.  Fills `tab`
-// when given; returns the total words.
-// Order INTT_n, NTT_2k, INTT_2k, NTT_n: a decode stages the first three, a
-// non-systematic encode the last one, systematic codes all four.
-enum : int { kTwPni = 0, kTwP2f = 1, kTwP2i = 2, kTwPnf = 3 };
-
-int lds_tables(const qi_plan* p, XfPlan* pl, std::vector<int32_t>* tab, int* twist = nullptr,
-               int* rinv_off = nullptr)
-{
+    const LdsTables T = lds_table_layout(p->n, p->len2k);
+    std::vector<int32_t> tab(T.words);
     const uint32_t w = root_of_unity(static_cast<uint32_t>(p->nmax));
-    const int h = p->len2k / 2;
-    const int Ns[4] = {p->n, h, h, p->n};
     const bool invs[4] = {true, false, true, false};
-    int off = 0;
-    for (int t = 0; t < 4; t++) {
-        if (t == kTwPnf) {
-            if (twist)
-                *twist = off;
-            // the decode's twist w2k^{+-t}, t < h, between INTT_h and NTT_n
-            // (a decode stages [0, NTT_n's offset))
-            if (tab) {
-                tab->resize(off + 2 * h);
-                const uint32_t w2 = powmod_c(w, static_cast<uint32_t>(p->nmax / p->len2k));
-                const uint32_t w2i = invmod_c(w2);
-                for (int i = 0; i < h; i++) {
-                    (*tab)[off + i] = balanced(powmod_c(w2, static_cast<uint32_t>(i)));
-                    (*tab)[off + h + i] = balanced(powmod_c(w2i, static_cast<uint32_t>(i)));
-                }
-            }
-            off += (2 * h + 3) & ~3;
+    for (int t = 0; t < 4; t++)
+        for (int q = 0; q < T.pl[t].np; q++) {
+            const int R = 1 << T.pl[t].lgr[q], sq = 1 << T.pl[t].sh[q], L = R * sq;
+            const uint32_t wl = powmod_c(w, static_cast<uint32_t>(p->nmax / L));
+            const uint32_t wb = invs[t] ? invmod_c(wl) : wl;
+            for (int j = 0; j < sq; j++)
+                for (int u = 0; u < R; u++)
+                    tab[T.pl[t].tw[q] + j * R + u] =
+                        balanced(powmod_c(wb, static_cast<uint32_t>(j * u % L)));
         }
-        pl[t] = xf_plan(Ns[t]);
-        const bool inv = invs[t];
-        for (int q = 0; q < pl[t].np; q++) {
-            const int R = 1 << pl[t].lgr[q], sq = 1 << pl[t].sh[q], L = R * sq;
-            pl[t].tw[q] = off;
-            if (tab) {
-                tab->resize(off + L);
-                const uint32_t wl = powmod_c(w, static_cast<uint32_t>(p->nmax / L));
-                const uint32_t wb = inv ? invmod_c(wl) : wl;
-                for (int j = 0; j < sq; j++)
-                    for (int u = 0; u < R; u++)
-                        (*tab)[off + j * R + u] = balanced(
-                            powmod_c(wb, static_cast<uint32_t>(j * u % L)));
-            }
-            off += (L + 3) & ~3;
-        }
+    // the decode's twist w2k^{+-t}, t < h, between INTT_h and NTT_n
+    const int h = p->len2k / 2;
+    const uint32_t w2 = powmod_c(w, static_cast<uint32_t>(p->nmax / p->len2k));
+    const uint32_t w2i = invmod_c(w2);
+    for (int i = 0; i < h; i++) {
+        tab[T.twist + i] = balanced(powmod_c(w2, static_cast<uint32_t>(i)));
+        tab[T.twist + h + i] = balanced(powmod_c(w2i, static_cast<uint32_t>(i)));
     }
     // w_32^-x, x < 32: the inverse R-th roots of INTT_n's DIT passes for
     // every radix R | 32 (w_R^-x = w_32^(-x 32 / R)), for the erasure
     // decode's pruned last pass (lds_intt_top) and its two-pass completion
-    if (rinv_off)
-        *rinv_off = off;
-    if (tab) {
-        tab->resize(off + 32);
-        const uint32_t wi = invmod_c(root_of_unity(32u));
-        for (int x = 0; x < 32; x++)
-            (*tab)[off + x] = balanced(powmod_c(wi, static_cast<uint32_t>(x)));
-    }
-    off += 32;
-    if (tab)
-        tab->resize(off);
-    return off;
+    const uint32_t wi = invmod_c(root_of_unity(32u));
+    for (int x = 0; x < 32; x++)
+        tab[T.rinv + x] = balanced(powmod_c(wi, static_cast<uint32_t>(x)));
+    return tab;
 }
 
-// rows: the image's rows (nmax; n for the non-systematic encode, which
-// runs NTT_n alone)
-size_t lds_bytes(const qi_plan* p, int lgT, int tw_words, bool twg, int rows)
+// ntt_geom.h on a plan
+LdsGeom lds_geom(const qi_plan* p, int mode)
 {
-    return ((static_cast<size_t>(prow(rows)) << lgT) +
-            lds_side_words(tw_words, p->k, p->len2k, twg)) *
-           4;
+    return qi::lds_geom(p->k, p->n, p->len2k, mode);
 }
 
-constexpr size_t kLdsCap = 160 * 1024;  // LDS per CU
-
-// the table range [lo, hi) a mode stages (see the table order above)
-void lds_table_range(const qi_plan* p, int mode, int* lo, int* hi)
+LdsGeom eras_geom(const qi_plan* p, bool dec)
 {
-    XfPlan pl[4];
-    const int end = lds_tables(p, pl, nullptr);
-    if (mode == kLdsEnc) {
-        *lo = pl[kTwPnf].tw[0];
-        *hi = end;
-    } else {
-        *lo = 0;
-        *hi = mode == kLdsDec ? pl[kTwPnf].tw[0] : end;
-    }
-}
-
-// columns per workgroup: the widest tile (<= 64 columns) that leaves room
-// for two workgroups per CU with the tables staged, else with the tables
-// read from global memory (*twg), else one workgroup per CU (at least 8
-// columns)
-int lds_geom(const qi_plan* p, int tw_words, bool* twg, int rows)
-{
-    for (int g = 0; g < 2; g++)
-        for (int lg = 6; lg >= 3; lg--)
-            if (lds_bytes(p, lg, tw_words, g == 1, rows) <= kLdsCap / 2) {
-                *twg = g == 1;
-                return lg;
-            }
-    *twg = false;
-    return lds_bytes(p, 3, tw_words, false, rows) <= kLdsCap ? 3 : -1;
+    return qi::eras_geom(p->k, p->n, p->len2k, dec);
 }
 
 bool lds_engine(const qi_plan* p)
 {
-    if (p->nmax > kLdsMaxN)
-        return false;
-    int lo, hi;
-    lds_table_range(p, kLdsSysDec, &lo, &hi);  // the largest set
-    bool twg;
-    return lds_geom(p, hi - lo, &twg, p->nmax) >= 0;
-}
-
-// ---- erasure decode (ntt_eras_kernel) ----
-// the two-pass completion (ntt_eras_kernel<., true>): the non-systematic
-// decode of a two-pass INTT_n; it reads no position map, and that region
-// holds the e x T syndromes instead
-static bool eras_c2(const XfPlan& pni)
-{
-    return pni.np == 2;
+    return qi::lds_engine(p->k, p->n, p->len2k);
 }
 
 bool eras_plan(const qi_plan* p)
@@ -1673,60 +1451,79 @@ ErasCtxLayout eras_layout(const qi_plan* p)
     return ErasCtxLayout{p->k, p->n, p->n - p->k};
 }
 
-size_t eras_bytes(const qi_plan* p, int lgT, int tw_words, bool twg, bool c2)
+// what every launch of the two kernels fills alike
+NttLdsArgs lds_args(const qi_plan* p, int mode, long long words, const RowSrc& src,
+                    const int32_t* ctx, long long cs, RowDst out, int out_first, int out_rows)
 {
-    const ErasCtxLayout L = eras_layout(p);
-    const size_t posw = c2 ? static_cast<size_t>(L.e) << lgT : static_cast<size_t>(L.n);
-    return ((static_cast<size_t>(prow(p->n)) << lgT) + (twg ? 0 : tw_words) + L.k + posw + L.e +
-            static_cast<size_t>(L.e) * L.e + (static_cast<size_t>(L.e) << lgT) + 32) *
-           4;
+    NttLdsArgs a{};
+    a.mode = mode;
+    a.k = p->k;
+    a.n = p->n;
+    a.len2k = p->len2k;
+    a.words = words;
+    a.src = src;
+    a.ctx = ctx;
+    a.cs = cs;
+    a.out = out.base;
+    a.oss = out.ss;
+    a.ors = out.rs;
+    a.out_first = out_first;
+    a.out_rows = out_rows;
+    a.err = p->d_err;
+    return a;
 }
 
-// INTT_n's tables only: [0, NTT_h's first table)
-int eras_tw_words(const qi_plan* p, XfPlan* pl)
+// 16-byte row pieces: every row base and stride 8-word aligned and
+// words % 8 == 0
+bool rows_wide(const NttLdsArgs& a)
 {
-    lds_tables(p, pl, nullptr);
-    return pl[kTwP2f].tw[0];
+    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    auto a8 = [](long long v) { return (v & 7) == 0; };
+    const RowSrc& r = a.src;
+    return (a.words & 7) == 0 && al(r.base0) && a8(r.ss0) && a8(r.rs0) &&
+           (!r.base1 || (al(r.base1) && a8(r.ss1) && a8(r.rs1))) && al(a.out) && a8(a.oss) &&
+           a8(a.ors);
 }
 
-// tile width (log2 T) at two workgroups per CU, tables staged when they
-// fit; *c2: the launch takes the two-pass completion (dec: a non-systematic
-// decode)
-int eras_geom(const qi_plan* p, bool dec, bool* twg, bool* c2)
+// column tiles of 2^lgT per stripe; -1 when S stripes of them pass a grid
+int lds_tiles(long long words, int lgT, int S)
 {
-    XfPlan pl[4];
-    const int tw_words = eras_tw_words(p, pl);
-    for (int g = 0; g < 2; g++)
-        for (int lg = 6; lg >= 3; lg--) {
-            const bool two = dec && eras_c2(pl[kTwPni]);
-            if (eras_bytes(p, lg, tw_words, g == 1, two) <= kLdsCap / 2) {
-                *twg = g == 1;
-                *c2 = two;
-                return lg;
-            }
-        }
-    *twg = false;
-    *c2 = dec && eras_c2(pl[kTwPni]);
-    return eras_bytes(p, 3, tw_words, false, *c2) <= kLdsCap ? 3 : -1;
+    const long long tiles = (words + (1LL << lgT) - 1) >> lgT;
+    return tiles * S > 0x7fffffffLL ? -1 : static_cast<int>(tiles);
+}
+
+// One launch of an instantiation of either kernel over S stripes, tile width
+// and LDS bytes from its geometry: opts in above 64 KiB
+using LdsKernel = void (*)(NttLdsArgs);
+
+int launch_lds(LdsKernel fn, const LdsGeom& g, NttLdsArgs a, int S, hipStream_t st)
+{
+    a.lgT = g.lgT;
+    a.tiles = lds_tiles(a.words, g.lgT, S);
+    if (a.tiles < 0)
+        return -3;
+    a.wide = rows_wide(a);
+    if (g.bytes > 65536 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(g.bytes)) != hipSuccess)
+        return -2;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(a.tiles) * static_cast<unsigned>(S)),
+                       dim3(kLdsThreads), g.bytes, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int eras_launch(const qi_plan* p, NttLdsArgs a, int S, hipStream_t st)
 {
-    a.k = p->k;
-    a.n = p->n;
-    a.len2k = p->len2k;
-    a.nmax = p->n;
-    XfPlan pl[4];
-    a.tw_words = eras_tw_words(p, pl);
-    a.pni = pl[kTwPni];
-    a.tw = p->d_ldstw;
-    int rinv_off = 0;
-    lds_tables(p, pl, nullptr, nullptr, &rinv_off);
-    a.rinv = p->d_ldstw ? p->d_ldstw + rinv_off : nullptr;
-    bool twg, c2;
-    a.lgT = eras_geom(p, a.mode == kLdsDec, &twg, &c2);
-    if (a.lgT < 0 || !a.tw)
+    const LdsGeom g = eras_geom(p, a.mode == kLdsDec);
+    if (g.lgT < 0 || !p->d_ldstw)
         return -3;
+    const LdsTables T = lds_table_layout(p->n, p->len2k);
+    a.nmax = p->n;
+    a.pni = T.pl[kTwPni];
+    a.tw = p->d_ldstw;
+    a.tw_words = g.tw_words;
+    a.rinv = p->d_ldstw + T.rinv;
     const ErasCtxLayout L = eras_layout(p);
     a.ids_off = static_cast<int>(L.ids_off());
     a.pos_off = static_cast<int>(L.pos_off());
@@ -1734,99 +1531,36 @@ int eras_launch(const qi_plan* p, NttLdsArgs a, int S, hipStream_t st)
     a.eras_eid = static_cast<int>(L.eid_off());
     a.eras_b = static_cast<int>(L.b_off());
     a.inv_n = balanced(invmod_c(static_cast<uint32_t>(p->n)));
-    const long long tiles = (a.words + (1LL << a.lgT) - 1) >> a.lgT;
-    if (tiles * S > 0x7fffffffLL)
-        return -3;
-    a.tiles = static_cast<int>(tiles);
-    {
-        auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        auto a8 = [](long long v) { return (v & 7) == 0; };
-        const RowSrc& r = a.src;
-        a.wide = (a.words & 7) == 0 && al(r.base0) && a8(r.ss0) && a8(r.rs0) &&
-                 (!r.base1 || (al(r.base1) && a8(r.ss1) && a8(r.rs1))) && al(a.out) &&
-                 a8(a.oss) && a8(a.ors);
-    }
-    const size_t lds = eras_bytes(p, a.lgT, a.tw_words, twg, c2);
-    const void* fn =
-        twg ? (c2 ? reinterpret_cast<const void*>(&ntt_eras_kernel<true, true>)
-                  : reinterpret_cast<const void*>(&ntt_eras_kernel<true, false>))
-            : (c2 ? reinterpret_cast<const void*>(&ntt_eras_kernel<false, true>)
-                  : reinterpret_cast<const void*>(&ntt_eras_kernel<false, false>));
-    if (lds > 65536 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds)) != hipSuccess)
-        return -2;
-    const dim3 grid(static_cast<unsigned>(tiles * S));
-    if (twg && c2)
-        hipLaunchKernelGGL((ntt_eras_kernel<true, true>), grid, dim3(kLdsThreads), lds, st, a);
-    else if (twg)
-        hipLaunchKernelGGL((ntt_eras_kernel<true, false>), grid, dim3(kLdsThreads), lds, st, a);
-    else if (c2)
-        hipLaunchKernelGGL((ntt_eras_kernel<false, true>), grid, dim3(kLdsThreads), lds, st, a);
-    else
-        hipLaunchKernelGGL((ntt_eras_kernel<false, false>), grid, dim3(kLdsThreads), lds, st,
-                           a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_lds(g.c2 ? ntt_eras_kernel<true> : ntt_eras_kernel<false>, g, a, S, st);
 }
 
 int lds_launch(const qi_plan* p, NttLdsArgs a, int S, hipStream_t st)
 {
-    a.k = p->k;
-    a.n = p->n;
-    a.len2k = p->len2k;
-    a.nmax = p->nmax;
-    XfPlan pl[4];
-    int twist = 0;
-    lds_tables(p, pl, nullptr, &twist);
-    int lo, hi;
-    lds_table_range(p, a.mode, &lo, &hi);
-    for (XfPlan& x : pl)
-        for (int q = 0; q < x.np; q++)
-            x.tw[q] -= lo;  // offsets within the staged range
-    a.twist = twist - lo;  // (read by decodes only, which stage from 0)
-    a.pni = pl[kTwPni];
-    a.p2f = pl[kTwP2f];
-    a.p2i = pl[kTwP2i];
-    a.pnf = pl[kTwPnf];
-    a.tw = p->d_ldstw + lo;
-    a.tw_words = hi - lo;
     // the non-systematic encode runs NTT_n alone and could take an n-row
     // image (wider tiles where len_2k > n); measured slower at k1000 (T = 16
     // instead of 8: encode 1.27-1.29 -> 1.33 ms, gpurun_out ab_route), so the
     // image stays nmax rows (the n-row variant measured 1.31 vs 1.25 ms
     // after the padded rows, round 4)
-    bool twg;
-    a.lgT = lds_geom(p, a.tw_words, &twg, a.nmax);
-    if (a.lgT < 0)
+    const LdsGeom g = lds_geom(p, a.mode);
+    if (g.lgT < 0)
         return -3;
+    LdsTables T = lds_table_layout(p->n, p->len2k);
+    for (XfPlan& x : T.pl)
+        for (int q = 0; q < x.np; q++)
+            x.tw[q] -= g.tw_lo;  // offsets within the staged range
+    a.nmax = p->nmax;
+    a.twist = T.twist - g.tw_lo;  // (read by decodes only, which stage from 0)
+    a.pni = T.pl[kTwPni];
+    a.p2f = T.pl[kTwP2f];
+    a.p2i = T.pl[kTwP2i];
+    a.pnf = T.pl[kTwPnf];
+    a.tw = p->d_ldstw + g.tw_lo;
+    a.tw_words = g.tw_words;
     const NttCtxLayout L = ctx_layout_of(p);
     a.ids_off = static_cast<int>(L.ids_off());
     a.c_off = static_cast<int>(L.c_off());
     a.pos_off = static_cast<int>(L.pos_off());
-    const long long tiles = (a.words + (1LL << a.lgT) - 1) >> a.lgT;
-    if (tiles * S > 0x7fffffffLL)
-        return -3;
-    a.tiles = static_cast<int>(tiles);
-    {
-        auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        auto a8 = [](long long v) { return (v & 7) == 0; };
-        const RowSrc& r = a.src;
-        a.wide = (a.words & 7) == 0 && al(r.base0) && a8(r.ss0) && a8(r.rs0) &&
-                 (!r.base1 || (al(r.base1) && a8(r.ss1) && a8(r.rs1))) && al(a.out) &&
-                 a8(a.oss) && a8(a.ors);
-    }
-    const size_t lds = lds_bytes(p, a.lgT, a.tw_words, twg, a.nmax);
-    const void* fn = twg ? reinterpret_cast<const void*>(&ntt_lds_kernel<true>)
-                         : reinterpret_cast<const void*>(&ntt_lds_kernel<false>);
-    if (lds > 65536 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds)) != hipSuccess)
-        return -2;
-    if (twg)
-        hipLaunchKernelGGL(ntt_lds_kernel<true>, dim3(static_cast<unsigned>(tiles * S)),
-                           dim3(kLdsThreads), lds, st, a);
-    else
-        hipLaunchKernelGGL(ntt_lds_kernel<false>, dim3(static_cast<unsigned>(tiles * S)),
-                           dim3(kLdsThreads), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_lds(g.twg ? ntt_lds_kernel<true> : ntt_lds_kernel<false>, g, a, S, st);
 }
 
 RowSrc offset_src(RowSrc s, int sg0, long long c0)
@@ -1926,11 +1660,6 @@ static int launch_ntt_ctx(const qi_plan* p, const NttCtxArgs& a, int S, hipStrea
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-bool eras_shape(int k, int n)
-{
-    return n <= kLdsMaxN && n - k <= kErasMax;
-}
-
 long long ntt_ctx_words(const qi_plan* p)
 {
     return eras_plan(p) ? eras_layout(p).words() : ctx_layout_of(p).words();
@@ -1994,9 +1723,7 @@ int ntt_plan_init(qi_plan* p)
     if (hipMemcpy(d, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return -2;
     if (lds_engine(p) || eras_plan(p)) {
-        XfPlan pl[4];
-        std::vector<int32_t> tab;
-        lds_tables(p, pl, &tab);
+        const std::vector<int32_t> tab = lds_tables(p);
         if (hipMalloc(&p->d_ldstw, tab.size() * 4) != hipSuccess ||
             hipMemcpy(p->d_ldstw, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) !=
                 hipSuccess)
@@ -2016,22 +1743,15 @@ int ntt_plan_init(qi_plan* p)
 
 std::string ntt_kernel_names(const qi_plan* p, bool decode)
 {
-    if (eras_plan(p) && (decode || p->sys)) {
-        bool twg, c2;
-        (void)eras_geom(p, decode && !p->sys, &twg, &c2);
+    if (eras_plan(p) && (decode || p->sys))
         return std::string(decode ? "eras_ctx_kernel + " : "") + "ntt_eras_kernel<" +
-               (twg ? "true" : "false") + ", " + (c2 ? "true" : "false") + ">";
-    }
+               (eras_geom(p, decode && !p->sys).c2 ? "true" : "false") + ">";
     if (!lds_engine(p))
         return decode ? "ntt_ctx_kernel + ntt_expand_kernel + ntt_fix_kernel + ntt_pass_kernel"
                       : "ntt_pass_kernel";
-    const int mode = decode ? (p->sys ? kLdsSysDec : kLdsDec) : (p->sys ? kLdsSysEnc : kLdsEnc);
-    int lo, hi;
-    lds_table_range(p, mode, &lo, &hi);
-    bool twg;
-    (void)lds_geom(p, hi - lo, &twg, p->nmax);
     return std::string(decode ? "ntt_ctx_kernel + " : "") +
-           (twg ? "ntt_lds_kernel<true>" : "ntt_lds_kernel<false>");
+           (lds_geom(p, lds_mode(p->sys, decode)).twg ? "ntt_lds_kernel<true>"
+                                                      : "ntt_lds_kernel<false>");
 }
 
 void ntt_plan_free(qi_plan* p)
@@ -2054,40 +1774,17 @@ int ntt_encode(const qi_plan* p, const uint16_t* data, long long dss, long long 
 {
     if (S <= 0 || words <= 0)
         return 0;
-    if (p->sys && eras_plan(p)) {
-        // the parities as the erased symbols of the data's codeword
-        NttLdsArgs a{};
-        a.mode = kLdsSysEnc;
-        a.words = words;
-        a.src = RowSrc{data, dss, drs, 1 << 30, nullptr, 0, 0, 1, p->k, 0};
-        a.ctx = p->d_sysctx;
-        a.cs = 0;
-        a.out = out.base;
-        a.oss = out.ss;
-        a.ors = out.rs;
-        a.out_first = p->k;
-        a.out_rows = p->n_outputs;
+    // systematic with few parities: they are the erased symbols of the
+    // data's codeword
+    const bool eras = p->sys && eras_plan(p);
+    if (eras || lds_engine(p)) {
+        NttLdsArgs a = lds_args(p, p->sys ? kLdsSysEnc : kLdsEnc, words,
+                                RowSrc{data, dss, drs, 1 << 30, nullptr, 0, 0, 1, p->k, 0},
+                                p->sys ? p->d_sysctx : nullptr, 0, out, p->sys ? p->k : 0,
+                                p->n_outputs);
         if (oor && oor->counts)
             a.out_oor = *oor;
-        a.err = p->d_err;
-        return eras_launch(p, a, S, st);
-    }
-    if (lds_engine(p)) {
-        NttLdsArgs a{};
-        a.mode = p->sys ? kLdsSysEnc : kLdsEnc;
-        a.words = words;
-        a.src = RowSrc{data, dss, drs, 1 << 30, nullptr, 0, 0, 1, p->k, 0};
-        a.ctx = p->sys ? p->d_sysctx : nullptr;
-        a.cs = 0;
-        a.out = out.base;
-        a.oss = out.ss;
-        a.ors = out.rs;
-        a.out_first = p->sys ? p->k : 0;
-        a.out_rows = p->n_outputs;
-        if (oor && oor->counts)
-            a.out_oor = *oor;
-        a.err = p->d_err;
-        return lds_launch(p, a, S, st);
+        return eras ? eras_launch(p, a, S, st) : lds_launch(p, a, S, st);
     }
     const Slicing sl = slicing(p, words, S);
     const long long sss = static_cast<long long>(p->nmax) * sl.W;
@@ -2159,21 +1856,11 @@ int ntt_decode(const qi_plan* p, const int32_t* ctx, long long cs, RowSrc src,
     if (S <= 0 || words <= 0)
         return 0;
     if (lds_engine(p) || eras_plan(p)) {
-        NttLdsArgs a{};
-        a.mode = p->sys ? kLdsSysDec : kLdsDec;
-        a.words = words;
-        a.src = src;
-        a.ctx = ctx;
-        a.cs = cs;
+        NttLdsArgs a = lds_args(p, p->sys ? kLdsSysDec : kLdsDec, words, src, ctx, cs, out, 0,
+                                p->k);
         if (in_oor && in_oor->counts)
             a.in_oor = *in_oor;
         a.slot_base = slot_base;
-        a.out = out.base;
-        a.oss = out.ss;
-        a.ors = out.rs;
-        a.out_first = 0;
-        a.out_rows = p->k;
-        a.err = p->d_err;
         return eras_plan(p) ? eras_launch(p, a, S, st) : lds_launch(p, a, S, st);
     }
     const Slicing sl = slicing(p, words, S);

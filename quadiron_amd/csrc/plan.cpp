@@ -9,6 +9,7 @@
 #include "../../include/qi_gpu.h"
 #include "gf65537.h"
 #include "matrix_pack.h"
+#include "ntt_geom.h"  // eras_shape
 #include "qi_internal.h"
 #include "qi_plan.h"
 

@@ -115,11 +115,10 @@ struct qi_plan {
 namespace qi {
 // ---- general-k path (ntt.hip) ----
 int ntt_plan_init(qi_plan* p);
-// the erasure decode's shape (n <= 2048, n - k <= 64; ntt.hip)
-bool eras_shape(int k, int n);
 // the NTT engine's kernels for an encode or a decode (a decode's list starts
-// with its context builder): ntt_eras_kernel<TWG> (few erasures), ntt_lds_kernel<TWG>
-// (max(n, len_2k) <= 2048) or the multi-pass engine
+// with its context builder): ntt_eras_kernel<C2> (few erasures: eras_shape,
+// ntt_geom.h), ntt_lds_kernel<TWG> (max(n, len_2k) <= 2048) or the multi-pass
+// engine
 std::string ntt_kernel_names(const qi_plan* p, bool decode);
 void ntt_plan_free(qi_plan* p);
 long long ntt_ctx_words(const qi_plan* p);

@@ -438,6 +438,36 @@ def test_batch_vs_oracle(k, m, sys_, S, P):
     _batch_roundtrip(k, m, sys_, S, P, seed=k * 1000 + m + P, n_craft=16)
 
 
+LDS = "ntt_lds_kernel<false>"        # pass tables and C staged in LDS
+LDS_TWG = "ntt_lds_kernel<true>"     # ... read from global memory
+ERAS_C2 = "ntt_eras_kernel<true>"    # two-pass completion
+ERAS = "ntt_eras_kernel<false>"      # second load + INTT_n
+
+
+@pytest.mark.parametrize("P", [19, 24])
+@pytest.mark.parametrize("k,m,sys_,enc,dec", [
+    (257, 255, 0, LDS, LDS),          # T = 16 (encode) / 8 (decode)
+    (257, 255, 1, LDS, LDS),
+    (513, 511, 0, LDS_TWG, LDS_TWG),
+    (513, 511, 1, LDS_TWG, LDS_TWG),
+    (450, 62, 0, LDS, ERAS_C2),
+    (450, 62, 1, ERAS, ERAS),
+    (1990, 58, 0, "ntt_pass_kernel", ERAS),   # n = 2048: three-pass INTT_n
+])
+def test_lds_engine_variants(k, m, sys_, enc, dec, P):
+    """Every instantiation of the LDS engine's two kernels at the smallest
+    code that reaches it, on the narrow lanes with a ragged last tile (P = 19)
+    and on the 16-byte lanes (P = 24: the last tile of a T = 16 kernel has
+    half its wide lanes past the row, a T = 8 kernel runs three tiles)."""
+    _torch()
+    import quadiron_amd as qa
+    names = qa.Plan(k, m, sys_).kernels(P)
+    print(f"\n{(k, m, sys_, P)}: {names}")
+    enc_names, dec_names = names[len("encode="):].split("; decode=")
+    assert enc_names.endswith(enc) and dec_names.endswith(dec), names
+    _batch_roundtrip(k, m, sys_, 2, P, seed=[k, m, sys_, P], n_craft=6)
+
+
 def _random_shapes(n, seed):
     """n codes drawn from a fixed seed: k near every routing boundary (the
     matrix-core K-steps, the context kernels, the NTT engine) or uniform up

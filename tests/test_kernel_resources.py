@@ -45,7 +45,8 @@ def test_report_lists_the_hot_kernels():
     ks = kernels()
     for name in ("encode_fnt_kernel", "matrix_mfma_kernel", "matrix_kernel",
                  "decode_ctx_kernel", "matrix_redo_kernel", "ntt_pass_kernel",
-                 "ntt_ctx_kernel", "ntt_expand_kernel", "ntt_fix_kernel"):
+                 "ntt_ctx_kernel", "ntt_expand_kernel", "ntt_fix_kernel",
+                 "ntt_lds_kernel", "ntt_eras_kernel"):
         assert any(name in k for k in ks), name
 
 
@@ -80,3 +81,14 @@ def test_mfma_kernel_occupancy():
         if ks >= 8:
             want = 2  # 128 < 16 KS rows: 198-248 VGPRs
         assert v.get("Occupancy", 0) >= want, (k, v, want)
+
+
+def test_lds_engine_kernel_occupancy():
+    """lds_geom / eras_geom (ntt_geom.h) size the tiles for two 512-thread
+    workgroups per CU: 4 waves per SIMD, so at most 128 VGPRs, in every
+    instantiation of the LDS engine's two kernels."""
+    found = {k: v for k, v in kernels().items()
+             if re.search(r"ntt_(lds|eras)_kernelILb[01]EEE", k)}
+    assert len(found) == 4, sorted(found)
+    for k, v in found.items():
+        assert v.get("Occupancy", 0) >= 4 and v.get("ScratchSize") == 0, (k, v)
