@@ -143,6 +143,15 @@ int qi_gpu_decode_ctx(qi_plan* plan, const uint16_t* d_ids,
  * with slot = f - k (systematic) or f (non-systematic).
  * OOR buckets of the coded rows are indexed by the same slot (slots =
  * n_outputs); pass NULL counts when there are none.  Output: k data rows.
+ * NULL counts mean "no marks" whatever the context was built with: the
+ * decode is then the interpolation of the stored symbols (a result of 65536
+ * is stored as 0), on every kernel path, and marks routed into the context
+ * by qi_gpu_decode_ctx are NOT restored.  Rows that carry marks need their
+ * buckets at decode time; giving them to the context builder as well only
+ * makes that decode faster.  (Only the matrix contexts hold routed marks; an
+ * NTT context holds none, so "restore what the context holds" could not be
+ * kept for every k, and neither could a check.)  The same holds for
+ * qi_gpu_decode_packed, qi_gpu_repair and qi_gpu_verify and their contexts.
  * The context is not const in effect: a decode whose rows the matrix cores
  * cannot address fills the context's lazily built sections (the dot2
  * kernel's packed rows for k <= 256, the NTT engine's half for 256 < k <=

@@ -2187,6 +2187,12 @@ int launch_matrix(const MatLayout& L, const int32_t* mat, long long ms,
     if (in_oor && !slow.base)
         return -1;  // input marks need the slow-tile lists
     const Oor none{nullptr, nullptr, 0, 0};
+    // no input buckets: no marks.  The route table goes with them: the
+    // operand-stationary kernel and the NTT engine restore nothing without
+    // the buckets, so the kernels that read the table alone must not either
+    // (qi_gpu.h, qi_gpu_decode)
+    if (!in_oor)
+        route = nullptr;
     MatArgs a{L, mat, ms, ids, is, src, dst, mat_ext(src, L.R, dst, words), words, 0, in_oor ? *in_oor : none, slot_base, out_oor ? *out_oor : none,
               rowmap, route, rstride, in_oor ? slow : SlowList{nullptr, 0}, err};
     // a fused check (ver): the stored rows are the source regions', nothing

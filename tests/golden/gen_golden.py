@@ -285,6 +285,69 @@ def _gen_cabi_scn(ref, ora, name, k, m, sys_, block_bytes, seed, patterns,
           f"reconstructs={len(rec_dest)}")
 
 
+FILL = 0xA5   # buffers the reference must leave alone start as this byte
+
+
+def _gen_masked(ref, ora, name, k, m, sys_, pkt, block_bytes, seed, n_craft,
+                out_dir):
+    """Unwanted outputs (src/fec_base.h:1066-1151, :1177-1321,
+    src/quadiron_c.cpp:73-140): an alternating mask on the block encode and
+    on the C-ABI encode, a one-hot mask (the last data row) on the block
+    decode.  Every buffer the calls may write starts as FILL, so the stored
+    results show what the reference writes and what it leaves untouched; the
+    property lists are those of ALL outputs."""
+    rng = np.random.default_rng(seed)
+    codec = Codec()
+    assert ora.qo_codec_init(C.byref(codec), k, m, sys_) == 0
+    no = codec.n_outputs
+    first = k if sys_ else 0
+    data = rng.integers(0, 256, (k, block_bytes), dtype=np.uint8)
+    craft_oor(ora, codec, data, rng, n_craft)
+    cap = 64
+    enc_wanted = np.zeros(no, np.int32)
+    enc_wanted[::2] = 1
+
+    def encode(wanted):
+        outs = np.full((no, block_bytes), FILL, np.uint8)
+        oor = np.zeros((no, cap), np.uint32)
+        cnt = np.zeros(no, np.uint32)
+        rows = [data[i].copy() for i in range(k)]
+        orow = [outs[i] if wanted[i] else None for i in range(no)]
+        ref.ref_encode_blocks(sys_, k, m, C.c_size_t(pkt), ptrs(rows), ptrs(orow),
+                              C.c_size_t(block_bytes), vp(oor), vp(cnt),
+                              C.c_uint32(cap))
+        return outs, oor, cnt
+    full, oor, cnt = encode(np.ones(no, np.int32))
+    outs, m_oor, m_cnt = encode(enc_wanted)
+    assert (m_oor == oor).all() and (m_cnt == cnt).all() and cnt.sum() > 0
+    assert cnt[enc_wanted == 0].sum() > 0, "no mark on an unwanted output"
+    # m erasures with data fragment 0 among them; only the last row wanted
+    missing = np.zeros(k + m, np.int32)
+    missing[[0] + list(rng.choice(np.arange(1, k + m - 1), m - 1, replace=False))] = 1
+    dec_wanted = np.zeros(k, np.int32)
+    dec_wanted[k - 1] = 1
+    dec = [data[i].copy() if sys_ and not missing[i]
+           else np.full(block_bytes, FILL, np.uint8) for i in range(k)]
+    par = [None if missing[first + i] else full[i].copy() for i in range(no)]
+    assert ref.ref_decode_blocks(sys_, k, m, C.c_size_t(pkt), ptrs(dec), ptrs(par),
+                                 vp(oor), vp(cnt), C.c_uint32(cap), vp(missing),
+                                 vp(dec_wanted), C.c_size_t(block_bytes)) == 1
+    # the C-ABI encode with the same alternating mask
+    md = ref.ref_metadata_size(C.c_size_t(block_bytes))
+    cd = [np.concatenate([np.full(md, FILL, np.uint8), data[i]]) for i in range(k)]
+    cp = [np.full(md + block_bytes, FILL, np.uint8) for _ in range(m)]
+    assert ref.ref_c_encode(sys_, k, m, ptrs(cd), ptrs(cp), vp(enc_wanted),
+                            C.c_size_t(block_bytes)) == 0
+    np.savez_compressed(
+        os.path.join(out_dir, name + ".npz"),
+        params=np.array([k, m, sys_, pkt, block_bytes, cap, md], np.int64),
+        data=data, enc_wanted=enc_wanted, outputs=outs, full_outputs=full,
+        oor=oor, oor_count=cnt, missing=missing, dec_wanted=dec_wanted,
+        decoded=np.stack(dec), cabi_data=np.stack(cd), cabi_parity=np.stack(cp))
+    print(f"{name}: masks k={k} m={m} sys={sys_} block={block_bytes} "
+          f"oor={int(cnt.sum())}")
+
+
 def main():
     if not os.path.exists(REF):
         sys.exit("build the reference first: make -C oracle ref")
@@ -391,6 +454,13 @@ def main():
                  [i for i in range(64) if i % 4 != 1][:47]]
     gen_scn(ref, ora, "cabiscn_k16_m48", 16, 48, 0, 65536 + 2, 53,
             cfg2_pats, 24, out)
+
+    def gen_masked(*a):
+        if not only or a[2] in only:
+            _gen_masked(*a)
+    # unwanted outputs: the masks of the block calls and of the C-ABI encode
+    gen_masked(ref, ora, "mask_k4_m4", 4, 4, 0, 64, 256, 71, 12, out)
+    gen_masked(ref, ora, "mask_k4_m4_sys", 4, 4, 1, 64, 256, 72, 12, out)
 
 
 if __name__ == "__main__":

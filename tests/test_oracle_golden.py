@@ -140,6 +140,48 @@ def test_oracle_cabi_scenarios_vs_reference(name):
             C.c_size_t(B)))
 
 
+@pytest.mark.parametrize("name", golden_names("mask_"))
+def test_oracle_masks_vs_reference(name):
+    """Unwanted outputs (tests/golden/gen_golden.py `_gen_masked`): the
+    oracle's qo_encode_blocks with NULL outputs, qo_decode_blocks' `wanted`
+    and qo_fnt32_encode's `wanted_idxs` write what the reference writes,
+    leave what it leaves (the 0xA5 fill) and fill every output's mark list,
+    on the same buffers."""
+    g = load(name)
+    k, m, sys_, pkt, B, cap, md = (int(v) for v in g["params"])
+    c = codec(k, m, sys_)
+    o = oracle()
+    no = c.n_outputs
+    ew = g["enc_wanted"]
+    assert 0 < ew.sum() < no and g["oor_count"][ew == 0].sum() > 0
+    outs = np.full((no, B), 0xA5, np.uint8)
+    oor = np.zeros((no, cap), np.uint32)
+    cnt = np.zeros(no, np.uint32)
+    o.qo_encode_blocks(C.byref(c), ptrs([g["data"][i].copy() for i in range(k)]),
+                       ptrs([outs[i] if ew[i] else None for i in range(no)]),
+                       C.c_size_t(B), vp(oor), vp(cnt), C.c_uint32(cap))
+    assert (outs == g["outputs"]).all()
+    assert (outs[ew == 0] == 0xA5).all() and (outs[ew == 1] == g["full_outputs"][ew == 1]).all()
+    assert (cnt == g["oor_count"]).all() and (oor == g["oor"]).all()
+    miss, dw = g["missing"], g["dec_wanted"]
+    first = k if sys_ else 0
+    dec = [g["data"][i].copy() if sys_ and not miss[i] else np.full(B, 0xA5, np.uint8)
+           for i in range(k)]
+    par = [None if miss[first + i] else g["full_outputs"][i].copy() for i in range(no)]
+    assert o.qo_decode_blocks(C.byref(c), ptrs(dec), ptrs(par), vp(g["oor"]),
+                              vp(g["oor_count"]), C.c_uint32(cap), vp(miss), vp(dw),
+                              C.c_size_t(B)) == 1
+    assert (np.stack(dec) == g["decoded"]).all()
+    assert dw.sum() == 1 and (g["decoded"][k - 1] == g["data"][k - 1]).all()
+    assert (g["decoded"][0] == 0xA5).all()   # missing and not wanted: untouched
+    assert o.qo_metadata_size(C.c_size_t(B)) == md
+    cd = [np.concatenate([np.full(md, 0xA5, np.uint8), g["data"][i]]) for i in range(k)]
+    cp = [np.full(md + B, 0xA5, np.uint8) for _ in range(m)]
+    assert o.qo_fnt32_encode(C.byref(c), ptrs(cd), ptrs(cp), vp(ew), C.c_size_t(B)) == 0
+    assert (np.stack(cd) == g["cabi_data"]).all()
+    assert (np.stack(cp) == g["cabi_parity"]).all()
+
+
 @pytest.mark.parametrize("name", golden_names("nf4_"))
 def test_oracle_nf4_vs_reference(name):
     """RS-NF4 (src/fec_rs_nf4.h) restated as per-lane RS-FNT + (word,
