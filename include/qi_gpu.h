@@ -770,6 +770,121 @@ int qi_gpu_syndrome_locate(qi_plan* plan, const void* d_ctx, int n_checks, int m
 const char* qi_gpu_syndrome_locate_kernels(const qi_plan* plan, int n_checks, int max_errors,
                                            long long words);
 
+/* ---- Device patch: apply the fix lists of a locate to the rows and their
+ * marks.  qi_gpu_locate, qi_gpu_locate_multi and qi_gpu_syndrome_locate leave
+ * per list position a fix count and d_fixes[s][fix_cap][3]; this call consumes
+ * them on the device, so that verify -> locate -> patch -> decode / repair is
+ * a chain of asynchronous calls on one stream.  The rule is that of the host
+ * facade (qi_fec_locate_multi_blocks with `correct`, qi_fec_apply_deltas), per
+ * stripe, over the unordered device buckets.
+ *
+ * Any plan qi_plan_create accepts (any k, both code types); there is no
+ * context.  d_ids are the n_listed = N ids that were given to the locate's
+ * context, 1 <= N <= k + m.
+ *
+ * List position s owns d_ids[s * N ..], d_mine[s * N ..], d_unlocated[s],
+ * d_fix_counts[s], d_fixes[s], d_status[s] and d_applied[s], and patches the
+ * rows and buckets of stripe d_stripes[s] (d_stripes NULL: of stripe s).  Two
+ * list positions that name the same stripe in one call are undefined, and so
+ * is an id that d_ids[s * N ..] holds twice (two positions would share one row
+ * and one bucket); both stay inside the caller's rows and inside each bucket's
+ * oor_cap entries.  Rows and buckets are addressed by fragment id exactly as
+ * qi_gpu_decode addresses received rows: d_data for f < k of a systematic
+ * plan, d_coded by slot otherwise, the buckets with slots = n_outputs.  d_data
+ * may be NULL for a non-systematic plan; a systematic plan may pass NULL for a
+ * region none of its applied fixes touches.  Any positive strides with a unit
+ * inner stride, at any 2-byte alignment.
+ *
+ * The fixes of a stripe are its first min(d_fix_counts[s], fix_cap) entries
+ * {column, position p, third word}.  A fix with d_mine[s * N + p] == 0 is
+ * skipped (the holder's rule of qi_fec_apply_deltas: another node holds that
+ * fragment): only p < N is checked of it, and it is not counted.  For every
+ * other fix let y be the restored symbol of the row at the column: 65536
+ * where the column is in the row's bucket, else the stored word (a systematic
+ * data row has no bucket; with NULL counts nothing is marked).  Then
+ *   QI_PATCH_ABSOLUTE  v = the third word, valid in [0, 65536];
+ *   QI_PATCH_DELTA     e = the third word, valid in [1, 65536], and
+ *                      v = (y - e) mod 65537.
+ * The row's word becomes v & 0xffff and the column is in the row's bucket
+ * afterwards iff v == 65536: inserted if it was absent, removed if it was
+ * present and v != 65536, the bucket untouched otherwise.  Buckets stay
+ * unordered, their counts exact, without duplicates.  Rows, words and buckets
+ * that no applied fix names are not written.
+ *
+ * All or nothing per stripe.  d_status[s] is the smallest of these codes that
+ * applies; a stripe with one of them is left byte for byte as it was, rows
+ * and buckets, with d_applied[s] = 0:
+ *   QI_PATCH_UNLOCATED    d_unlocated is not NULL and d_unlocated[s] != 0;
+ *   QI_PATCH_TRUNCATED    d_fix_counts[s] > fix_cap: entries were dropped; or
+ *                         d_fix_counts[s] > QI_PATCH_MAX_FIXES, the longest
+ *                         list one call applies to a stripe, whatever fix_cap;
+ *   QI_PATCH_BAD_FIX      a position >= N; in a fix that is not skipped a
+ *                         column >= words, a third word out of range, an id
+ *                         >= k + m or an id in a region passed as NULL; a
+ *                         touched bucket whose count is already above oor_cap
+ *                         (this also raises bit 1 of qi_gpu_take_error);
+ *   QI_PATCH_DATA_MARK    a systematic data row would have to hold 65536;
+ *   QI_PATCH_BUCKET_FULL  a touched bucket's new count would exceed oor_cap
+ *                         (NULL counts: any v == 65536 on a coded row).
+ * Otherwise d_status[s] = QI_PATCH_DONE and d_applied[s] is the number of
+ * fixes applied, or QI_PATCH_NONE when that number is 0 (an empty list, or
+ * every fix skipped).  A (position, column) pair named twice in one list
+ * leaves that stripe unspecified, but the call stays inside the caller's rows
+ * and inside each bucket's oor_cap entries.  The new count is what decides:
+ * a bucket at oor_cap that loses one mark and gains one in the same list is
+ * patched, and no entry is ever written at or past oor_cap.
+ *
+ * A NULL plan, a mode that is not one of the two, n_listed outside 1 .. k + m,
+ * fix_cap < 0, words outside 1 .. 2^32 or n_stripes < 1 return -1 and launch
+ * nothing (the bytes call 0, the kernels call "").  So do, as in the sibling
+ * calls, a NULL d_ids, d_fix_counts, d_work, d_status or d_applied, NULL
+ * d_fixes with fix_cap > 0, oor_cap < 0, counts without entries at oor_cap >
+ * 0, and a negative stride of a region that is passed.  fix_cap == 0: every
+ * stripe gets QI_PATCH_NONE, or QI_PATCH_TRUNCATED where its count is not 0;
+ * d_fixes may then be NULL.
+ *
+ * Everything is asynchronous on `stream`: no host tables, no blocking copy.
+ * d_work is scratch of qi_gpu_patch_work_bytes bytes (per stripe and position
+ * the marks inserted and removed and the bucket's editing lane); it needs no
+ * clearing, and only one call at a time may use a given work buffer.
+ *
+ * Decode and repair contexts hold the marks of the buckets they were built
+ * from (the route tables): after a patch that changed a bucket they are stale
+ * and must be rebuilt before the healed rows are decoded. */
+#define QI_PATCH_ABSOLUTE 0   /* fixes {column, position, v}: qi_gpu_locate, qi_gpu_locate_multi */
+#define QI_PATCH_DELTA    1   /* fixes {column, position, e}: qi_gpu_syndrome_locate              */
+
+/* per-stripe status */
+#define QI_PATCH_NONE            0  /* nothing to apply                                   */
+#define QI_PATCH_DONE            1
+#define QI_PATCH_UNLOCATED       2  /* d_unlocated[s] != 0                                */
+#define QI_PATCH_TRUNCATED       3  /* d_fix_counts[s] > fix_cap (entries were dropped), or
+                                     * > QI_PATCH_MAX_FIXES                                */
+#define QI_PATCH_BAD_FIX         4  /* see above                                          */
+#define QI_PATCH_DATA_MARK       5  /* a systematic data row would have to hold 65536     */
+#define QI_PATCH_BUCKET_FULL     6  /* a bucket would grow past oor_cap (NULL counts: past 0) */
+
+/* the longest list one call applies to a stripe (one bit of a block's LDS per entry);
+ * fix_cap itself, the stride of d_fixes, is not bounded */
+#define QI_PATCH_MAX_FIXES 262144
+
+size_t qi_gpu_patch_work_bytes(const qi_plan* plan, int n_listed, int n_stripes);
+int qi_gpu_patch(qi_plan* plan, int mode,
+                 const uint16_t* d_ids /*[S][N] as given to the locate context*/, int n_listed,
+                 const uint8_t* d_mine /*[S][N] or NULL: 0 = not held here, skip*/,
+                 const uint32_t* d_stripes /*[S] or NULL, as qi_gpu_locate*/,
+                 const uint32_t* d_unlocated /*[S] or NULL*/,
+                 const uint32_t* d_fix_counts /*[S]*/, const uint32_t* d_fixes /*[S][fix_cap][3]*/,
+                 int fix_cap,
+                 uint16_t* d_data, long long dss, long long drs,
+                 uint16_t* d_coded, long long css, long long crs,
+                 uint32_t* d_oor_counts, uint32_t* d_oor_entries, int oor_cap,
+                 void* d_work, uint32_t* d_status /*[S]*/, uint32_t* d_applied /*[S]*/,
+                 long long words, int n_stripes, void* stream);
+/* "patch=<kernel>"; "" for arguments out of range.  Per calling thread, valid
+ * until its next call. */
+const char* qi_gpu_patch_kernels(const qi_plan* plan, int n_listed, int mode, long long words);
+
 /* Build identification: "<git describe>+src:<hash of the library sources>". */
 const char* qi_build_id(void);
 

@@ -96,6 +96,10 @@ def _declare(lib):
         "qi_gpu_syndrome_locate": (I, [V, V, I, I, V, LL, LL, V, V, I, V, V, V, V, V, I,
                                        LL, I, V]),
         "qi_gpu_syndrome_locate_kernels": (C.c_char_p, [V, I, I, LL]),
+        "qi_gpu_patch_work_bytes": (SZ, [V, I, I]),
+        "qi_gpu_patch": (I, [V, I, V, I, V, V, V, V, V, I, V, LL, LL, V, LL, LL, V, V, I, V, V, V,
+                             LL, I, V]),
+        "qi_gpu_patch_kernels": (C.c_char_p, [V, I, I, LL]),
         "qi_gpu_take_error": (I, [V]),
         "qi_build_id": (C.c_char_p, []),
         "qi_gpu_kernels": (C.c_char_p, [V, LL]),
@@ -965,6 +969,87 @@ class Plan:
             work.data_ptr(), fp.data_ptr(), words, S, self._stream(stream))
         if rc:
             raise RuntimeError(f"qi_gpu_fingerprint failed: {rc}")
+        return lib().qi_gpu_take_error(self.h) if check else 0
+
+    PATCH_ABSOLUTE, PATCH_DELTA = 0, 1  # QI_PATCH_ABSOLUTE, QI_PATCH_DELTA
+    # QI_PATCH_* per-stripe status
+    (PATCH_NONE, PATCH_DONE, PATCH_UNLOCATED, PATCH_TRUNCATED, PATCH_BAD_FIX, PATCH_DATA_MARK,
+     PATCH_BUCKET_FULL) = range(7)
+    PATCH_MAX_FIXES = 262144  # QI_PATCH_MAX_FIXES
+
+    def patch_kernels(self, n_listed, mode, words):
+        """'patch=<kernel>' (qi_gpu_patch_kernels); '' for arguments out of
+        range."""
+        return lib().qi_gpu_patch_kernels(self.h, n_listed, mode, words).decode()
+
+    def patch_work_bytes(self, n_listed, n_stripes):
+        """Bytes of the work buffer of a patch (0: arguments out of range)."""
+        return lib().qi_gpu_patch_work_bytes(self.h, n_listed, n_stripes)
+
+    def patch(self, mode, ids, fix_counts, fixes, fix_cap, coded, status, applied, work,
+              data=None, mine=None, stripes=None, unlocated=None, counts=None, entries=None,
+              cap=0, stream=None, check=True):
+        """Apply a locate's fix lists to the rows and buckets (qi_gpu_patch).
+        mode: PATCH_ABSOLUTE for the lists of locate / locate_multi,
+        PATCH_DELTA for syndrome_locate's.  ids: int16 [S, N], the ids given
+        to the locate's context; fix_counts [S], fixes [S, fix_cap, 3] and
+        unlocated [S] as the locate left them; mine: uint8 [S, N], 0 = that
+        fragment is not held here.  coded: [S_all, n_out, P] with its buckets
+        counts / entries, data: [S_all, k, P] for systematic codes (either may
+        be None when no applied fix lives there); stripes as for locate.
+        status and applied: int32 [S], written by the call; work: uint8 of
+        patch_work_bytes(N, S).  All or nothing per stripe.  Returns the
+        sticky error flags when check."""
+        import torch
+        if mode not in (self.PATCH_ABSOLUTE, self.PATCH_DELTA):
+            raise ValueError("patch: mode must be PATCH_ABSOLUTE or PATCH_DELTA")
+        if ids.dim() != 2:
+            raise ValueError("ids: expected [S, N]")
+        S, N = ids.shape
+        S_all = P = None
+        for t, name, rows in ((coded, "coded", self.n_outputs), (data, "data", self.k)):
+            if t is None:
+                continue
+            _rows(t, name, rows, S_all)
+            if P is not None and t.shape[2] != P:
+                raise ValueError("data and coded differ in width")
+            S_all, P = t.shape[0], t.shape[2]
+        if P is None or (coded is None and not self.sys):
+            raise ValueError("no rows given")
+        if data is not None and not self.sys:
+            data = None
+        if stripes is not None:
+            _flat(stripes, "stripes", S, (torch.int32,))
+            if stripes.numel() != S:
+                raise ValueError(f"stripes: expected {S} list positions")
+            if check and S > 0 and not (0 <= int(stripes.min()) and int(stripes.max()) < S_all):
+                raise ValueError(f"stripes: values must lie in [0, {S_all})")
+        elif S != S_all:
+            raise ValueError(f"ids: expected {S_all} stripes, got {S}")
+        need = self.patch_work_bytes(N, S)
+        if need == 0:
+            raise ValueError("patch: n_listed out of range (1 .. k + m), or no stripe")
+        if fix_cap < 0 or (fix_cap > 0 and fixes is None):
+            raise ValueError("fix_cap > 0 needs fixes")
+        _flat(ids, "ids", S * N, (torch.int16, torch.uint16))
+        _flat(mine, "mine", S * N, (torch.uint8,))
+        _flat(unlocated, "unlocated", S, (torch.int32,))
+        for t, name in ((fix_counts, "fix_counts"), (status, "status"), (applied, "applied")):
+            if t is None:
+                raise ValueError(f"{name}: required")
+            _flat(t, name, S, (torch.int32,))
+        _flat(fixes, "fixes", S * fix_cap * 3, (torch.int32,))
+        if work is None:
+            raise ValueError("work: required")
+        _flat(work, "work", need, (torch.uint8,))
+        _oor(counts, entries, cap, S_all, self.n_outputs)
+        rc = lib().qi_gpu_patch(
+            self.h, int(mode), ids.data_ptr(), N, _ptr(mine), _ptr(stripes), _ptr(unlocated),
+            fix_counts.data_ptr(), _ptr(fixes), int(fix_cap), *_row_args(data),
+            *_row_args(coded), _ptr(counts), _ptr(entries), int(cap), work.data_ptr(),
+            status.data_ptr(), applied.data_ptr(), P, S, self._stream(stream))
+        if rc:
+            raise RuntimeError(f"qi_gpu_patch failed: {rc}")
         return lib().qi_gpu_take_error(self.h) if check else 0
 
     def take_error(self):

@@ -13,6 +13,7 @@
 #include "locate_math.h"
 #include "locate_multi_math.h"
 #include "partial_math.h"
+#include "patch_math.h"
 #include "qi_internal.h"
 #include "qi_plan.h"
 #include "syndrome_math.h"
@@ -882,6 +883,60 @@ const char* qi_gpu_syndrome_locate_kernels(const qi_plan* p, int R, int t, long 
         return "";
     names = "syndrome_locate=" + syndrome_locate_ctx_kernel_name() + " + " +
             syndrome_locate_kernel_name(syndrome_locate_rp(R), true);
+    return names.c_str();
+}
+
+// ---- device patch: patch_kernel applies the fix lists of a locate to the rows
+// and the buckets, one block per list position (patch.hip, patch_math.h) ----
+static_assert(QI_PATCH_ABSOLUTE == kPatchAbsolute && QI_PATCH_DELTA == kPatchDelta &&
+                  QI_PATCH_NONE == kPatchNone && QI_PATCH_DONE == kPatchDone &&
+                  QI_PATCH_UNLOCATED == kPatchUnlocated && QI_PATCH_TRUNCATED == kPatchTruncated &&
+                  QI_PATCH_BAD_FIX == kPatchBadFix && QI_PATCH_DATA_MARK == kPatchDataMark &&
+                  QI_PATCH_BUCKET_FULL == kPatchBucketFull &&
+                  QI_PATCH_MAX_FIXES == kPatchMaxFixes,
+              "qi_gpu.h and patch_math.h differ");
+
+static bool patch_ok(const qi_plan* p, int N)
+{
+    return p && N >= 1 && N <= p->code_len;
+}
+
+size_t qi_gpu_patch_work_bytes(const qi_plan* p, int N, int n_stripes)
+{
+    if (!patch_ok(p, N) || n_stripes < 1)
+        return 0;
+    return static_cast<size_t>(patch_work_words(N, n_stripes)) * sizeof(uint32_t);
+}
+
+int qi_gpu_patch(qi_plan* p, int mode, const uint16_t* d_ids, int N, const uint8_t* d_mine,
+                 const uint32_t* d_stripes, const uint32_t* d_unlocated,
+                 const uint32_t* d_fix_counts, const uint32_t* d_fixes, int fix_cap,
+                 uint16_t* d_data, long long dss, long long drs, uint16_t* d_coded, long long css,
+                 long long crs, uint32_t* d_counts, uint32_t* d_entries, int cap, void* d_work,
+                 uint32_t* d_status, uint32_t* d_applied, long long words, int n_stripes,
+                 void* stream)
+{
+    if (!patch_ok(p, N) || (mode != QI_PATCH_ABSOLUTE && mode != QI_PATCH_DELTA) || fix_cap < 0 ||
+        words < 1 || words > (1LL << 32) || n_stripes < 1)
+        return -1;
+    if (!d_ids || !d_fix_counts || (fix_cap > 0 && !d_fixes) || !d_work || !d_status ||
+        !d_applied || cap < 0 || (d_counts && cap > 0 && !d_entries) ||
+        (d_data && (dss < 0 || drs < 0)) || (d_coded && (css < 0 || crs < 0)))
+        return -1;
+    const Oor marks{d_counts, d_entries, p->n_outputs, cap};
+    return launch_patch(mode, p->sys, p->k, p->code_len, d_ids, N, d_mine, d_stripes, d_unlocated,
+                        d_fix_counts, d_fixes, fix_cap, p->sys ? d_data : nullptr, dss, drs,
+                        d_coded, css, crs, marks, static_cast<uint32_t*>(d_work), d_status,
+                        d_applied, words, n_stripes, p->d_err, st(stream));
+}
+
+const char* qi_gpu_patch_kernels(const qi_plan* p, int N, int mode, long long words)
+{
+    static thread_local std::string names;
+    if (!patch_ok(p, N) || (mode != QI_PATCH_ABSOLUTE && mode != QI_PATCH_DELTA) || words < 1 ||
+        words > (1LL << 32))
+        return "";
+    names = "patch=" + patch_kernel_name();
     return names.c_str();
 }
 

@@ -407,6 +407,19 @@ std::string syndrome_ctx_kernel_name();
 std::string syndrome_locate_ctx_kernel_name();
 std::string syndrome_locate_kernel_name(int RP, bool vec);
 
+// the device patch (patch.hip, patch_math.h): the fix lists of n_stripes list
+// positions applied to the rows and the coded rows' buckets `marks` (counts
+// null: no marks), all or nothing per stripe; d_work: patch_work_words(N,
+// n_stripes) u32.  The caller checks the ranges
+int launch_patch(int mode, int sys, int k, int code_len, const uint16_t* d_ids, int N,
+                 const uint8_t* d_mine, const uint32_t* d_stripes, const uint32_t* d_unlocated,
+                 const uint32_t* d_fix_counts, const uint32_t* d_fixes, int fix_cap,
+                 uint16_t* d_data, long long dss, long long drs, uint16_t* d_coded, long long css,
+                 long long crs, const Oor& marks, uint32_t* d_work, uint32_t* d_status,
+                 uint32_t* d_applied, long long words, int n_stripes, uint32_t* d_err,
+                 hipStream_t st);
+std::string patch_kernel_name();
+
 // whether launch_matrix runs these rows on the matrix cores (whole
 // kRouteTile tiles): 8-byte aligned rows inside 31-bit buffer ranges.  The
 // kin > 256 layouts have no other kernel, so their callers check this first.
